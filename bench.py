@@ -14,6 +14,12 @@ Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 one process p
 under the driver's torch.distributed.run or started by bench.py itself (a child
 torch.distributed.run) when WORLD_SIZE is unset; RCCL carries only the barrier and the max-time
 reduction (the stripes need no data exchange).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes
+work of its own: the CPU baseline (the reference / the oracle timed on the host), the output
+check against the golden hashes and the --verify-launches repeated launches; without it
+`cpu_baseline` and `output_check` are null.
+--dump-outputs DIR writes the last timed step's output (a fixed sample of it) as DIR/*.npy.
 """
 from __future__ import annotations
 
@@ -240,6 +246,26 @@ def repeat_check(step, d_out, launches, world, device):
     return {"repeat_launches": int(n[0]), "repeat_launches_differing": int(n[1])}
 
 
+DUMP_MAX_BLOCKS = 131072       # x 64 coefficients x 4 B (float32) = 32 MiB, over all ranks
+
+
+def dump_outputs(path, d_out, name, max_blocks=DUMP_MAX_BLOCKS):
+    """--dump-outputs: the coefficients the last timed step left in d_out [B, blocks, 64], as
+    float32 in path/<name>.npy.  More than max_blocks blocks (the default workload has
+    3.1 M, 398 MB of int16): a fixed sample of them, the same (frame, block) positions in every
+    run of the same shape (numpy's PCG64 seeded with 0, ascending), gathered on the GPU.  Every
+    rank of N writes its own file and passes DUMP_MAX_BLOCKS // N: 32 MiB in all."""
+    import numpy as np
+    import torch
+    flat = d_out.view(-1, 64)
+    n = flat.shape[0]
+    if n > max_blocks:
+        idx = np.sort(np.random.default_rng(0).choice(n, max_blocks, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, name + ".npy"), flat.to(torch.float32).cpu().numpy())
+
+
 ALT_LIB = os.path.join(REPO, "jpeg-encoder-and-decoder_amd", "lib", "libjpgx_alt.so")
 
 
@@ -319,11 +345,19 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--quality", type=int, default=90)
     ap.add_argument("--sample-ratio", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the CPU baseline, the output "
+                         "check against the golden hashes and the --verify-launches repeated launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's output coefficients "
+                         "(float32; a fixed sample of the blocks when there are more than "
+                         f"{DUMP_MAX_BLOCKS}) to DIR/coefficients.npy")
     ap.add_argument("--verify-launches", type=int, default=256,
-                    help="after the timed region and the golden check, this many more launches "
-                         "compared with the checked output on the GPU (0 = off)")
+                    help="with --full: after the timed region and the golden check, this many more "
+                         "launches compared with the checked output on the GPU (0 = off)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
     ap.add_argument("--kernel", choices=["xform", "mx"], default=None,
                     help="4:4:4 transform kernel: k_mxs (the product: colour and row DCT on the "
                          "matrix cores) or k_xform (all-VALU, from the test-only cross-check "
@@ -486,8 +520,14 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     achieved = bytes_per_px * px_rank_step / (xform_ms * 1e-3) / 1e9
 
-    check = check_output(d_out, plan, W, H, q, args.subsample, world, cdev, jpgx)
-    if args.verify_launches > 0:
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out,
+                     "coefficients" if world == 1 else f"coefficients_rank{rank}",
+                     DUMP_MAX_BLOCKS // world)
+    check = None
+    if args.full:
+        check = check_output(d_out, plan, W, H, q, args.subsample, world, cdev, jpgx)
+    if args.full and args.verify_launches > 0:
         rep = repeat_check(step, d_out, args.verify_launches, world, cdev)
         if check is None:          # no committed golden at this config: self-consistency only
             check = {"frames_checked": 0, "ok": True,
@@ -497,7 +537,7 @@ def main():
     if rank == 0:
         t_ratio, t_src = measured_traffic(kname) if not args.subsample else (None, None)
         cpu = None
-        if N == 1 and not args.no_cpu_baseline:
+        if args.full and N == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(W, H, q, args.cpu_seconds, jpgx)
         line = {
             "metric": METRIC if not args.subsample else
@@ -516,7 +556,8 @@ def main():
                        "global_batch_frames": B, "width": W, "height": H, "quality": q,
                        "sample_ratio": args.sample_ratio, "parallelism": f"stripes{N}",
                        "collectives": ("none" if N == 1 else
-                                       f"{backend}: barrier, max-time, output check"),
+                                       f"{backend}: barrier, max-time"
+                                       + (", output check" if args.full else "")),
                        "kernel_timing": ("per-launch kernel begin/end HIP events (hipExtLaunchKernel)"
                                          if launch_ms else "HIP events around the K launches on their stream"),
                        "launch": launch_mode,

@@ -26,7 +26,7 @@ def test_bench_single_gpu_line(launch):
     """The timed K launches as one HIP-graph replay (default) or K eager launches: either way the
     last timed launch's output is checked against the golden hashes."""
     r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--launch", launch,
-                        "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=240)
+                        "--full", "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert d["config"]["launch"] == {"graph": "hip-graph", "eager": "eager"}[launch]
@@ -43,7 +43,7 @@ def test_bench_two_ranks_rehearsal():
     env = dict(os.environ, JPGX_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--frames-per-gpu", "2"], cwd=REPO, env=env, capture_output=True,
+                        "--full", "--frames-per-gpu", "2"], cwd=REPO, env=env, capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)

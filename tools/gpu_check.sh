@@ -12,10 +12,10 @@ echo "pytest rc=$rc"; tail -25 "$OUT/pytest_gpu.log"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1; rc=$?
 echo "smoke rc=$rc"; tail -3 "$OUT/smoke.log"; [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-timeout -k 10 400 python bench.py --steps $STEPS --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
+timeout -k 10 400 python bench.py --full --steps $STEPS --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"; rc=$?
 echo "bench rc=$rc"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"; [ $rc -eq 0 ] || exit $rc
 if [ "${PROF:-1}" = "1" ]; then
   cd /tmp
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python "$ROOT/bench.py" --steps $STEPS --warmup 5 --no-cpu-baseline > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; rc=$?
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python "$ROOT/bench.py" --steps $STEPS --warmup 5 > "$OUT/prof_bench.json" 2> "$OUT/prof.err"; rc=$?
   echo "rocprof rc=$rc"; find "$OUT/prof" -name "*stats*" | head; [ $rc -eq 0 ] || exit $rc
 fi
