@@ -63,10 +63,10 @@ struct jx_limtab {
 
 #define JX_MAXQ 97
 
-/* k_mx (csrc/jpgx_mx.hip): the colour conversion + row DCT of each pixel row is one f16 MFMA
- * product with B split into JX_MX_PARTS f16 parts (hi exact, lo parts scaled by 2^12).  Per
- * quality, plan column n = 8c + u holds the scales and guard band of coefficients (c, u,
- * v = 0..7). */
+/* k_mxs, k_mxs422, k_mxs420 (csrc/jpgx_mx.hip): the colour conversion + row DCT of each pixel row
+ * is an f16 MFMA product with B split into JX_MX_PARTS f16 parts (hi exact, lo parts scaled by
+ * 2^JX_MX_LOEXP).  Per quality, plan column n = 8c + u holds the scales and guard band of
+ * coefficients (c, u, v = 0..7). */
 #ifndef JX_MX_PARTS
 #define JX_MX_PARTS 2       /* 2: hi + one lo part (band 1.28x that of 3 parts, 16 MFMAs per
                                8 blocks instead of 24: jpgx_plan.cpp's bound covers either) */
@@ -106,24 +106,25 @@ void jx_under_dwords(const uint8_t under[3][8], uint32_t out[6]);
 long long jx_selftest_pk(long long nblocks, unsigned long long seed);
 int jx_mx_parts(void);
 int jx_mx_loexp(void);
-/* k_mx: tables and f16 B operands (host plan), launch (device side) */
+/* the MFMA kernels' host plan: per-quality tables, f16 B operands and the band's emulation
+ * self-test for k_mxs (4:4:4: operands [3 part + which][lane]), k_mxs422 and k_mxs420 (true
+ * 4:2:2 / 4:2:0: operands [part][which][lane]) */
 int jx_plan_tables_mx(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
+int jx_plan_tables_mx422(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
+int jx_plan_tables_mx420(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
 int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8]);
+int jx_mx422_operands(uint16_t ops[JX_MX_PARTS][4][64][8]);
+int jx_mx420_operands(uint16_t ops[JX_MX_PARTS][5][64][8]);
 long long jx_selftest_mx(long long nblocks, unsigned long long seed, int quality,
                          long long *flagged, double *ratio);
-int jx_launch_mx(const struct jx_xform_args *xa, void *stream, void *ev_start, void *ev_stop);
-/* k_mx422 (true 4:2:2 on the matrix cores): operands [part][which][lane], tables, launch */
-int jx_mx422_operands(uint16_t ops[JX_MX_PARTS][4][64][8]);
-int jx_plan_tables_mx422(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
 long long jx_selftest_mx422(long long nblocks, unsigned long long seed, int quality,
                             long long *flagged, double *ratio);
-int jx_launch_mx422(const struct jx_xform_args *xa, void *stream, void *ev_start, void *ev_stop);
-/* k_mx420 (true 4:2:0 on the matrix cores): operands [part][which][lane], tables, launch */
-int jx_mx420_operands(uint16_t ops[JX_MX_PARTS][5][64][8]);
-int jx_plan_tables_mx420(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
 long long jx_selftest_mx420(long long nblocks, unsigned long long seed, int quality,
                             long long *flagged, double *ratio);
-int jx_launch_mx420(const struct jx_xform_args *xa, void *stream, void *ev_start, void *ev_stop);
+/* device side (jpgx_mx.hip): launch the kernel of sample ratio sr (0: k_mxs, 1: k_mxs422,
+ * 2: k_mxs420); the workgroup image it would upload for (force, quality), host only */
+int jx_launch_mx(const struct jx_xform_args *xa, int sr, void *stream, void *ev_start, void *ev_stop);
+long long jx_mx_image(int sr, int force, int quality, void *dst, long long cap);
 #ifdef __cplusplus
 }
 #endif

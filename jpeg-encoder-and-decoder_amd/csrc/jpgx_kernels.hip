@@ -812,8 +812,8 @@ int resident_waves()
     return g_resident_waves[dev];
 }
 
-/* Dispatch.  The product library (libjpgx.so) runs one kernel per mode: k_mx for 4:4:4,
- * k_mx422 / k_mx420 for true 4:2:2 / 4:2:0.  The test-only cross-check library
+/* Dispatch.  The product library (libjpgx.so) runs one kernel per mode (jx_launch_mx): k_mxs for
+ * 4:4:4, k_mxs422 / k_mxs420 for true 4:2:2 / 4:2:0.  The test-only cross-check library
  * (libjpgx_alt.so, built from the same sources with -DJPGX_ALT_DISPATCH) runs the second
  * implementations instead: k_xform for 4:4:4 and k_xform (Y) + k_chroma<1|2> for true 4:2:x. */
 #ifndef JPGX_ALT_DISPATCH
@@ -911,29 +911,17 @@ static int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t
     xa.force_exact = (p->flags & JPGX_FLAG_FORCE_EXACT) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     xa.luma_only = sub ? 1 : 0;
-    if (!sub && !kAltDispatch) {
-        /* k_mx: colour + row DCT on the matrix cores, exact pass inside (csrc/jpgx_mx.hip) */
-        rc = jx_launch_mx(&xa, stream, ev_start, ev_stop);
-        if (rc) return rc;
-        if (event_after) rc = hip_rc(hipEventRecord((hipEvent_t)event_after, s));
+    if (!kAltDispatch) {
+        /* one pass on the matrix cores, exact pass inside (csrc/jpgx_mx.hip): k_mxs, or k_mxs422 /
+         * k_mxs420 for true 4:2:2 / 4:2:0 */
+        rc = jx_launch_mx(&xa, sub ? p->sample_ratio : 0, stream, ev_start, ev_stop);
+        if (!rc && event_after) rc = hip_rc(hipEventRecord((hipEvent_t)event_after, s));
         return rc;
     }
     /* k_xform: persistent, one wave per resident slot (at most one per tile) */
     const size_t ntiles = (total + 63) / 64;
     const size_t waves = std::min<size_t>(ntiles, (size_t)std::max(resident_waves(), 4));
     const unsigned grid = (unsigned)((waves + JX_WG / 64 - 1) / (JX_WG / 64));
-    if (sub && p->sample_ratio == 2 && !kAltDispatch) {
-        /* true 4:2:0 in one pass on the matrix cores (k_mx420, csrc/jpgx_mx.hip) */
-        rc = jx_launch_mx420(&xa, stream, ev_start, ev_stop);
-        if (!rc && event_after) rc = hip_rc(hipEventRecord((hipEvent_t)event_after, s));
-        return rc;
-    }
-    if (sub && p->sample_ratio == 1 && !kAltDispatch) {
-        /* true 4:2:2 in one pass on the matrix cores (k_mx422, csrc/jpgx_mx.hip) */
-        rc = jx_launch_mx422(&xa, stream, ev_start, ev_stop);
-        if (!rc && event_after) rc = hip_rc(hipEventRecord((hipEvent_t)event_after, s));
-        return rc;
-    }
     if (ev_start) {                                   /* the test library: events around its kernels */
         rc = hip_rc(hipEventRecord((hipEvent_t)ev_start, s));
         if (rc) return rc;

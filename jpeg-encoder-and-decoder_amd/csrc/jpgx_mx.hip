@@ -2082,16 +2082,20 @@ static void mx_fill_recip(jx_mxtab &t)
             }
 }
 
-/* the per-quality tables of one kernel family ([force][quality]): scales w (2^9 folded, kRScale),
- * squared band limits (all -1 under FORCE_EXACT), divisors and the fast decision's reciprocals */
-template <class Plan>
-int mx_plan_tabs(std::vector<jx_mxtab> &tab, Plan plan)
+/* the host plan's tables of plan mode 0 (k_mxs), 1 (k_mxs422), 2 (k_mxs420) */
+typedef int (*mx_plan_fn)(int, float[24][8], float[24][8], int16_t[2][64]);
+constexpr mx_plan_fn kMxPlan[3] = {jx_plan_tables_mx, jx_plan_tables_mx422, jx_plan_tables_mx420};
+
+/* the per-quality tables of one plan mode ([force][quality], qualities qlo..qhi filled): scales w
+ * (2^9 folded, kRScale), squared band limits (all -1 under FORCE_EXACT), divisors and the fast
+ * decision's reciprocals */
+int mx_plan_tabs(std::vector<jx_mxtab> &tab, int mode, int qlo, int qhi)
 {
     tab.assign(2 * (JX_MAXQ + 1), jx_mxtab{});
-    for (int q = 1; q <= JX_MAXQ; q++) {
+    for (int q = qlo; q <= qhi; q++) {
         float w[24][8], lim[24][8];
         int16_t qq[2][64];
-        const int rc = plan(q, w, lim, qq);
+        const int rc = kMxPlan[mode](q, w, lim, qq);
         if (rc) return rc;
         for (int f = 0; f < 2; f++) {
             jx_mxtab &t = tab[f * (JX_MAXQ + 1) + q];
@@ -2143,141 +2147,141 @@ void mx_ex_tab(MxExTab &x, const jx_mxtab &t)
     memcpy(x.r_, t.r, sizeof t.r);
 }
 
-std::once_flag g_mx_once[kMaxDev];
-int g_mx_rc[kMaxDev];
+/* ---- the three kernels, as the host sees them ------------------------------------------------
+ * One description per kernel: its workgroup image and plan mode, the plan column of table tt at
+ * lane profile jp (mx_layout_tab), the plan's operand tiles ([tiles * part + which][lane][e]; the
+ * tiles pair, pair + 1 hold one matrix for block set 0 / set 1 in C columns 0..7 / 8..15 and must be
+ * zero in the other half: the kernels' K-concatenated sums are exact because of it), how table and
+ * operands land in the image and on the device, and the launch shape: waves per workgroup, and a
+ * wave's share per_wave of the stripe's work units of `unit` blocks each (a block, or a 16 x 16
+ * MCU's four: the 4:2:0 stripe is an even number of block rows). */
+typedef uint16_t mx_tile[64][8];
 
+/* k_mxs: 4:4:4 / reference-parity output.  The table is Y|Cb at 16 lane profiles with Cr compacted
+ * to 8 (MxsTab); the operands stay outside the image (g_mxs_B: Y|Cb, Cr set 0, Cr set 1). */
+struct MxsK {
+    typedef MxsImg Img;
+    static constexpr const char *name = "k_mxs";
+    static constexpr int mode = 0;
+    static constexpr unsigned tiles = 3, pair = 1, wpg = kMxsWPG, unit = 1, per_wave = 8 * kMxsC;
+    static auto kernel() { return k_mxs; }
+    static auto &symbol() { return g_mxs_img; }
+    static unsigned ncol(unsigned tt, unsigned jp) { return tt < 2 ? jp : 16u + (jp & 7u); }
+    static int operands(mx_tile *ops) { return jx_mx_operands(ops); }
+    static void land(Img &I, const MxTab &full, const mx_tile *)
+    {
+        for (unsigned jp = 0; jp < 16; jp++)
+            for (int tt = 0; tt < 2; tt++)
+                for (int h = 0; h < 2; h++) {
+                    I.tab.yc[tt][h][jp] = full.wl[tt][h][jp];
+                    if (jp < 8) I.tab.cr[tt][h][jp] = full.wl[2 + tt][h][jp];
+                }
+    }
+    static hipError_t upload_operands(const mx_tile *ops)
+    {
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_mxs_B), ops, sizeof(mx_tile) * tiles * JX_MX_PARTS);
+    }
+};
+
+/* k_mxs422 / k_mxs420 (true 4:2:2 / 4:2:0: Y [nb][64], Cb and Cr [nb / 2][64] or [nb / 4][64] per
+ * frame).  The table is Y at plan column j % 8, chroma at 8 + j; the image holds per part the two Y
+ * sets' operands merged (lane l keeps set (l & 15) / 8's, the kernel rebuilds the zeros) and the
+ * chroma K steps. */
+template <class ImgT, int SUB>
+struct MxsSubK {
+    typedef ImgT Img;
+    static constexpr int mode = SUB;
+    static constexpr unsigned tiles = 3 + SUB, pair = 0;
+    static unsigned ncol(unsigned tt, unsigned jp) { return tt < 2 ? (jp & 7u) : 8u + jp; }
+    static void land(Img &I, const MxTab &full, const mx_tile *ops)
+    {
+        I.tab = full;
+        for (unsigned p = 0; p < JX_MX_PARTS; p++)
+            for (unsigned l = 0; l < 64; l++) {
+                memcpy(&I.B[(tiles - 1) * p][l], ops[tiles * p + ((l & 15u) < 8 ? 0 : 1)][l], 16);
+                for (unsigned w = 2; w < tiles; w++) memcpy(&I.B[(tiles - 1) * p + w - 1][l], ops[tiles * p + w][l], 16);
+            }
+    }
+    static hipError_t upload_operands(const mx_tile *) { return hipSuccess; }      /* they are in the image */
+};
+
+struct Mxs422K : MxsSubK<MxsImg422, 1> {
+    static constexpr const char *name = "k_mxs422";
+    static constexpr unsigned wpg = kMxs422WPG, unit = 1, per_wave = 8 * kMxs422C;
+    static auto kernel() { return k_mxs422; }
+    static auto &symbol() { return g_mxs422_img; }
+    static int operands(mx_tile *ops) { return jx_mx422_operands((uint16_t(*)[4][64][8])ops); }
+};
+
+struct Mxs420K : MxsSubK<MxsImg420, 2> {
+    static constexpr const char *name = "k_mxs420";
+    static constexpr unsigned wpg = kMxs420WPG, unit = 4, per_wave = 8;
+    static auto kernel() { return k_mxs420; }
+    static auto &symbol() { return g_mxs420_img; }
+    static int operands(mx_tile *ops) { return jx_mx420_operands((uint16_t(*)[5][64][8])ops); }
+};
+
+/* f(K{}) for the kernel of sample ratio sr: 0 (4:4:4), 1 (true 4:2:2), 2 (true 4:2:0) */
+template <class F>
+auto mx_for_kernel(int sr, F f)
+{
+    return sr == 1 ? f(Mxs422K{}) : sr == 2 ? f(Mxs420K{}) : f(MxsK{});
+}
+
+/* A kernel's workgroup images [force][quality] for the qualities qlo..qhi (the others stay zero)
+ * and its operand tiles.  Pure host code: no HIP call.  An image is the scale / limit table, the
+ * hot-path limits mx_limc computes from the full table, the zig-zag positions, the exact pass's
+ * tables and (K::land) the operands. */
+template <class K>
+int mx_build_images(std::vector<typename K::Img> &img, std::vector<uint16_t> &opsv, int qlo, int qhi)
+{
+    typedef typename K::Img Img;
+    std::vector<jx_mxtab> tab;
+    int rc = mx_plan_tabs(tab, K::mode, qlo, qhi);
+    opsv.assign(sizeof(mx_tile) / sizeof(uint16_t) * K::tiles * JX_MX_PARTS, 0);   /* heap: reentrant */
+    mx_tile *ops = (mx_tile *)opsv.data();
+    if (!rc) rc = K::operands(ops);
+    if (rc) return rc;
+    for (unsigned p = 0; p < JX_MX_PARTS; p++)          /* the pair's zero halves */
+        for (unsigned l = 0; l < 64; l++)
+            for (int e = 0; e < 8; e++)
+                if (ops[K::tiles * p + K::pair + ((l & 15u) < 8 ? 1 : 0)][l][e]) return JPGX_EARG;
+    img.resize(2 * (JX_MAXQ + 1));
+    memset(img.data(), 0, img.size() * sizeof(Img));
+    for (int f = 0; f < 2; f++)
+        for (int q = qlo; q <= qhi; q++) {
+            Img &I = img[f * (JX_MAXQ + 1) + q];
+            const jx_mxtab &t = tab[f * (JX_MAXQ + 1) + q];
+            MxTab full;
+            mx_layout_tab(full, t, K::ncol);
+            for (unsigned jp = 0; jp < 16; jp++) {
+                I.limc[0][jp] = mx_limc(full, 1, jp);
+                I.limc[1][jp] = mx_limc(full, 3, jp);
+            }
+            K::land(I, full, ops);
+            mx_scan_t(I.scan_t);
+            mx_ex_tab(I.ex, t);
+        }
+    return JPGX_OK;
+}
+
+/* once per device: build the kernel's images and upload them */
+template <class K>
 int mx_tables_for_current_device()
 {
+    static std::once_flag once[kMaxDev];
+    static int rcs[kMaxDev];
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return JPGX_ENODEV;
-    std::call_once(g_mx_once[dev], [dev]() {
-        std::vector<jx_mxtab> tab;
-        int rc = mx_plan_tabs(tab, jx_plan_tables_mx);
-        std::unique_ptr<uint16_t[][64][8]> opsp(new uint16_t[3 * JX_MX_PARTS][64][8]);   /* heap: reentrant */
-        auto ops = opsp.get();
-        if (!rc) rc = jx_mx_operands(ops);
-        if (!rc) {
-            /* k_mxs's workgroup images: B operands, the scale / limit table (Y|Cb at 16 lane
-             * profiles, Cr compacted to 8), the hot-path limits mx_limc computes from the full
-             * table, the zig-zag positions and the exact pass's tables */
-            std::vector<MxsImg> img(2 * (JX_MAXQ + 1));
-            memset(img.data(), 0, img.size() * sizeof(MxsImg));
-            for (int f = 0; f < 2; f++)
-                for (int q = 1; q <= JX_MAXQ; q++) {
-                    MxsImg &I = img[f * (JX_MAXQ + 1) + q];
-                    const jx_mxtab &t = tab[f * (JX_MAXQ + 1) + q];
-                    mx_ex_tab(I.ex, t);
-                    MxTab full;
-                    mx_layout_tab(full, t, [](unsigned tt, unsigned jp) { return tt < 2 ? jp : 16u + (jp & 7u); });
-                    for (unsigned jp = 0; jp < 16; jp++) {
-                        I.limc[0][jp] = mx_limc(full, 1, jp);
-                        I.limc[1][jp] = mx_limc(full, 3, jp);
-                        for (int tt = 0; tt < 2; tt++)
-                            for (int h = 0; h < 2; h++) {
-                                I.tab.yc[tt][h][jp] = full.wl[tt][h][jp];
-                                if (jp < 8) I.tab.cr[tt][h][jp] = full.wl[2 + tt][h][jp];
-                            }
-                    }
-                    mx_scan_t(I.scan_t);
-                }
-            if (!rc) rc = mx_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_mxs_img), img.data(), img.size() * sizeof(MxsImg)));
-            /* the Cr sets' operands are zero in opposite column halves (B1 in 8..15, B2 in 0..7):
-             * the kernel's Cr sum cr[0] + cr[1] is exact because of it */
-            for (int p = 0; p < JX_MX_PARTS; p++)
-                for (unsigned l = 0; l < 64; l++)
-                    for (int e = 0; e < 8; e++)
-                        if (ops[3 * p + ((l & 15u) < 8 ? 2 : 1)][l][e]) rc = JPGX_EARG;
-            if (!rc) rc = mx_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_mxs_B), ops, sizeof(uint16_t) * 3 * JX_MX_PARTS * 64 * 8));
-        }
-        g_mx_rc[dev] = rc;
+    std::call_once(once[dev], [dev]() {
+        std::vector<typename K::Img> img;
+        std::vector<uint16_t> ops;
+        int rc = mx_build_images<K>(img, ops, 1, JX_MAXQ);
+        if (!rc) rc = mx_rc(hipMemcpyToSymbol(HIP_SYMBOL(K::symbol()), img.data(), img.size() * sizeof(img[0])));
+        if (!rc) rc = mx_rc(K::upload_operands((const mx_tile *)ops.data()));
+        rcs[dev] = rc;
     });
-    return g_mx_rc[dev];
-}
-
-std::once_flag g_mx422_once[kMaxDev];
-int g_mx422_rc[kMaxDev];
-
-int mx422_tables_for_current_device()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return JPGX_ENODEV;
-    std::call_once(g_mx422_once[dev], [dev]() {
-        std::vector<jx_mxtab> tab;
-        int rc = mx_plan_tabs(tab, jx_plan_tables_mx422);
-        std::unique_ptr<uint16_t[][4][64][8]> opsp(new uint16_t[JX_MX_PARTS][4][64][8]);   /* heap: reentrant */
-        auto ops = opsp.get();
-        if (!rc) rc = jx_mx422_operands(ops);
-        if (!rc) {
-            /* k_mxs422's image: B operands, the scale / limit table (Y at plan column j % 8,
-             * chroma at 8 + j), hot-path limits, zig-zag positions, the exact pass's tables */
-            std::vector<MxsImg422> img(2 * (JX_MAXQ + 1));
-            memset(img.data(), 0, img.size() * sizeof(MxsImg422));
-            for (size_t i = 0; i < img.size(); i++) {
-                mx_layout_tab(img[i].tab, tab[i], [](unsigned tt, unsigned jp) { return tt < 2 ? (jp & 7u) : 8u + jp; });
-                for (int p = 0; p < JX_MX_PARTS; p++)
-                    for (unsigned l = 0; l < 64; l++) {
-                        const bool set0 = (l & 15u) < 8;
-                        const uint16_t *keep = ops[p][set0 ? 0 : 1][l], *zero = ops[p][set0 ? 1 : 0][l];
-                        for (int e = 0; e < 8; e++)
-                            if (zero[e]) rc = JPGX_EARG;      /* the merge needs the zero halves (as jpgx_plan.cpp) */
-                        memcpy(&img[i].B[3 * p][l], keep, 16);
-                        memcpy(&img[i].B[3 * p + 1][l], ops[p][2][l], 16);
-                        memcpy(&img[i].B[3 * p + 2][l], ops[p][3][l], 16);
-                    }
-                for (unsigned jp = 0; jp < 16; jp++) {
-                    img[i].limc[0][jp] = mx_limc(img[i].tab, 1, jp);
-                    img[i].limc[1][jp] = mx_limc(img[i].tab, 3, jp);
-                }
-                mx_scan_t(img[i].scan_t);
-                mx_ex_tab(img[i].ex, tab[i]);
-            }
-            if (!rc) rc = mx_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_mxs422_img), img.data(), img.size() * sizeof(MxsImg422)));
-        }
-        g_mx422_rc[dev] = rc;
-    });
-    return g_mx422_rc[dev];
-}
-
-std::once_flag g_mx420_once[kMaxDev];
-int g_mx420_rc[kMaxDev];
-
-int mx420_tables_for_current_device()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return JPGX_ENODEV;
-    std::call_once(g_mx420_once[dev], [dev]() {
-        std::vector<jx_mxtab> tab;
-        int rc = mx_plan_tabs(tab, jx_plan_tables_mx420);
-        std::unique_ptr<uint16_t[][5][64][8]> opsp(new uint16_t[JX_MX_PARTS][5][64][8]);   /* heap: reentrant */
-        auto ops = opsp.get();
-        if (!rc) rc = jx_mx420_operands(ops);
-        if (!rc) {
-            /* k_mxs420's image (the 4:2:2 table layout) */
-            std::vector<MxsImg420> img(2 * (JX_MAXQ + 1));
-            memset(img.data(), 0, img.size() * sizeof(MxsImg420));
-            for (size_t i = 0; i < img.size(); i++) {
-                for (int p = 0; p < JX_MX_PARTS; p++)
-                    for (unsigned l = 0; l < 64; l++) {
-                        const bool set0 = (l & 15u) < 8;   /* the Y sets' zero halves (as k_mxs422) */
-                        const uint16_t *keep = ops[p][set0 ? 0 : 1][l], *zero = ops[p][set0 ? 1 : 0][l];
-                        for (int e = 0; e < 8; e++)
-                            if (zero[e]) rc = JPGX_EARG;
-                        memcpy(&img[i].B[4 * p][l], keep, 16);
-                        for (int w = 2; w < 5; w++) memcpy(&img[i].B[4 * p + w - 1][l], ops[p][w][l], 16);
-                    }
-                mx_layout_tab(img[i].tab, tab[i], [](unsigned tt, unsigned jp) { return tt < 2 ? (jp & 7u) : 8u + jp; });
-                for (unsigned jp = 0; jp < 16; jp++) {
-                    img[i].limc[0][jp] = mx_limc(img[i].tab, 1, jp);
-                    img[i].limc[1][jp] = mx_limc(img[i].tab, 3, jp);
-                }
-                mx_scan_t(img[i].scan_t);
-                mx_ex_tab(img[i].ex, tab[i]);
-            }
-            if (!rc) rc = mx_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_mxs420_img), img.data(), img.size() * sizeof(MxsImg420)));
-        }
-        g_mx420_rc[dev] = rc;
-    });
-    return g_mx420_rc[dev];
+    return rcs[dev];
 }
 
 }  // namespace
@@ -2294,49 +2298,44 @@ void mx_launch_k(K kernel, dim3 grid, dim3 block, hipStream_t s, void *ev_start,
         hipLaunchKernelGGL(kernel, grid, block, 0, s, a);
 }
 
-/* k_mxs420 over every frame of the stripe (true 4:2:0: Y [nb][64], Cb and Cr [nb / 4][64] per
- * frame, the stripe an even number of block rows); no workspace. */
-extern "C" int jx_launch_mx420(const jx_xform_args *xa, void *stream, void *ev_start, void *ev_stop)
+/* the kernel of sample ratio sr over every frame of the stripe; no workspace */
+extern "C" int jx_launch_mx(const jx_xform_args *xa, int sr, void *stream, void *ev_start, void *ev_stop)
 {
-    const int rc = mx420_tables_for_current_device();
-    if (rc) return rc;
-    const size_t mcus = (size_t)xa->g.nb / 4 * (size_t)xa->g.nframes;
-    const size_t waves = (mcus + 7) / 8;
-    mx_launch_k(k_mxs420, dim3((unsigned)((waves + kMxs420WPG - 1) / kMxs420WPG)), dim3(64 * kMxs420WPG), (hipStream_t)stream,
-                ev_start, ev_stop, *xa);
-    return mx_rc(hipGetLastError());
-}
-
-/* k_mxs422 over every frame of the stripe (true 4:2:2: Y [nb][64], Cb and Cr [nb / 2][64] per
- * frame); no workspace. */
-extern "C" int jx_launch_mx422(const jx_xform_args *xa, void *stream, void *ev_start, void *ev_stop)
-{
-    const int rc = mx422_tables_for_current_device();
-    if (rc) return rc;
-    const size_t nsteps = ((size_t)xa->g.nb * (size_t)xa->g.nframes + 7) / 8;
-    const size_t waves = (nsteps + kMxs422C - 1) / kMxs422C;
-    mx_launch_k(k_mxs422, dim3((unsigned)((waves + kMxs422WPG - 1) / kMxs422WPG)), dim3(64 * kMxs422WPG), (hipStream_t)stream,
-                ev_start, ev_stop, *xa);
-    return mx_rc(hipGetLastError());
-}
-
-/* k_mxs over every frame of the stripe (4:4:4 / reference-parity output); no workspace. */
-extern "C" int jx_launch_mx(const jx_xform_args *xa, void *stream, void *ev_start, void *ev_stop)
-{
-    const int rc = mx_tables_for_current_device();
-    if (rc) return rc;
-    const size_t nsteps = ((size_t)xa->g.nb * (size_t)xa->g.nframes + 7) / 8;
-    const size_t waves = (nsteps + kMxsC - 1) / kMxsC;
-    mx_launch_k(k_mxs, dim3((unsigned)((waves + kMxsWPG - 1) / kMxsWPG)), dim3(64 * kMxsWPG), (hipStream_t)stream,
-                ev_start, ev_stop, *xa);
-    return mx_rc(hipGetLastError());
+    return mx_for_kernel(sr, [&](auto k) {
+        typedef decltype(k) K;
+        const int rc = mx_tables_for_current_device<K>();
+        if (rc) return rc;
+        const size_t units = (size_t)xa->g.nb / K::unit * (size_t)xa->g.nframes;
+        const size_t waves = (units + K::per_wave - 1) / K::per_wave;
+        mx_launch_k(K::kernel(), dim3((unsigned)((waves + K::wpg - 1) / K::wpg)), dim3(64 * K::wpg), (hipStream_t)stream,
+                    ev_start, ev_stop, *xa);
+        return mx_rc(hipGetLastError());
+    });
 }
 
 /* the kernel a launch runs for sample ratio 0 (4:4:4), 1 (true 4:2:2), 2 (4:2:0): bench.py and
  * the profiles name the kernel they time with it */
 extern "C" const char *jx_mx_kernel_name(int sr)
 {
-    if (sr == 1) return "k_mxs422";
-    if (sr == 2) return "k_mxs420";
-    return "k_mxs";
+    return mx_for_kernel(sr, [](auto k) { return decltype(k)::name; });
+}
+
+/* TEST HOOK (host only, no HIP call): the workgroup image mx_build_images makes for the kernel of
+ * sample ratio sr, force and quality, copied to dst; returns its size (negative JPGX_E* for bad
+ * arguments or cap below the size).  tests/test_mx_pins.py pins the images with it. */
+extern "C" long long jx_mx_image(int sr, int force, int quality, void *dst, long long cap)
+{
+    if (sr < 0 || sr > 2) return JPGX_ESAMPLE;
+    if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
+    if (force < 0 || force > 1 || !dst) return JPGX_EARG;
+    return mx_for_kernel(sr, [&](auto k) -> long long {
+        typedef decltype(k) K;
+        if (cap < (long long)sizeof(typename K::Img)) return JPGX_EARG;
+        std::vector<typename K::Img> img;
+        std::vector<uint16_t> ops;
+        const int rc = mx_build_images<K>(img, ops, quality, quality);
+        if (rc) return rc;
+        memcpy(dst, &img[force * (JX_MAXQ + 1) + quality], sizeof(typename K::Img));
+        return (long long)sizeof(typename K::Img);
+    });
 }

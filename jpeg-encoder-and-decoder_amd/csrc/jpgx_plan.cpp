@@ -181,15 +181,37 @@ static long double dct_kfactor(int k)
     return (k == 0 ? 8.0L : 4.0L) / out[k];
 }
 
-int jx_plan_tables_mode(int quality, int sub, float w[3][64], float lim[3][64], int16_t q[2][64])
+/* this quality's scaled divisors: qs[t][u][v], and q[t][u * 8 + v] as the kernels take them */
+static int plan_divisors(int quality, int qs[2][8][8], int16_t q[2][64])
 {
-    int qs[2][8][8];
-    int rc = jpgx_scale_table(0, quality, qs[0]);
+    const int rc = jpgx_scale_table(0, quality, qs[0]);
     if (rc) return rc;
     jpgx_scale_table(1, quality, qs[1]);
     for (int t = 0; t < 2; t++)
         for (int u = 0; u < 8; u++)
             for (int v = 0; v < 8; v++) q[t][u * 8 + v] = (int16_t)qs[t][u][v];
+    return JPGX_OK;
+}
+
+/* a coefficient's fp32 scale and band limit from its exact scale ws and the bound b of its fp32
+ * value: the error of t_fp vs the reference's real-arithmetic quotient, plus the final fma
+ * rounding of d (< 2^-25), plus slack for the reference's own double rounding (< 1e-10) and for
+ * this bound's own double arithmetic */
+static void plan_band(long double ws, const Bnd &b, float *w, float *lim)
+{
+    const float wf = (float)ws;
+    const double mF = BoundOps::mag(b) + b.E;
+    double et = b.E * fabs((double)wf) + mF * (double)fabsl((long double)wf - ws) + 0x1p-25;
+    et = et * 1.01 + 1e-7;
+    *w = wf;
+    *lim = (float)(0.5 - et);
+}
+
+int jx_plan_tables_mode(int quality, int sub, float w[3][64], float lim[3][64], int16_t q[2][64])
+{
+    int qs[2][8][8];
+    const int rc = plan_divisors(quality, qs, q);
+    if (rc) return rc;
 
     Bnd F[3][8][8];
     coef_bounds<0>(F[0]);                  /* luma is never averaged */
@@ -204,16 +226,7 @@ int jx_plan_tables_mode(int quality, int sub, float w[3][64], float lim[3][64], 
                 const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
                 const long double ku = dct_kfactor(u), kv = dct_kfactor(v);
                 const long double ws = 0.25L * au * av * ku * kv / (long double)qs[t][u][v];
-                const float wf = (float)ws;
-                const Bnd &b = F[ch][v][u];
-                const double mF = BoundOps::mag(b) + b.E;
-                /* error of t_fp vs the reference's real-arithmetic quotient, plus the final
-                 * fma rounding of d (< 2^-25), plus slack for the reference's own double
-                 * rounding (< 1e-10) and for this bound's own double arithmetic */
-                double et = b.E * fabs((double)wf) + mF * (double)fabsl((long double)wf - ws) + 0x1p-25;
-                et = et * 1.01 + 1e-7;
-                w[ch][v * 8 + u] = wf;
-                lim[ch][v * 8 + u] = (float)(0.5 - et);
+                plan_band(ws, F[ch][v][u], &w[ch][v * 8 + u], &lim[ch][v * 8 + u]);
             }
     }
     return JPGX_OK;
@@ -372,35 +385,41 @@ extern "C" long long jx_selftest_pk(long long nblocks, unsigned long long seed)
     return bad;
 }
 
-extern "C" {
-
-}  /* extern "C" */
-
-/* ---- k_mx: colour conversion + row DCT as one f16 MFMA product --------------------------
+/* ---- k_mxs / k_mxs422 / k_mxs420: colour conversion + row DCT as f16 MFMA products --------
  *
- * k_mx multiplies each pixel row, 24 bytes b_k (k = 3x + p, plane p of pixel x), by B[k][n] =
- * a[c][p] cos((2x+1)u pi/16), n = 8c + u, with a bias row (input 1.0) carrying the level shift,
- * -8 * 128 for Y at u = 0 (preprocess.c:160-162,186-188: Y - 128; the level-shifted chroma has
- * no constant; the true cosines of u > 0 sum to 0).  B is split into JX_MX_PARTS f16 parts:
- *   Bh  B rounded to a multiple of 2^-11 (|B| < 1: 11 bits; bias: its f16),
- *   Bl  2^12 (B - Bh),  [Bm  2^12 (B - Bh) - Bl]   (each rounded to f16).
+ * The kernels multiply a row of pixel bytes b_k by a matrix B[k][n], split into JX_MX_PARTS f16
+ * parts.  Three matrices ("mode"), one code path below:
+ *   mode 0 (k_mxs, and the Y of every kernel): a pixel row of a block, 24 bytes (k = 3x + p, plane
+ *     p of pixel x), B[k][n] = a[c][p] cos((2x+1)u pi/16), n = 8c + u, c = Y, Cb, Cr, with a bias
+ *     row (input 1.0) carrying the level shift, -8 * 128 for Y at u = 0 (preprocess.c:160-162,
+ *     186-188: Y - 128; the level-shifted chroma has no constant; the true cosines of u > 0 sum
+ *     to 0).  One K = 32 product per part.
+ *   mode 1 / 2 (the chroma of k_mxs422 / k_mxs420; the EXTENSION's definition, oracle/cpu_ref.c
+ *     cpuref_chroma_sample): a chroma row of a chroma block is, for 4:2:2, the 16 pixels (48 bytes)
+ *     of one pixel row of its MCU, the sample X the average of pixels 2X, 2X+1 of the level-shifted
+ *     chroma; for 4:2:0 the 16 pixels of two pixel rows (96 bytes, k = 48 r + 3x + p), the sample
+ *     the average of the 2 x 2 quad.  The row transform is linear in the bytes:
+ *       R(u) = sum_{r, x < 16, p} b_{48r+3x+p} w a[c][p] cos((2 floor(x/2) + 1) u pi/16),
+ *     w = 1/2 or 1/4, c = Cb, Cr, n = 8 c' + u (c' = 0 Cb, 1 Cr); its bias row is all zero.  Two /
+ *     three K = 32 products per part (k = 0..31, 32..63 [, 64..95]).
+ * The split: Bh = B rounded to a multiple of 2^-11 (|B| < 1: 11 bits; bias: its f16), Bl = the f16
+ * of B - Bh [, Bm = the f16 of B - Bh - Bl], the lo parts stored x 2^JX_MX_LOEXP (0: at the hi
+ * part's scale, R = acc_h + acc_l is one add).
  * Encoding (the kernel's A is one v_perm per two bytes): A holds the byte zero-extended to 16
  * bits, i.e. the f16 subnormal b 2^-24 (exact), the bias lanes 1.0; B's byte rows are stored
  * x 2^15 and the bias row x 2^-9, so every product is b B 2^-9 (exact in fp32) and the MFMA's
  * results are R 2^-9.  Scaling by a power of two changes no rounding, so the kernel's fp32
  * values are those of the true-scale arithmetic below times 2^-9 bit for bit; the column pass
- * scales with them, and the quantiser's w x 2^9 (JX_MX_RSCALE) gives the very fp32 F w.
+ * scales with them, and the quantiser's w x 2^9 (jpgx_mx.hip kRScale) gives the very fp32 F w.
  * acc_h = sum_k b_k Bh_k is EXACT whatever the order of the MFMA's additions: every product
  * and every partial sum is a multiple of 2^-11 below 2^13 in magnitude (24 bits).  acc_l =
- * sum_k b_k (Bl_k [+ Bm_k]) 2^-12 is below 1 in magnitude; each of its additions is charged
- * one ulp.  R = fl(acc_h + 2^-12 acc_l) (one fma) then enters the column pass (jx_fdct8,
- * FOps, two blocks per v_pk_* pair) as usual.
+ * sum_k b_k (Bl_k [+ Bm_k]) is below 1 in magnitude; each of its additions is charged one ulp
+ * (32 products per MFMA plus the accumulator: 33, 65 or 97 per lo part).  R = fl(acc_h + acc_l)
+ * then enters the column pass (jx_fdct8, FOps, two blocks per v_pk_* pair) as usual.
  *
  * Operand layout (v_mfma_f32_16x16x32_f16: lane l holds A[row l & 15][k = 8 (l >> 4) + e] and
- * B[k = 8 (l >> 4) + e][column l & 15], e = 0..7): k < 24 is byte k of the pixel row, k = 24
- * the bias (A = 1.0), k > 24 weight 0.  Three B matrices ("which"): 0 = columns j = 8c + u for
- * c = Y, Cb; 1 = Cr at u = j for j < 8, zero columns j >= 8; 2 = zero columns j < 8, Cr at
- * u = j - 8 for j >= 8 (k_mx sums A_set0 B1 + A_set1 B2: the two sets concatenated along K).
+ * B[k = 8 (l >> 4) + e][column l & 15], e = 0..7); mode 0: k < 24 is byte k of the pixel row,
+ * k = 24 the bias (A = 1.0), k > 24 weight 0.
  */
 static const double kMxA[3][3] = {{0.299, 0.587, 0.114},
                                   {-0.168736, 0.331264, -0.5},
@@ -429,18 +448,28 @@ static long double f16_round(long double x, uint16_t *bits)
     return v;
 }
 
-/* exact B[k][n] (k < 24: matrix, k = 24: bias row; n < 24) */
-static long double mx_exact(int k, int n)
+/* a mode's byte rows (the bias row is row mx_nk), columns, and K = 32 products per part */
+static int mx_nk(int mode) { return mode ? 48 * mode : 24; }
+static int mx_ncol(int mode) { return mode ? 16 : 24; }
+static int mx_products(int mode) { return mode + 1; }
+
+/* exact B[k][n] of a mode (k < mx_nk: matrix, k = mx_nk: bias row) */
+static long double mx_exact(int mode, int k, int n)
 {
-    if (n >= 24) return 0;
-    const int c = n / 8, u = n % 8;
+    if (n >= mx_ncol(mode) || k > mx_nk(mode)) return 0;
     const long double pi = 3.141592653589793238462643383279502884L;
-    if (k < 24) {
-        const int x = k / 3, p = k % 3;
-        return (long double)kMxA[c][p] * cosl((2 * x + 1) * u * pi / 16);
+    const int u = n % 8;
+    if (mode == 0) {
+        const int c = n / 8;
+        if (k < 24) {
+            const int x = k / 3, p = k % 3;
+            return (long double)kMxA[c][p] * cosl((2 * x + 1) * u * pi / 16);
+        }
+        return u == 0 && c == 0 ? -1024.0L : 0;
     }
-    if (k == 24 && u == 0 && c == 0) return -1024.0L;
-    return 0;
+    if (k == mx_nk(mode)) return 0;
+    const int c = 1 + n / 8, kk = k % 48, x = kk / 3, p = kk % 3;
+    return (mode == 1 ? 0.5L : 0.25L) * (long double)kMxA[c][p] * cosl((2 * (x / 2) + 1) * u * pi / 16);
 }
 
 /* f16 encodings of the split parts (see above): a byte row's value x 2^15, the bias row's
@@ -452,23 +481,33 @@ static long double mx_enc(long double v, bool bias, uint16_t *bits)
     return ldexpl(f16_round(ldexpl(v, e), bits), -e);
 }
 
+/* one mode's split matrix: true-scale values and f16 bit patterns, rows 0..nk (nk = the bias row) */
 struct MxSplit {
-    long double h[25][32], l[25][32], m[25][32];      /* m = 0 unless JX_MX_PARTS == 3 */
-    uint16_t bh[25][32], bl[25][32], bm[25][32];
+    int mode, nk, ncol;
+    long double h[97][24], l[97][24], m[97][24];      /* m = 0 unless JX_MX_PARTS == 3 */
+    uint16_t bh[97][24], bl[97][24], bm[97][24];
+    uint16_t bits(int part, int k, int n) const
+    {
+        return k > nk ? 0 : (part == 0 ? bh[k][n] : (part == 1 ? bl[k][n] : bm[k][n]));
+    }
 };
+typedef std::unique_ptr<MxSplit> MxSplitPtr;        /* heap, per call: reentrant across threads */
 
-static int mx_split(MxSplit &S)
+static int mx_split(int mode, MxSplit &S)
 {
     memset(&S, 0, sizeof S);
-    for (int k = 0; k < 25; k++)
-        for (int n = 0; n < 24; n++) {
-            const long double B = mx_exact(k, n);
-            const bool bias = k == 24;
+    S.mode = mode;
+    S.nk = mx_nk(mode);
+    S.ncol = mx_ncol(mode);
+    for (int k = 0; k <= S.nk; k++)
+        for (int n = 0; n < S.ncol; n++) {
+            const long double B = mx_exact(mode, k, n);
+            const bool bias = k == S.nk;
             const long double hv = mx_enc(bias ? B : rintl(ldexpl(B, 11)) / 2048.0L, bias, &S.bh[k][n]);
             if (ldexpl(hv, 11) != rintl(ldexpl(hv, 11))) return JPGX_EARG;
             S.h[k][n] = hv;
-            /* the lo parts are stored scaled by 2^JX_MX_LOEXP (round 4: 2^0); k_mx takes R =
-             * acc_h + 2^-LOEXP acc_l, exact scaling.  S.l / S.m hold the unscaled values. */
+            /* the lo parts are stored scaled by 2^JX_MX_LOEXP (exact scaling: the kernels take R =
+             * acc_h + 2^-LOEXP acc_l).  S.l / S.m hold the unscaled values. */
             const long double ls = mx_enc(ldexpl(B - hv, JX_MX_LOEXP), bias, &S.bl[k][n]);
             S.l[k][n] = ldexpl(ls, -JX_MX_LOEXP);
             if (JX_MX_PARTS == 3) {
@@ -476,9 +515,9 @@ static int mx_split(MxSplit &S)
                 S.m[k][n] = ldexpl(ms, -JX_MX_LOEXP);
             }
         }
-    for (int n = 0; n < 24; n++) {              /* acc_h exactness: partial sums < 2^13 */
-        long double sh = fabsl(S.h[24][n]);
-        for (int k = 0; k < 24; k++) sh += 255.0L * fabsl(S.h[k][n]);
+    for (int n = 0; n < S.ncol; n++) {          /* acc_h exactness: partial sums < 2^13 */
+        long double sh = fabsl(S.h[S.nk][n]);
+        for (int k = 0; k < S.nk; k++) sh += 255.0L * fabsl(S.h[k][n]);
         if (sh >= 8192.0L) return JPGX_EARG;
     }
     return JPGX_OK;
@@ -487,13 +526,15 @@ static int mx_split(MxSplit &S)
 extern "C" int jx_mx_parts(void) { return JX_MX_PARTS; }
 extern "C" int jx_mx_loexp(void) { return JX_MX_LOEXP; }
 
+/* k_mxs's operands, 3 * part + which; lane l holds B[k = 8 (l >> 4) + e][plan column of l & 15].
+ * which 0 = columns j = 8c + u for c = Y, Cb; 1 = Cr at u = j for j < 8, zero columns j >= 8;
+ * 2 = zero columns j < 8, Cr at u = j - 8 for j >= 8 (the kernel sums A_set0 B1 + A_set1 B2: the
+ * two sets concatenated along K) */
 extern "C" int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8])
 {
-    std::unique_ptr<MxSplit> S_(new MxSplit);   /* heap, per call: reentrant across threads */
-    MxSplit &S = *S_;
-    const int rc = mx_split(S);
+    MxSplitPtr S(new MxSplit);
+    const int rc = mx_split(0, *S);
     if (rc) return rc;
-    /* operand 3 * part + which; lane l holds B[k = 8 (l >> 4) + e][plan column of l & 15] */
     for (int part = 0; part < JX_MX_PARTS; part++)
         for (int which = 0; which < 3; which++)
             for (int l = 0; l < 64; l++)
@@ -503,290 +544,182 @@ extern "C" int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8])
                     if (which == 0) n = j;
                     else if (which == 1 && j < 8) n = 16 + j;
                     else if (which == 2 && j >= 8) n = 16 + j - 8;
-                    uint16_t v = 0;
-                    if (n >= 0 && k <= 24)
-                        v = part == 0 ? S.bh[k][n] : (part == 1 ? S.bl[k][n] : S.bm[k][n]);
-                    ops[3 * part + which][l][e] = v;
+                    ops[3 * part + which][l][e] = n >= 0 ? S->bits(part, k, n) : 0;
                 }
     return JPGX_OK;
 }
 
-/* Interval + error bound of R (the column pass input) for column n = 8c + u. */
+/* k_mxs422's / k_mxs420's operands [part][which][lane][e], which < 2 + mx_products(mode): 0 / 1 = Y
+ * of set 0 / set 1 (mode 0's Y columns in C columns 0..7 / 8..15, the other half zero: the product
+ * A_set0 B_Y0 + A_set1 B_Y1 is K-concatenated as k_mxs's Cr), 2.. = the chroma K steps
+ * (k = 32 (which - 2) + 8 (l >> 4) + e); lane l holds B[k][column l & 15] */
+static int mxc_operands(int mode, uint16_t *ops)
+{
+    MxSplitPtr Y(new MxSplit), C(new MxSplit);
+    int rc = mx_split(0, *Y);
+    if (!rc) rc = mx_split(mode, *C);
+    if (rc) return rc;
+    const int nwhich = 2 + mx_products(mode);
+    for (int part = 0; part < JX_MX_PARTS; part++)
+        for (int which = 0; which < nwhich; which++)
+            for (int l = 0; l < 64; l++)
+                for (int e = 0; e < 8; e++) {
+                    const int j = l & 15, k = 8 * (l >> 4) + e;
+                    uint16_t v = 0;
+                    if (which >= 2) v = C->bits(part, 32 * (which - 2) + k, j);
+                    else if (which == 0 ? j < 8 : j >= 8) v = Y->bits(part, k, j & 7);
+                    ops[((part * nwhich + which) * 64 + l) * 8 + e] = v;
+                }
+    return JPGX_OK;
+}
+
+extern "C" int jx_mx422_operands(uint16_t ops[JX_MX_PARTS][4][64][8]) { return mxc_operands(1, &ops[0][0][0][0]); }
+extern "C" int jx_mx420_operands(uint16_t ops[JX_MX_PARTS][5][64][8]) { return mxc_operands(2, &ops[0][0][0][0]); }
+
+/* Interval + error bound of R (the column pass input) for column n of the split's matrix. */
 static Bnd mx_row_bound(const MxSplit &S, int n)
 {
-    long double loh = S.h[24][n], hih = S.h[24][n];
-    long double lol = S.l[24][n] + S.m[24][n], hil = lol;
-    long double sl = fabsl(S.l[24][n]) + fabsl(S.m[24][n]);
-    long double rep = fabsl(mx_exact(24, n) - S.h[24][n] - S.l[24][n] - S.m[24][n]);
-    for (int k = 0; k < 24; k++) {             /* bytes 0..255 */
+    const int nk = S.nk;
+    long double loh = S.h[nk][n], hih = S.h[nk][n];
+    long double lol = S.l[nk][n] + S.m[nk][n], hil = lol;
+    long double sl = fabsl(S.l[nk][n]) + fabsl(S.m[nk][n]);
+    long double rep = fabsl(mx_exact(S.mode, nk, n) - S.h[nk][n] - S.l[nk][n] - S.m[nk][n]);
+    for (int k = 0; k < nk; k++) {             /* bytes 0..255 */
         const long double bh = S.h[k][n], bo = S.l[k][n] + S.m[k][n];
         loh += std::min(0.0L, 255.0L * bh);
         hih += std::max(0.0L, 255.0L * bh);
         lol += std::min(0.0L, 255.0L * bo);
         hil += std::max(0.0L, 255.0L * bo);
         sl += 255.0L * (fabsl(S.l[k][n]) + fabsl(S.m[k][n]));
-        rep += 255.0L * fabsl(mx_exact(k, n) - S.h[k][n] - S.l[k][n] - S.m[k][n]);
+        rep += 255.0L * fabsl(mx_exact(S.mode, k, n) - S.h[k][n] - S.l[k][n] - S.m[k][n]);
     }
-    /* acc_l: per lo part one MFMA of 32 products (K = 32: 25 weights, 7 zeros; the Cr tile's
-     * second, K-concatenated MFMA adds exact zeros in every column) plus the accumulator input;
-     * every addition charged one ulp of the magnitude bound, twice over for an unknown
+    /* acc_l: per lo part mx_products MFMAs of 32 products (mode 0: 25 weights, 7 zeros; k_mxs's Cr
+     * tile's second, K-concatenated MFMA adds exact zeros in every column) plus the accumulator
+     * input; every addition charged one ulp of the magnitude bound, twice over for an unknown
      * summation tree and rounding mode */
-    const double nadd = 2.0 * (33.0 * (JX_MX_PARTS - 1));
+    const double nadd = 2.0 * ((32.0 * mx_products(S.mode) + 1.0) * (JX_MX_PARTS - 1));
     const double el = (double)(nadd * sl * 0x1p-23L + rep);
     return BoundOps::add(Bnd{(double)loh, (double)hih, 0.0},
                          Bnd{(double)lol - el, (double)hil + el, el});
+}
+
+/* The tables of the kernel of `mode`, plan columns n = 8 c + u as jx_mxtab: mode 0 all three
+ * channels from mode 0's matrix; mode 1 / 2: c = 0 Y (mode 0's bound), 1 Cb, 2 Cr (the subsampled
+ * rows' matrix, columns n - 8) */
+static int mx_plan_tables(int mode, int quality, float w[24][8], float lim[24][8], int16_t q[2][64])
+{
+    int qs[2][8][8];
+    int rc = plan_divisors(quality, qs, q);
+    if (rc) return rc;
+    MxSplitPtr Y(new MxSplit), C;
+    rc = mx_split(0, *Y);
+    if (!rc && mode) {
+        C.reset(new MxSplit);
+        rc = mx_split(mode, *C);
+    }
+    if (rc) return rc;
+    const long double a0 = 1.0L / sqrtl(2.0L);
+    for (int n = 0; n < 24; n++) {
+        const int c = n / 8, u = n % 8, t = c == 0 ? 0 : 1;
+        const Bnd R = mode == 0 || c == 0 ? mx_row_bound(*Y, n) : mx_row_bound(*C, n - 8);
+        Bnd col[8], out[8];
+        for (int y = 0; y < 8; y++) col[y] = R;
+        jx_fdct8<BoundOps>(col, out);
+        for (int v = 0; v < 8; v++) {
+            /* the row transform uses exact cosines: only the column pass's k(v) */
+            const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
+            const long double ws = 0.25L * au * av * dct_kfactor(v) / (long double)qs[t][u][v];
+            plan_band(ws, out[v], &w[n][v], &lim[n][v]);
+        }
+    }
+    return JPGX_OK;
 }
 
 extern "C" int jx_plan_tables_mx(int quality, float w[24][8], float lim[24][8], int16_t q[2][64])
 {
-    int qs[2][8][8];
-    int rc = jpgx_scale_table(0, quality, qs[0]);
-    if (rc) return rc;
-    jpgx_scale_table(1, quality, qs[1]);
-    for (int t = 0; t < 2; t++)
-        for (int u = 0; u < 8; u++)
-            for (int v = 0; v < 8; v++) q[t][u * 8 + v] = (int16_t)qs[t][u][v];
-    std::unique_ptr<MxSplit> S_(new MxSplit);   /* heap, per call: reentrant across threads */
-    MxSplit &S = *S_;
-    rc = mx_split(S);
-    if (rc) return rc;
-    const long double a0 = 1.0L / sqrtl(2.0L);
-    for (int n = 0; n < 24; n++) {
-        const int c = n / 8, u = n % 8, t = c == 0 ? 0 : 1;
-        const Bnd R = mx_row_bound(S, n);
-        Bnd col[8], out[8];
-        for (int y = 0; y < 8; y++) col[y] = R;
-        jx_fdct8<BoundOps>(col, out);
-        for (int v = 0; v < 8; v++) {
-            const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
-            const long double ws = 0.25L * au * av * dct_kfactor(v) / (long double)qs[t][u][v];
-            const float wf = (float)ws;
-            const Bnd &b = out[v];
-            const double mF = BoundOps::mag(b) + b.E;
-            double et = b.E * fabs((double)wf) + mF * (double)fabsl((long double)wf - ws) + 0x1p-25;
-            et = et * 1.01 + 1e-7;
-            w[n][v] = wf;
-            lim[n][v] = (float)(0.5 - et);
-        }
-    }
-    return JPGX_OK;
-}
-
-/* ---- k_mx422 / k_mx420: true 4:2:2 / 4:2:0 on the matrix cores --------------------------
- *
- * Y is k_mx's Y (plan columns n = u, the 4:4:4 split S), its B laid out K-concatenated: the
- * product A_set0 B_Y0 + A_set1 B_Y1 puts set 0's blocks in C columns 0..7 and set 1's in
- * 8..15 (B_Y0 zero in columns 8..15, B_Y1 zero in 0..7), exactly as k_mx's Cr tile.
- * Chroma (the EXTENSION's definition, oracle/cpu_ref.c cpuref_chroma_sample): a chroma row of a
- * chroma block is, for 4:2:2 (sub 1), the 16 pixels (48 bytes) of one pixel row of its MCU, the
- * sample X the average of pixels 2X, 2X+1 of the level-shifted chroma; for 4:2:0 (sub 2) the 16
- * pixels of two pixel rows (96 bytes, k = 48 r + 3x + p), the sample the average of the 2 x 2
- * quad.  The row transform is linear in the bytes:
- *   R(u) = sum_{r, x < 16, p} b_{48r+3x+p} w a[c][p] cos((2 floor(x/2) + 1) u pi/16),
- * w = 1/2 (4:2:2) or 1/4 (4:2:0), a = kMxA[c], c = Cb, Cr, b = the byte (the level-shifted
- * chroma has no constant: no bias row), n = 8 c' + u (c' = 0 Cb, 1 Cr).  K = 32 MFMAs over
- * k = 0..31, 32..63 [, 64..95].  Same encoding and split as k_mx: Bh a multiple of 2^-11 (acc_h
- * exact in any order: every partial sum a multiple of 2^-11 below 2^13), the lo part(s) scaled
- * by 2^12, each of acc_l's additions charged one ulp (65 per 4:2:2 chroma row, 97 per 4:2:0 one:
- * 32 products per MFMA plus the accumulator).
- */
-static int mxc_nk(int sub) { return 48 * sub; }
-static int mxc_ksteps(int sub) { return sub == 1 ? 2 : 3; }
-
-static long double mxc_exact(int sub, int k, int n)
-{
-    if (n >= 16 || k >= mxc_nk(sub)) return 0;
-    const int c = 1 + n / 8, u = n % 8, kk = k % 48, x = kk / 3, p = kk % 3;
-    const long double pi = 3.141592653589793238462643383279502884L;
-    return (sub == 1 ? 0.5L : 0.25L) * (long double)kMxA[c][p] * cosl((2 * (x / 2) + 1) * u * pi / 16);
-}
-
-struct MxcSplit {
-    long double h[96][16], l[96][16], m[96][16];
-    uint16_t bh[96][16], bl[96][16], bm[96][16];
-};
-
-static int mxc_split(int sub, MxcSplit &S)
-{
-    memset(&S, 0, sizeof S);
-    const int nk = mxc_nk(sub);
-    for (int k = 0; k < nk; k++)
-        for (int n = 0; n < 16; n++) {
-            const long double B = mxc_exact(sub, k, n);
-            const long double hv = mx_enc(rintl(ldexpl(B, 11)) / 2048.0L, false, &S.bh[k][n]);
-            if (ldexpl(hv, 11) != rintl(ldexpl(hv, 11))) return JPGX_EARG;
-            S.h[k][n] = hv;
-            const long double ls = mx_enc(ldexpl(B - hv, JX_MX_LOEXP), false, &S.bl[k][n]);
-            S.l[k][n] = ldexpl(ls, -JX_MX_LOEXP);
-            if (JX_MX_PARTS == 3) {
-                const long double ms = mx_enc(ldexpl(B - hv, JX_MX_LOEXP) - ls, false, &S.bm[k][n]);
-                S.m[k][n] = ldexpl(ms, -JX_MX_LOEXP);
-            }
-        }
-    for (int n = 0; n < 16; n++) {              /* acc_h exactness: partial sums < 2^13 */
-        long double sh = 0;
-        for (int k = 0; k < nk; k++) sh += 255.0L * fabsl(S.h[k][n]);
-        if (sh >= 8192.0L) return JPGX_EARG;
-    }
-    return JPGX_OK;
-}
-
-/* operand [part][which][lane][e]: which 0 / 1 = Y of set 0 / set 1 (K = 32: 24 bytes + bias),
- * 2.. = chroma k-steps (k = 32 (which - 2) + 8 (l >> 4) + e); lane l holds B[k][column l & 15] */
-static int mxc_operands(int sub, uint16_t (*ops)[5][64][8])
-{
-    std::unique_ptr<MxSplit> S_(new MxSplit);   /* heap, per call: reentrant across threads */
-    MxSplit &S = *S_;
-    std::unique_ptr<MxcSplit> C_(new MxcSplit);
-    MxcSplit &C = *C_;
-    int rc = mx_split(S);
-    if (!rc) rc = mxc_split(sub, C);
-    if (rc) return rc;
-    for (int part = 0; part < JX_MX_PARTS; part++)
-        for (int which = 0; which < 5; which++)
-            for (int l = 0; l < 64; l++)
-                for (int e = 0; e < 8; e++) {
-                    const int j = l & 15;
-                    uint16_t v = 0;
-                    if (which < 2) {
-                        const int k = 8 * (l >> 4) + e;
-                        const bool on = which == 0 ? j < 8 : j >= 8;
-                        if (on && k <= 24) {
-                            const int n = j & 7;
-                            v = part == 0 ? S.bh[k][n] : (part == 1 ? S.bl[k][n] : S.bm[k][n]);
-                        }
-                    } else {
-                        const int k = 32 * (which - 2) + 8 * (l >> 4) + e;
-                        if (k < mxc_nk(sub)) v = part == 0 ? C.bh[k][j] : (part == 1 ? C.bl[k][j] : C.bm[k][j]);
-                    }
-                    ops[part][which][l][e] = v;
-                }
-    return JPGX_OK;
-}
-
-extern "C" int jx_mx422_operands(uint16_t ops[JX_MX_PARTS][4][64][8])
-{
-    std::unique_ptr<uint16_t[][5][64][8]> o5(new uint16_t[JX_MX_PARTS][5][64][8]);
-    const int rc = mxc_operands(1, o5.get());
-    if (rc) return rc;
-    for (int part = 0; part < JX_MX_PARTS; part++) memcpy(ops[part], o5[part], sizeof ops[part]);
-    return JPGX_OK;
-}
-
-extern "C" int jx_mx420_operands(uint16_t ops[JX_MX_PARTS][5][64][8])
-{
-    return mxc_operands(2, ops);
-}
-
-/* Interval + error bound of a chroma row transform R (column n = 8 c' + u) */
-static Bnd mxc_row_bound(int sub, const MxcSplit &S, int n)
-{
-    long double loh = 0, hih = 0, lol = 0, hil = 0, sl = 0, rep = 0;
-    for (int k = 0; k < mxc_nk(sub); k++) {    /* bytes 0..255 */
-        const long double bh = S.h[k][n], bo = S.l[k][n] + S.m[k][n];
-        loh += std::min(0.0L, 255.0L * bh);
-        hih += std::max(0.0L, 255.0L * bh);
-        lol += std::min(0.0L, 255.0L * bo);
-        hil += std::max(0.0L, 255.0L * bo);
-        sl += 255.0L * (fabsl(S.l[k][n]) + fabsl(S.m[k][n]));
-        rep += 255.0L * fabsl(mxc_exact(sub, k, n) - S.h[k][n] - S.l[k][n] - S.m[k][n]);
-    }
-    /* acc_l: per lo part mxc_ksteps MFMAs of 32 products plus the accumulator input, every
-     * addition charged one ulp of the magnitude bound, twice over (unknown summation tree and
-     * rounding mode) */
-    const double nadd = 2.0 * ((32.0 * mxc_ksteps(sub) + 1.0) * (JX_MX_PARTS - 1));
-    const double el = (double)(nadd * sl * 0x1p-23L + rep);
-    return BoundOps::add(Bnd{(double)loh, (double)hih, 0.0},
-                         Bnd{(double)lol - el, (double)hil + el, el});
-}
-
-/* plan columns n = 8 c + u as jx_mxtab: c = 0 Y (k_mx's bound), 1 Cb, 2 Cr (subsampled rows) */
-static int mxc_plan_tables(int sub, int quality, float w[24][8], float lim[24][8], int16_t q[2][64])
-{
-    int qs[2][8][8];
-    int rc = jpgx_scale_table(0, quality, qs[0]);
-    if (rc) return rc;
-    jpgx_scale_table(1, quality, qs[1]);
-    for (int t = 0; t < 2; t++)
-        for (int u = 0; u < 8; u++)
-            for (int v = 0; v < 8; v++) q[t][u * 8 + v] = (int16_t)qs[t][u][v];
-    std::unique_ptr<MxSplit> S_(new MxSplit);   /* heap, per call: reentrant across threads */
-    MxSplit &S = *S_;
-    std::unique_ptr<MxcSplit> C_(new MxcSplit);
-    MxcSplit &C = *C_;
-    rc = mx_split(S);
-    if (!rc) rc = mxc_split(sub, C);
-    if (rc) return rc;
-    const long double a0 = 1.0L / sqrtl(2.0L);
-    for (int n = 0; n < 24; n++) {
-        const int c = n / 8, u = n % 8, t = c == 0 ? 0 : 1;
-        const Bnd R = c == 0 ? mx_row_bound(S, n) : mxc_row_bound(sub, C, n - 8);
-        Bnd col[8], out[8];
-        for (int y = 0; y < 8; y++) col[y] = R;
-        jx_fdct8<BoundOps>(col, out);
-        for (int v = 0; v < 8; v++) {
-            const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
-            const long double ws = 0.25L * au * av * dct_kfactor(v) / (long double)qs[t][u][v];
-            const float wf = (float)ws;
-            const Bnd &b = out[v];
-            const double mF = BoundOps::mag(b) + b.E;
-            double et = b.E * fabs((double)wf) + mF * (double)fabsl((long double)wf - ws) + 0x1p-25;
-            et = et * 1.01 + 1e-7;
-            w[n][v] = wf;
-            lim[n][v] = (float)(0.5 - et);
-        }
-    }
-    return JPGX_OK;
+    return mx_plan_tables(0, quality, w, lim, q);
 }
 
 extern "C" int jx_plan_tables_mx422(int quality, float w[24][8], float lim[24][8], int16_t q[2][64])
 {
-    return mxc_plan_tables(1, quality, w, lim, q);
+    return mx_plan_tables(1, quality, w, lim, q);
 }
 
 extern "C" int jx_plan_tables_mx420(int quality, float w[24][8], float lim[24][8], int16_t q[2][64])
 {
-    return mxc_plan_tables(2, quality, w, lim, q);
+    return mx_plan_tables(2, quality, w, lim, q);
 }
 
-/* Host emulation of the subsampled chroma fast path (acc_h exact, acc_l in fp32, R = fl(acc_h +
- * 2^-12 acc_l), FOps column pass, quantiser) against the definition's exact quotient on random
- * MCUs: unflagged mismatches (must be 0), flagged count, worst error / band. */
-static long long mxc_selftest(int sub, long long nblocks, unsigned long long seed, int quality,
-                              long long *flagged, double *ratio)
+/* the emulation's test rows: random bytes, every fourth block flat, and for the chroma modes every
+ * fourth saturated red */
+static void mx_selftest_rows(int mode, long long bk, int nk, uint64_t &s, int px[8][96])
 {
-    std::unique_ptr<MxcSplit> C_(new MxcSplit);
-    MxcSplit &C = *C_;
-    if (mxc_split(sub, C)) return -1;
+    for (int y = 0; y < 8; y++)
+        for (int k = 0; k < nk; k++) {
+            s = s * 6364136223846793005ULL + 1442695040888963407ULL;
+            px[y][k] = (int)(s >> 56);
+            if ((bk & 3) == 1) px[y][k] = px[0][k % 3];      /* flat blocks too */
+            if (mode && (bk & 3) == 2) px[y][k] = (k % 3 == 0) ? 255 : 0;
+        }
+}
+
+/* the exact sample X of a row of channel c (the definition): mode 0 the level-shifted colour of
+ * pixel X from double coefficients, mode 1 / 2 the average of the pair's / quad's chroma */
+static long double mx_selftest_sample(int mode, int c, const int *row, int X)
+{
+    if (mode == 0) {
+        long double s = (long double)kMxA[c][0] * row[3 * X] + (long double)kMxA[c][1] * row[3 * X + 1] +
+                        (long double)kMxA[c][2] * row[3 * X + 2];
+        s += c == 0 ? -128.0L : 0.0L;
+        return s;
+    }
+    long double cs = 0;
+    for (int r = 0; r < mode; r++)
+        for (int h = 0; h < 2; h++) {
+            const int x = 2 * X + h, o = 48 * r + 3 * x;
+            cs += (long double)kMxA[c][0] * row[o] + (long double)kMxA[c][1] * row[o + 1] +
+                  (long double)kMxA[c][2] * row[o + 2];
+        }
+    return (mode == 1 ? 0.5L : 0.25L) * cs;
+}
+
+/* Host emulation of a kernel's fast path on random rows (acc_h exact, acc_l summed in fp32,
+ * R = fl(acc_h + acc_l), then the kernel's FOps column pass and quantiser) against the exact
+ * quotient 1/4 a(u) a(v) sum_x sum_y X c_u(x) c_v(y) / Q: counts the coefficients whose unflagged
+ * fp32 result differs from round(exact quotient) (must be 0) and the flagged ones.  ratio[0] = max
+ * |fp32 quotient - exact| / (0.5 - lim).  Mode 0 covers k_mxs's 24 plan columns, mode 1 / 2 the 16
+ * chroma columns of k_mxs422 / k_mxs420 (their Y is mode 0's). */
+static long long mx_selftest(int mode, long long nblocks, unsigned long long seed, int quality,
+                             long long *flagged, double *ratio)
+{
+    MxSplitPtr S_(new MxSplit);
+    const MxSplit &S = *S_;
+    if (mx_split(mode, *S_)) return -1;
     float w[24][8], lim[24][8];
     int16_t q[2][64];
-    if (mxc_plan_tables(sub, quality, w, lim, q)) return -1;
+    if (mx_plan_tables(mode, quality, w, lim, q)) return -1;
     const long double pi = 3.141592653589793238462643383279502884L;
     const long double a0 = 1.0L / sqrtl(2.0L);
-    const int nk = mxc_nk(sub);
+    long double cs[8][8];                       /* cos((2x+1) u pi/16) at [x][u] */
+    for (int x = 0; x < 8; x++)
+        for (int u = 0; u < 8; u++) cs[x][u] = cosl((2 * x + 1) * u * pi / 16);
     uint64_t s = seed;
     long long bad = 0, nfl = 0;
     double worst = 0;
     for (long long bk = 0; bk < nblocks; bk++) {
-        int px[8][96];                          /* chroma row y: [r][16 pixels][3] */
-        for (int y = 0; y < 8; y++)
-            for (int k = 0; k < nk; k++) {
-                s = s * 6364136223846793005ULL + 1442695040888963407ULL;
-                px[y][k] = (int)(s >> 56);
-                if ((bk & 3) == 1) px[y][k] = px[0][k % 3];      /* flat blocks too */
-                if ((bk & 3) == 2) px[y][k] = (k % 3 == 0) ? 255 : 0;
-            }
-        for (int n = 0; n < 16; n++) {
-            const int c = 1 + n / 8, u = n % 8, pn = 8 + n;
+        int px[8][96];                          /* row y: mode 0 [8 pixels][3], else [r][16 pixels][3] */
+        mx_selftest_rows(mode, bk, S.nk, s, px);
+        for (int n = 0; n < S.ncol; n++) {
+            const int pn = 24 - S.ncol + n, c = pn / 8, u = pn % 8;      /* plan column */
             float R[8];
             for (int y = 0; y < 8; y++) {
-                long double ah = 0;
-                float al = 0.0f;
-                for (int k = 0; k < nk; k++) {
+                long double ah = S.h[S.nk][n];
+                float al = (float)(S.l[S.nk][n] + S.m[S.nk][n]);
+                for (int k = 0; k < S.nk; k++) {
                     const int sv = px[y][k];
-                    ah += sv * C.h[k][n];
-                    al = al + (float)(sv * C.l[k][n]);
-                    if (JX_MX_PARTS == 3) al = al + (float)(sv * C.m[k][n]);
+                    ah += sv * S.h[k][n];
+                    al = al + (float)(sv * S.l[k][n]);
+                    if (JX_MX_PARTS == 3) al = al + (float)(sv * S.m[k][n]);
                 }
                 R[y] = (float)ah + al;
             }
@@ -795,19 +728,10 @@ static long long mxc_selftest(int sub, long long nblocks, unsigned long long see
             for (int v = 0; v < 8; v++) {
                 long double sum = 0;
                 for (int y = 0; y < 8; y++)
-                    for (int X = 0; X < 8; X++) {
-                        long double cs = 0;
-                        for (int r = 0; r < sub; r++)
-                            for (int h = 0; h < 2; h++) {
-                                const int x = 2 * X + h, o = 48 * r + 3 * x;
-                                cs += (long double)kMxA[c][0] * px[y][o] + (long double)kMxA[c][1] * px[y][o + 1] +
-                                      (long double)kMxA[c][2] * px[y][o + 2];
-                            }
-                        sum += (sub == 1 ? 0.5L : 0.25L) * cs * cosl((2 * X + 1) * u * pi / 16) *
-                               cosl((2 * y + 1) * v * pi / 16);
-                    }
+                    for (int X = 0; X < 8; X++)
+                        sum += mx_selftest_sample(mode, c, px[y], X) * cs[X][u] * cs[y][v];
                 const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
-                const long double qx = 0.25L * au * av * sum / q[1][u * 8 + v];
+                const long double qx = 0.25L * au * av * sum / q[c == 0 ? 0 : 1][u * 8 + v];
                 const float tm = fmaf(F[v], w[pn][v], 12582912.0f);
                 const float rr = tm - 12582912.0f;
                 const float d = fmaf(F[v], w[pn][v], -rr);
@@ -827,88 +751,20 @@ static long long mxc_selftest(int sub, long long nblocks, unsigned long long see
     return bad;
 }
 
+extern "C" long long jx_selftest_mx(long long nblocks, unsigned long long seed, int quality,
+                                    long long *flagged, double *ratio)
+{
+    return mx_selftest(0, nblocks, seed, quality, flagged, ratio);
+}
+
 extern "C" long long jx_selftest_mx422(long long nblocks, unsigned long long seed, int quality,
                                        long long *flagged, double *ratio)
 {
-    return mxc_selftest(1, nblocks, seed, quality, flagged, ratio);
+    return mx_selftest(1, nblocks, seed, quality, flagged, ratio);
 }
 
 extern "C" long long jx_selftest_mx420(long long nblocks, unsigned long long seed, int quality,
                                        long long *flagged, double *ratio)
 {
-    return mxc_selftest(2, nblocks, seed, quality, flagged, ratio);
-}
-
-/* Host emulation of k_mx's fast path on random blocks (acc_h exact, acc_l summed in fp32,
- * R = fl(acc_h + acc_l), then the kernel's FOps column pass and quantiser): counts the
- * coefficients whose unflagged fp32 result differs from round(exact quotient) (must be 0)
- * and the flagged ones.  ratio[0] = max |fp32 quotient - exact| / (0.5 - lim). */
-extern "C" long long jx_selftest_mx(long long nblocks, unsigned long long seed, int quality,
-                                    long long *flagged, double *ratio)
-{
-    std::unique_ptr<MxSplit> S_(new MxSplit);   /* heap, per call: reentrant across threads */
-    MxSplit &S = *S_;
-    if (mx_split(S)) return -1;
-    float w[24][8], lim[24][8];
-    int16_t q[2][64];
-    if (jx_plan_tables_mx(quality, w, lim, q)) return -1;
-    const long double pi = 3.141592653589793238462643383279502884L;
-    const long double a0 = 1.0L / sqrtl(2.0L);
-    uint64_t s = seed;
-    long long bad = 0, nfl = 0;
-    double worst = 0;
-    for (long long bk = 0; bk < nblocks; bk++) {
-        int px[8][24];
-        for (int y = 0; y < 8; y++)
-            for (int k = 0; k < 24; k++) {
-                s = s * 6364136223846793005ULL + 1442695040888963407ULL;
-                px[y][k] = (int)(s >> 56);
-                if ((bk & 3) == 1) px[y][k] = px[0][k % 3];      /* flat blocks too */
-            }
-        for (int n = 0; n < 24; n++) {
-            const int c = n / 8, u = n % 8;
-            float R[8];
-            for (int y = 0; y < 8; y++) {
-                long double ah = S.h[24][n];
-                float al = (float)(S.l[24][n] + S.m[24][n]);
-                for (int k = 0; k < 24; k++) {
-                    const int sv = px[y][k];
-                    ah += sv * S.h[k][n];
-                    al = al + (float)(sv * S.l[k][n]);
-                    if (JX_MX_PARTS == 3) al = al + (float)(sv * S.m[k][n]);
-                }
-                R[y] = (float)ah + al;
-            }
-            float F[8];
-            jx_fdct8<FOps>(R, F);
-            for (int v = 0; v < 8; v++) {
-                /* exact: 1/4 a(u) a(v) sum_x sum_y X c_u(x) c_v(y) / Q, X from double colours */
-                long double sum = 0;
-                for (int y = 0; y < 8; y++)
-                    for (int x = 0; x < 8; x++) {
-                        long double X = (long double)kMxA[c][0] * px[y][3 * x] +
-                                        (long double)kMxA[c][1] * px[y][3 * x + 1] +
-                                        (long double)kMxA[c][2] * px[y][3 * x + 2];
-                        X += c == 0 ? -128.0L : 0.0L;
-                        sum += X * cosl((2 * x + 1) * u * pi / 16) * cosl((2 * y + 1) * v * pi / 16);
-                    }
-                const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
-                const long double qx = 0.25L * au * av * sum / q[c == 0 ? 0 : 1][u * 8 + v];
-                const float tm = fmaf(F[v], w[n][v], 12582912.0f);
-                const float rr = tm - 12582912.0f;
-                const float d = fmaf(F[v], w[n][v], -rr);
-                const double qf = (double)F[v] * (double)w[n][v];
-                const double band = 0.5 - (double)lim[n][v];
-                worst = std::max(worst, (double)fabsl((long double)qf - qx) / band);
-                if (fabsf(d) >= lim[n][v]) {
-                    nfl++;
-                    continue;
-                }
-                if ((long double)rr != roundl(qx)) bad++;
-            }
-        }
-    }
-    if (flagged) *flagged = nfl;
-    if (ratio) *ratio = worst;
-    return bad;
+    return mx_selftest(2, nblocks, seed, quality, flagged, ratio);
 }

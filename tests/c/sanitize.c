@@ -8,7 +8,8 @@
  *     huge dimensions, W*H*3 beyond the file, wrong bit depth, empty, missing) -- the loader
  *     restates bitmap.c:41-152, which trusts its header;
  *   - validation, defaults, the glibc underflow model, scale tables, the guard-band planning
- *     (jpgx_plan.cpp, every quality, both kernels' tables) and stripes;
+ *     (jpgx_plan.cpp, every quality, every kernel's tables; the MFMA kernels' operands and a
+ *     short run of the 4:2:x band emulation) and stripes;
  *   - the oracle's whole hot path, including the modelled x0 = -8 underflow read
  *     (preprocess.c:159-160) at block-row 0 and inside stripes, the true 4:2:x
  *     definition, the entropy statistics and the BMP decode of hostile buffers;
@@ -28,7 +29,15 @@
 int jx_plan_tables(int quality, float w[3][64], float lim[3][64], int16_t q[2][64]);
 int jx_plan_tables_mode(int quality, int sub, float w[3][64], float lim[3][64], int16_t q[2][64]);
 int jx_plan_tables_mx(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
+int jx_plan_tables_mx422(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
+int jx_plan_tables_mx420(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
 int jx_mx_operands(uint16_t ops[3 * 2][64][8]);
+int jx_mx422_operands(uint16_t ops[2][4][64][8]);
+int jx_mx420_operands(uint16_t ops[2][5][64][8]);
+long long jx_selftest_mx422(long long nblocks, unsigned long long seed, int quality, long long *flagged,
+                            double *ratio);
+long long jx_selftest_mx420(long long nblocks, unsigned long long seed, int quality, long long *flagged,
+                            double *ratio);
 int jx_mx_parts(void);
 long long jx_selftest_pk(long long nblocks, unsigned long long seed);
 
@@ -175,9 +184,26 @@ static void planning(void)
         for (int sub = 0; sub <= 2; sub++) CHECK(jx_plan_tables_mode(q, sub, s, lim, qq) == 0);
         float w[24][8], l2[24][8];
         CHECK(jx_plan_tables_mx(q, w, l2, qq) == 0);
+        CHECK(jx_plan_tables_mx422(q, w, l2, qq) == 0);
+        CHECK(jx_plan_tables_mx420(q, w, l2, qq) == 0);
     }
-    uint16_t ops[3 * 2][64][8];
-    if (jx_mx_parts() == 2) CHECK(jx_mx_operands(ops) == 0);
+    if (jx_mx_parts() == 2) {
+        /* exact-size heap buffers, so ASan sees any write outside the operand arrays */
+        uint16_t(*ops)[64][8] = malloc(sizeof(uint16_t[3 * 2][64][8]));
+        uint16_t(*ops422)[4][64][8] = malloc(sizeof(uint16_t[2][4][64][8]));
+        uint16_t(*ops420)[5][64][8] = malloc(sizeof(uint16_t[2][5][64][8]));
+        CHECK(jx_mx_operands(ops) == 0);
+        CHECK(jx_mx422_operands(ops422) == 0);
+        CHECK(jx_mx420_operands(ops420) == 0);
+        free(ops420);
+        free(ops422);
+        free(ops);
+    }
+    /* the band's emulation over the 48- and 96-byte chroma rows (run-time K): no unflagged miss */
+    long long flagged;
+    double ratio;
+    CHECK(jx_selftest_mx422(24, 5, 90, &flagged, &ratio) == 0 && ratio < 1.0);
+    CHECK(jx_selftest_mx420(24, 6, 90, &flagged, &ratio) == 0 && ratio < 1.0);
     CHECK(jx_selftest_pk(2000, 7) == 0);
     /* geometry edges */
     const int geo[][2] = {{0, 8}, {8, 0}, {-8, 8}, {12, 8}, {8, 12}, {8, 8}, {16, 16}, {1 << 20, 8}};
