@@ -174,6 +174,32 @@ int jpgx_entropy_stats_gpu_batch(const int16_t *d_coef, size_t coef_frame_stride
                                  size_t nb_c, const int32_t *carry, int32_t *d_dc, uint32_t *d_hist,
                                  void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* The JFIF files of a batch of frames, coded on the device from jpgx_blocks_gpu's output: frame
+ * f's file (SOI .. EOI) at d_out + f * out_frame_stride, its length in d_len[f].  The bytes are
+ * those of jpgx_write_jfif_ex (jpgx_compat.h) for the same coefficients, quality, sample_ratio and
+ * restart interval: Annex K Huffman tables, one interleaved scan, d_coef frames laid out
+ * [3][nb][64] (sample_ratio 0) or Y | Cb | Cr as JPGX_FLAG_SUBSAMPLE writes them (sample_ratio 1:
+ * 4:2:2, 2: 4:2:0), frame f at d_coef + f * coef_frame_stride int16 elements (a multiple of 64,
+ * at least one frame).
+ * The device path NEEDS restart intervals -- they are what it codes in parallel: restart_rows >= 1
+ * MCU rows per interval, or -1 for one MCU row per interval (NOT jpgx_write_jfif_ex's
+ * thread-count-dependent -1: pass 1 there for the same bytes).  JPGX_EARG for restart_rows 0 or
+ * below -1, for an interval above 65535 MCUs, nframes 0 or above 65535, out_frame_stride <
+ * out_cap, null or misaligned pointers (d_coef, d_out, d_workspace: 16 bytes; d_len: 8);
+ * JPGX_EWORKSPACE when workspace_bytes < jpgx_jfif_gpu_workspace_size() (0 for bad arguments).
+ * Every argument check happens before the first device call.
+ * Overflow: a frame that needs more than out_cap bytes writes nothing at or beyond out_cap in
+ * its slot; d_len[f] then has bit 63 set and its low bits hold a capacity that suffices whatever
+ * the byte stuffing (headers + 2 x unstuffed scan bytes + markers + EOI).  The other frames of
+ * the batch are unaffected.  Asynchronous on `stream`, capturable, no global state; the library
+ * initialises what it needs of the workspace itself. */
+size_t jpgx_jfif_gpu_workspace_size(int width, int height, int sample_ratio, int restart_rows,
+                                    size_t nframes, size_t out_cap);
+int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width,
+                  int height, int quality, int sample_ratio, int restart_rows, uint8_t *d_out,
+                  size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
+                  size_t workspace_bytes, void *stream);
+
 /* Synthetic frames, generated directly in device memory (SURVEY.md 8c generator G: byte k
  * of the buffer = splitmix64(seed + (k+1)*0x9E3779B97F4A7C15) >> 56). */
 int jpgx_gen_splitmix_gpu(uint8_t *d_dst, size_t nbytes, uint64_t seed, void *stream);

@@ -86,7 +86,7 @@ struct jx_mxtab {
 };
 
 struct jx_xform_args {
-    jx_geom g;
+    struct jx_geom g;
     int quality;            /* index into the device table                                */
     int force_exact;        /* JPGX_FLAG_FORCE_EXACT: flag every coefficient              */
     int luma_only;          /* k_xform: channel 0 only (chroma from k_chroma)             */
@@ -125,6 +125,19 @@ long long jx_selftest_mx420(long long nblocks, unsigned long long seed, int qual
  * 2: k_mxs420); the workgroup image it would upload for (force, quality), host only */
 int jx_launch_mx(const struct jx_xform_args *xa, int sr, void *stream, void *ev_start, void *ev_stop);
 long long jx_mx_image(int sr, int force, int quality, void *dst, long long cap);
+/* the JFIF writer's tables and header bytes (host/jpgx_jfif.c), shared by jpgx_write_jfif_ex and
+ * the device coder (csrc/jpgx_jfif.hip).
+ * jx_jfif_codes: the canonical Huffman codes of the Annex K.3 tables (T.81 Annex C) indexed by
+ * symbol, packed code << 8 | length; cl[0] DC luminance, cl[1] AC luminance, cl[2] DC chrominance,
+ * cl[3] AC chrominance.
+ * jx_jfif_header: SOI .. SOS for a width x height frame of `quality`, Y sampled hs x vs by
+ * sample_ratio (0: 1x1, 1: 2x1, 2: 2x2), with a DRI segment of `ri` MCUs when ri != 0.  Writes
+ * the first `cap` of them into out and returns their number (at most JX_JFIF_HDR_MAX; 0 when
+ * the quality is outside 1..97). */
+#define JX_JFIF_HDR_MAX 768
+void jx_jfif_codes(uint32_t cl[4][256]);
+size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
+                      uint8_t *out, size_t cap);
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,556 @@
+/*
+ * jpgx_jfif.hip -- the JFIF writer's scan on the device: the bytes of
+ * jpgx_write_jfif_ex (host/jpgx_jfif.c) with restart intervals, for a batch of frames whose
+ * coefficients are in device memory.
+ *
+ * A restart interval is self-contained (DC predictors reset, byte aligned), so one workgroup
+ * codes one interval, its lanes looping over the interval's blocks in scan order (MCU by MCU:
+ * hs x vs luma blocks, Cb, Cr).  Five launches per batch:
+ *   k_jf_len    per block the coded bit count (the DC predecessor is the previous block of the
+ *               same component in scan order -- a lookup, not a recurrence), a workgroup
+ *               exclusive scan -> each block's bit offset within its interval, the interval's bits
+ *   k_jf_place  per frame: the intervals' 16-byte-aligned places in the unstuffed stream
+ *   k_jf_pack   zeroes the interval's place, then every lane writes its block's codes at its
+ *               bit offset (interior words: stores; the partial first and last words, shared
+ *               with the neighbouring lanes' blocks, are merged in LDS), the last block also the
+ *               1-bit padding; then counts the interval's 0xFF bytes
+ *   k_jf_frame  per frame: the intervals' places in the file (uint64 scan of stuffed sizes and
+ *               RSTm markers), the frame's length or its overflow report, headers and EOI
+ *   k_jf_stuff  per interval: unstuffed bytes -> file bytes with 0xFF 0x00 stuffing, RSTm
+ * A lane keeps its block in LDS (its own 33-dword row: conflict-free when the lanes of a wave read
+ * the same coefficient) and walks only the nonzero coefficients (a 64-bit mask, ctz), as the host
+ * writer does.  The code tables and the header bytes come from the host writer's own functions
+ * (jx_jfif_codes, jx_jfif_header) as by-value kernel arguments: nothing is copied with a memcpy,
+ * the call is asynchronous, capturable and keeps no state.
+ */
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "jpgx_internal.h"
+
+namespace {
+
+constexpr int kT = 256;                 /* threads per workgroup (4 waves) */
+constexpr int kRow = 33;                /* LDS dwords per lane's block (32 + 1: bank = lane + k / 2) */
+
+struct JfTabs {                         /* code << 8 | length */
+    uint32_t dc[2][16];                 /* [luma, chroma][category] */
+    uint32_t ac[2][256];                /* [luma, chroma][run << 4 | category] */
+};
+
+struct JfHdr {
+    uint8_t b[JX_JFIF_HDR_MAX];
+};
+
+struct JfArgs {
+    const int16_t *coef;                /* frame f: Y [nb][64] | Cb [nbc][64] | Cr [nbc][64] at f fstride */
+    unsigned long long fstride;         /* int16 elements */
+    uint32_t hs, lum, bpm;              /* Y blocks per MCU row of blocks, per MCU; blocks per MCU */
+    uint32_t vs, bpr, cpr, mrows;       /* Y blocks per row, MCUs per row, MCU rows */
+    uint32_t rpi, ni;                   /* MCU rows per interval, intervals per frame */
+    uint32_t nb, nbc, nblkf;            /* blocks: Y, per chroma plane, per frame */
+    uint32_t ivblk;                     /* blocks of a full interval */
+    uint32_t hdrlen;
+    uint32_t *offs;                     /* [nframes][nblkf] bit offset within the interval (scan order) */
+    uint32_t *ibits;                    /* [nframes][ni] coded bits of the interval */
+    uint32_t *nff;                      /* [nframes][ni] 0xFF bytes of the interval (padding included) */
+    unsigned long long *ustart;         /* [nframes][ni] place in the frame's unstuffed stream */
+    unsigned long long *ostart;         /* [nframes][ni] place in the frame's file */
+    uint32_t *ovf;                      /* [nframes] the frame does not fit */
+    uint8_t *ustream;                   /* [nframes][uarea] */
+    unsigned long long uarea;
+    uint8_t *out;
+    unsigned long long ostride, ocap;
+    unsigned long long *len;
+};
+
+/* block (MCU m of interval iv, position j in the MCU) in the frame's coefficient array */
+__device__ __forceinline__ size_t jf_block(const JfArgs &a, uint32_t iv, uint32_t m, uint32_t j)
+{
+    const uint32_t mr = m / a.cpr, mx = m - mr * a.cpr, my = iv * a.rpi + mr;
+    if (j < a.lum) {
+        const uint32_t dy = j / a.hs, dx = j - dy * a.hs;
+        return (size_t)(my * a.vs + dy) * a.bpr + mx * a.hs + dx;
+    }
+    return (size_t)a.nb + (size_t)(j - a.lum) * a.nbc + (size_t)my * a.cpr + mx;
+}
+
+/* the interval's block count */
+__device__ __forceinline__ uint32_t jf_nblk(const JfArgs &a, uint32_t iv)
+{
+    const uint32_t r0 = iv * a.rpi;
+    const uint32_t rows = min(a.rpi, a.mrows - r0);
+    return rows * a.cpr * a.bpm;
+}
+
+typedef uint32_t jf_u4 __attribute__((ext_vector_type(4)));
+
+/* scan-order block i of interval iv of frame f into this lane's LDS row; returns the mask of its
+ * nonzero coefficients, the DC difference (clamped as the host writer clamps it) and whether it is
+ * a chroma block */
+__device__ __forceinline__ uint64_t jf_load(const JfArgs &a, uint32_t f, uint32_t iv, uint32_t i, uint32_t *row,
+                                            int &diff, uint32_t &chroma)
+{
+    const uint32_t m = i / a.bpm, j = i - m * a.bpm;
+    const int16_t *base = a.coef + (size_t)f * a.fstride;
+    const int16_t *z = base + jf_block(a, iv, m, j) * 64;
+    /* the previous block of the same component: the luma block before it in the MCU, else the
+     * previous MCU's last luma block / same chroma block; none at the interval's first MCU */
+    int pred = 0;
+    if (j > 0 && j < a.lum) pred = base[jf_block(a, iv, m, j - 1) * 64];
+    else if (m > 0) pred = base[jf_block(a, iv, m - 1, j == 0 ? a.lum - 1 : j) * 64];
+    uint64_t nz = 0;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        /* plain loads: a lane's eight loads share one 128-byte line, which must stay in L1 between
+         * them (nontemporal loads: 427 instead of 335 us per 8 x 4K batch) */
+        const jf_u4 x = ((const jf_u4 *)z)[r];
+        const uint32_t w[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            row[4 * r + e] = w[e];
+            const uint64_t two = ((w[e] & 0xffffu) ? 1u : 0u) | ((w[e] >> 16) ? 2u : 0u);
+            nz |= two << (8 * r + 2 * e);
+        }
+    }
+    int d = (int)(int16_t)(row[0] & 0xffffu) - pred;
+    d = d > 2047 ? 2047 : d;
+    d = d < -2047 ? -2047 : d;
+    diff = d;
+    chroma = j >= a.lum ? 1u : 0u;
+    return nz & ~1ull;
+}
+
+/* magnitude category and the value's additional bits (T.81 F.1.2.1) */
+__device__ __forceinline__ uint32_t jf_category(int v, uint32_t &extra)
+{
+    const uint32_t a = (uint32_t)(v < 0 ? -v : v);
+    const uint32_t s = a ? 32u - (uint32_t)__builtin_clz(a) : 0u;
+    extra = (uint32_t)(v < 0 ? v + (1 << s) - 1 : v) & ((1u << s) - 1u);
+    return s;
+}
+
+/* counts bits */
+struct BitCount {
+    uint32_t n;
+    __device__ __forceinline__ void put(uint32_t, uint32_t nb) { n += nb; }
+};
+
+/* writes bits MSB first from a bit offset.  The words a block covers whole are its own (plain
+ * stores).  The word it starts in and the word it ends in may be shared with the neighbouring
+ * blocks, whose lanes are the neighbouring lanes: those partial words are ORed into the
+ * workgroup's LDS slots (one per distinct word a lane of this pass starts in, k_jf_pack) and
+ * leave as one store each -- a global atomic per partial word costs more than the whole walk
+ * (eight and more blocks share a word).  Only the last lane's last word
+ * has no slot: it is shared with the next pass and goes to memory with an atomicOr. */
+struct BitPack {
+    uint32_t *wp;
+    uint32_t *slots;                    /* the workgroup's LDS slots */
+    uint32_t head, tail;                /* slots of the first and the last word; tail ~0: none */
+    uint64_t acc;                       /* the low nacc bits are pending */
+    uint32_t nacc;
+    bool first;
+    __device__ __forceinline__ void open(uint8_t *area, uint32_t bit, uint32_t *lds_slots, uint32_t head_slot,
+                                         uint32_t tail_slot)
+    {
+        wp = (uint32_t *)area + (bit >> 5);
+        slots = lds_slots;
+        head = head_slot;
+        tail = tail_slot;
+        acc = 0;
+        nacc = bit & 31u;               /* the bits before ours: zeros, neutral under OR */
+        first = true;
+    }
+    __device__ __forceinline__ void put(uint32_t v, uint32_t nb)   /* v < 2^nb, nb <= 27 */
+    {
+        acc = (acc << nb) | v;
+        nacc += nb;
+        if (nacc >= 32u) {
+            nacc -= 32u;
+            const uint32_t x = __builtin_bswap32((uint32_t)(acc >> nacc));
+            if (first) atomicOr(slots + head, x);
+            else *wp = x;
+            first = false;
+            wp++;
+        }
+    }
+    __device__ __forceinline__ void close()
+    {
+        if (!nacc) return;
+        const uint32_t x = __builtin_bswap32((uint32_t)(acc << (32u - nacc)));
+        if (first) atomicOr(slots + head, x);   /* the block ends in the word it starts in */
+        else if (tail != ~0u) atomicOr(slots + tail, x);
+        else atomicOr(wp, x);
+    }
+};
+
+/* one block's Huffman-coded data (T.81 F.1.2), as encode_block of host/jpgx_jfif.c */
+template <class W>
+__device__ __forceinline__ void jf_code(W &w, const uint32_t *row, uint64_t nz, int diff, const uint32_t *dc,
+                                        const uint32_t *ac)
+{
+    uint32_t extra;
+    uint32_t s = jf_category(diff, extra);
+    uint32_t c = dc[s];
+    w.put((c >> 8) << s | extra, (c & 0xffu) + s);
+    uint32_t prev = 0;
+    uint32_t k = nz ? (uint32_t)__builtin_ctzll(nz) : 0u;
+    uint32_t word = row[k >> 1];
+    while (nz) {                        /* one code per turn: a ZRL while the run exceeds 15 */
+        const uint32_t run = k - prev - 1u;
+        const bool zrl = run > 15u;
+        /* the next turn's coefficient is read under this turn's table lookup */
+        const uint64_t nzn = zrl ? nz : nz & (nz - 1);
+        const uint32_t kn = nzn ? (uint32_t)__builtin_ctzll(nzn) : 0u;
+        const uint32_t wordn = row[kn >> 1];
+        int v = (k & 1u) ? (int)word >> 16 : (int)(int16_t)(word & 0xffffu);
+        v = v > 1023 ? 1023 : v;
+        v = v < -1023 ? -1023 : v;
+        s = jf_category(v, extra);
+        c = ac[zrl ? 0xf0u : (run << 4 | s)];
+        s = zrl ? 0u : s;
+        extra = zrl ? 0u : extra;
+        prev = zrl ? prev + 16u : k;
+        nz = nzn;
+        k = kn;
+        word = wordn;
+        w.put((c >> 8) << s | extra, (c & 0xffu) + s);
+    }
+    if (prev < 63u) {
+        c = ac[0x00];
+        w.put(c >> 8, c & 0xffu);
+    }
+}
+
+/* workgroup exclusive scan (kT threads); total = the sum.  wtot: LDS [kT / 64] */
+template <class T>
+__device__ __forceinline__ T jf_scan(T x, T *wtot, T &total)
+{
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    T incl = x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(incl, o, 64);
+        if (lane >= (unsigned)o) incl += y;
+    }
+    if (lane == 63u) wtot[wave] = incl;
+    __syncthreads();
+    T base = 0;
+    total = 0;
+#pragma unroll
+    for (unsigned w = 0; w < kT / 64; w++) {
+        const T y = wtot[w];
+        if (w < wave) base += y;
+        total += y;
+    }
+    __syncthreads();                    /* wtot is free again */
+    return base + incl - x;
+}
+
+__device__ __forceinline__ void jf_tabs_to_lds(const JfTabs &t, uint32_t (*dc)[16], uint32_t (*ac)[256])
+{
+    for (unsigned i = threadIdx.x; i < 512u; i += kT) (&ac[0][0])[i] = (&t.ac[0][0])[i];
+    if (threadIdx.x < 32u) (&dc[0][0])[threadIdx.x] = (&t.dc[0][0])[threadIdx.x];
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kT) void k_jf_len(const JfArgs a, const JfTabs tabs)
+{
+    __shared__ uint32_t tile[kT * kRow];
+    __shared__ uint32_t dc[2][16], ac[2][256];
+    __shared__ uint32_t wtot[kT / 64];
+    const uint32_t iv = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    jf_tabs_to_lds(tabs, dc, ac);
+    const uint32_t n = jf_nblk(a, iv);
+    uint32_t *offs = a.offs + (size_t)f * a.nblkf + (size_t)iv * a.ivblk;
+    uint32_t carry = 0;
+    for (uint32_t i0 = 0; i0 < n; i0 += kT) {
+        const uint32_t i = i0 + t;
+        BitCount w{0};
+        if (i < n) {
+            int diff;
+            uint32_t ch;
+            const uint64_t nz = jf_load(a, f, iv, i, tile + t * kRow, diff, ch);
+            jf_code(w, tile + t * kRow, nz, diff, dc[ch], ac[ch]);
+        }
+        uint32_t total;
+        const uint32_t ex = jf_scan(w.n, wtot, total);
+        if (i < n) offs[i] = carry + ex;
+        carry += total;
+    }
+    if (t == 0) a.ibits[(size_t)f * a.ni + iv] = carry;
+}
+
+/* the intervals' places in the frame's unstuffed stream, 16-byte aligned so that no word (and no
+ * 16-byte read of k_jf_stuff) is shared by two workgroups; a frame whose places do not fit its
+ * area (out_cap + 16 bytes per interval) cannot fit out_cap either */
+__global__ __launch_bounds__(kT) void k_jf_place(const JfArgs a)
+{
+    __shared__ unsigned long long wtot[kT / 64];
+    const uint32_t f = blockIdx.x, t = threadIdx.x;
+    unsigned long long carry = 0;
+    for (uint32_t i0 = 0; i0 < a.ni; i0 += kT) {
+        const uint32_t iv = i0 + t;
+        unsigned long long sz = 0;
+        if (iv < a.ni) sz = ((unsigned long long)((a.ibits[(size_t)f * a.ni + iv] + 7u) >> 3) + 15ull) & ~15ull;
+        unsigned long long total;
+        const unsigned long long ex = jf_scan(sz, wtot, total);
+        if (iv < a.ni) a.ustart[(size_t)f * a.ni + iv] = carry + ex;
+        carry += total;
+    }
+    if (t == 0) a.ovf[f] = carry > a.uarea ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const JfTabs tabs)
+{
+    __shared__ uint32_t tile[kT * kRow];
+    __shared__ uint32_t dc[2][16], ac[2][256];
+    __shared__ uint32_t wtot[kT / 64];
+    __shared__ uint32_t slot[kT], hws[kT], rk[kT];
+    const uint32_t iv = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    if (a.ovf[f]) return;
+    jf_tabs_to_lds(tabs, dc, ac);
+    const uint32_t n = jf_nblk(a, iv);
+    const uint32_t bits = a.ibits[(size_t)f * a.ni + iv];
+    const uint32_t nbytes = (bits + 7u) >> 3, nchunk = (nbytes + 15u) >> 4;
+    uint8_t *area = a.ustream + (size_t)f * a.uarea + a.ustart[(size_t)f * a.ni + iv];
+    for (uint32_t c = t; c < nchunk; c += kT) ((uint4 *)area)[c] = make_uint4(0, 0, 0, 0);
+    __syncthreads();                    /* the interval's place is zero before any lane ORs into it */
+    const uint32_t *offs = a.offs + (size_t)f * a.nblkf + (size_t)iv * a.ivblk;
+    for (uint32_t i0 = 0; i0 < n; i0 += kT) {
+        const uint32_t i = i0 + t;
+        const bool live = i < n;
+        const uint32_t off = live ? offs[i] : 0u;
+        /* slots: lane t starts in word hw; the distinct hw of this pass, in lane order, are the
+         * slots (rank = the number of lanes before t that start a new word) */
+        slot[t] = 0;
+        hws[t] = live ? off >> 5 : ~0u;
+        __syncthreads();
+        const uint32_t opens = live && (t == 0 || hws[t - 1] != (off >> 5)) ? 1u : 0u;
+        uint32_t nslots;
+        const uint32_t rank = jf_scan(opens, wtot, nslots) + opens - 1u;      /* live: lane 0 opens */
+        rk[t] = rank;
+        __syncthreads();
+        if (live) {
+            int diff;
+            uint32_t ch;
+            const uint64_t nz = jf_load(a, f, iv, i, tile + t * kRow, diff, ch);
+            const bool last = i + 1 == n || t + 1 == kT;       /* the next block is the next pass's */
+            BitPack w;
+            w.open(area, off, slot, rank, last ? ~0u : rk[t + 1]);
+            jf_code(w, tile + t * kRow, nz, diff, dc[ch], ac[ch]);
+            if (i + 1 == n) {           /* the interval's end: 1-bits up to the byte boundary */
+                const uint32_t pad = (8u - (bits & 7u)) & 7u;
+                if (pad) w.put((1u << pad) - 1u, pad);
+            }
+            w.close();
+        }
+        __syncthreads();                /* the slots are complete */
+        if (opens) {                    /* lane 0's word may hold the previous pass's last bits */
+            if (t == 0) atomicOr((uint32_t *)area + (off >> 5), slot[rank]);
+            else ((uint32_t *)area)[off >> 5] = slot[rank];
+        }
+        __syncthreads();                /* before the next pass clears the slots */
+    }
+    __syncthreads();                    /* every lane's stores and ORs are done */
+    /* the 0xFF bytes; loads at agent scope: the ORs were done in L2 */
+    uint32_t cnt = 0;
+    for (uint32_t c = t; c < 2u * nchunk; c += kT) {
+        const unsigned long long x =
+            __hip_atomic_load((const unsigned long long *)area + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int b = 0; b < 8; b++) cnt += ((x >> (8 * b)) & 0xffull) == 0xffull ? 1u : 0u;
+    }
+    uint32_t total;
+    jf_scan(cnt, wtot, total);
+    if (t == 0) a.nff[(size_t)f * a.ni + iv] = total;
+}
+
+/* per frame: where each interval's stuffed bytes go, the length (or the overflow report: bit 63 and
+ * a capacity that suffices whatever the stuffing -- headers + 2 x unstuffed bytes + markers + EOI),
+ * the header bytes and EOI */
+__global__ __launch_bounds__(kT) void k_jf_frame(const JfArgs a, const JfHdr hdr)
+{
+    __shared__ unsigned long long wtot[kT / 64];
+    __shared__ uint32_t fits;
+    const uint32_t f = blockIdx.x, t = threadIdx.x;
+    const bool early = a.ovf[f] != 0;
+    unsigned long long carry = a.hdrlen, raw = 0;
+    for (uint32_t i0 = 0; i0 < a.ni; i0 += kT) {
+        const uint32_t iv = i0 + t;
+        unsigned long long sz = 0, un = 0;
+        if (iv < a.ni) {
+            un = (a.ibits[(size_t)f * a.ni + iv] + 7u) >> 3;
+            sz = un + (early ? 0u : a.nff[(size_t)f * a.ni + iv]) + (iv + 1 < a.ni ? 2u : 0u);
+        }
+        unsigned long long total, rtotal;
+        const unsigned long long ex = jf_scan(sz, wtot, total);
+        jf_scan(un, wtot, rtotal);
+        if (iv < a.ni) a.ostart[(size_t)f * a.ni + iv] = carry + ex;
+        carry += total;
+        raw += rtotal;
+    }
+    const unsigned long long len = carry + 2;
+    if (t == 0) {
+        const bool ok = !early && len <= a.ocap;
+        fits = ok ? 1u : 0u;
+        a.ovf[f] = ok ? 0u : 1u;
+        a.len[f] = ok ? len : (1ull << 63) | (a.hdrlen + 2 * raw + 2ull * (a.ni - 1) + 2);
+    }
+    __syncthreads();
+    if (!fits) return;
+    uint8_t *out = a.out + (size_t)f * a.ostride;
+    for (uint32_t i = t; i < a.hdrlen; i += kT) out[i] = hdr.b[i];
+    if (t < 2) out[len - 2 + t] = t ? 0xd9 : 0xff;
+}
+
+/* unstuffed bytes -> file bytes: a lane takes 16 bytes, a workgroup scan of the 0xFF counts places
+ * them; RSTm (m = interval index mod 8) after every interval but the last */
+__global__ __launch_bounds__(kT) void k_jf_stuff(const JfArgs a)
+{
+    __shared__ uint32_t wtot[kT / 64];
+    const uint32_t iv = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    if (a.ovf[f]) return;
+    const uint32_t nbytes = (a.ibits[(size_t)f * a.ni + iv] + 7u) >> 3;
+    const uint8_t *area = a.ustream + (size_t)f * a.uarea + a.ustart[(size_t)f * a.ni + iv];
+    uint8_t *out = a.out + (size_t)f * a.ostride + a.ostart[(size_t)f * a.ni + iv];
+    uint32_t carry = 0;
+    for (uint32_t c0 = 0; 16u * c0 < nbytes; c0 += kT) {
+        const uint32_t c = c0 + t;
+        const uint32_t nv = 16u * c < nbytes ? min(16u, nbytes - 16u * c) : 0u;
+        uint4 q = make_uint4(0, 0, 0, 0);
+        if (nv) q = ((const uint4 *)area)[c];       /* bytes past nbytes in the place are zero */
+        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int b = 0; b < 16; b++) cnt += ((w[b >> 2] >> (8 * (b & 3))) & 0xffu) == 0xffu ? 1u : 0u;
+        uint32_t total;
+        uint32_t pos = 16u * c + carry + jf_scan(cnt, wtot, total);
+        carry += total;
+#pragma unroll
+        for (int b = 0; b < 16; b++) {
+            if ((uint32_t)b < nv) {
+                const uint32_t x = (w[b >> 2] >> (8 * (b & 3))) & 0xffu;
+                out[pos++] = (uint8_t)x;
+                if (x == 0xffu) out[pos++] = 0;
+            }
+        }
+    }
+    if (t < 2 && iv + 1 < a.ni) out[nbytes + carry + t] = t ? (uint8_t)(0xd0u + (iv & 7u)) : (uint8_t)0xff;
+}
+
+size_t r16(size_t x) { return (x + 15) / 16 * 16; }
+
+/* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0 */
+int jf_geometry(int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
+{
+    if (width <= 0 || height <= 0 || width % 8 || height % 8 || width > 65535 || height > 65535 ||
+        sample_ratio < 0 || sample_ratio > 2 || restart_rows == 0 || restart_rows < -1 || nframes == 0 ||
+        nframes > 65535)
+        return JPGX_EARG;
+    const uint32_t hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;
+    if (width % (8 * hs) || height % (8 * vs)) return JPGX_EGEOMETRY;
+    a.hs = hs;
+    a.vs = vs;
+    a.lum = hs * vs;
+    a.bpm = a.lum + 2;
+    a.bpr = (uint32_t)width / 8;
+    a.cpr = a.bpr / hs;
+    a.mrows = (uint32_t)height / 8 / vs;
+    a.nb = a.bpr * ((uint32_t)height / 8);
+    a.nbc = a.cpr * a.mrows;
+    a.nblkf = a.nb + 2 * a.nbc;
+    a.rpi = restart_rows > 0 ? (uint32_t)restart_rows : 1u;
+    if (a.rpi > 65535u / a.cpr) return JPGX_EARG;             /* Ri is a 16-bit field */
+    a.ni = (a.mrows + a.rpi - 1) / a.rpi;
+    a.ivblk = a.rpi * a.cpr * a.bpm;
+    return JPGX_OK;
+}
+
+struct JfLayout {
+    size_t offs, ibits, nff, ustart, ostart, ovf, ustream, uarea, total;
+};
+
+JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap)
+{
+    JfLayout l;
+    size_t at = 0;
+    l.offs = at, at += r16(nframes * a.nblkf * sizeof(uint32_t));
+    l.ibits = at, at += r16(nframes * a.ni * sizeof(uint32_t));
+    l.nff = at, at += r16(nframes * a.ni * sizeof(uint32_t));
+    l.ustart = at, at += r16(nframes * a.ni * sizeof(unsigned long long));
+    l.ostart = at, at += r16(nframes * a.ni * sizeof(unsigned long long));
+    l.ovf = at, at += r16(nframes * sizeof(uint32_t));
+    l.uarea = r16(out_cap) + 16 * (size_t)a.ni;
+    l.ustream = at, at += nframes * l.uarea;
+    l.total = at;
+    return l;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jpgx_jfif_gpu_workspace_size(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
+                                    size_t out_cap)
+{
+    JfArgs a;
+    if (jf_geometry(width, height, sample_ratio, restart_rows, nframes, a)) return 0;
+    return jf_layout(a, nframes, out_cap).total;
+}
+
+int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                  int quality, int sample_ratio, int restart_rows, uint8_t *d_out, size_t out_frame_stride,
+                  size_t out_cap, uint64_t *d_len, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    JfArgs a;
+    memset(&a, 0, sizeof a);
+    if (!d_coef || !d_out || !d_len || !d_workspace || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_out & 15) ||
+        ((uintptr_t)d_len & 7) || ((uintptr_t)d_workspace & 15))
+        return JPGX_EARG;
+    int rc = jf_geometry(width, height, sample_ratio, restart_rows, nframes, a);
+    if (rc) return rc;
+    if (coef_frame_stride % 64 || coef_frame_stride < (size_t)a.nblkf * 64 || out_frame_stride < out_cap)
+        return JPGX_EARG;
+    JfHdr hdr;
+    memset(&hdr, 0, sizeof hdr);
+    const size_t hl = jx_jfif_header(width, height, quality, sample_ratio, a.rpi * a.cpr, hdr.b, sizeof hdr.b);
+    if (!hl) return JPGX_EQUALITY;
+    if (hl > sizeof hdr.b) return JPGX_EARG;
+    const JfLayout l = jf_layout(a, nframes, out_cap);
+    if (workspace_bytes < l.total) return JPGX_EWORKSPACE;
+    uint32_t cl[4][256];
+    jx_jfif_codes(cl);
+    JfTabs tabs;
+    for (int c = 0; c < 2; c++) {
+        memcpy(tabs.dc[c], cl[2 * c], sizeof tabs.dc[c]);
+        memcpy(tabs.ac[c], cl[2 * c + 1], sizeof tabs.ac[c]);
+    }
+    char *ws = (char *)d_workspace;
+    a.coef = d_coef;
+    a.fstride = coef_frame_stride;
+    a.hdrlen = (uint32_t)hl;
+    a.offs = (uint32_t *)(ws + l.offs);
+    a.ibits = (uint32_t *)(ws + l.ibits);
+    a.nff = (uint32_t *)(ws + l.nff);
+    a.ustart = (unsigned long long *)(ws + l.ustart);
+    a.ostart = (unsigned long long *)(ws + l.ostart);
+    a.ovf = (uint32_t *)(ws + l.ovf);
+    a.ustream = (uint8_t *)(ws + l.ustream);
+    a.uarea = l.uarea;
+    a.out = d_out;
+    a.ostride = out_frame_stride;
+    a.ocap = out_cap;
+    a.len = (unsigned long long *)d_len;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 per_interval(a.ni, (unsigned)nframes), per_frame((unsigned)nframes);
+    hipLaunchKernelGGL(k_jf_len, per_interval, dim3(kT), 0, s, a, tabs);
+    hipLaunchKernelGGL(k_jf_place, per_frame, dim3(kT), 0, s, a);
+    hipLaunchKernelGGL(k_jf_pack, per_interval, dim3(kT), 0, s, a, tabs);
+    hipLaunchKernelGGL(k_jf_frame, per_frame, dim3(kT), 0, s, a, hdr);
+    hipLaunchKernelGGL(k_jf_stuff, per_interval, dim3(kT), 0, s, a);
+    return hipGetLastError() == hipSuccess ? JPGX_OK : JPGX_EHIP;
+}
+
+}  /* extern "C" */

@@ -28,6 +28,7 @@
 
 #include "../../include/jpgx_compat.h"
 #include "../csrc/jx_consts.h"
+#include "../csrc/jpgx_internal.h"
 
 /* ITU-T T.81 Annex K.3, Tables K.3-K.6: code-length counts and symbol values */
 static const uint8_t kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
@@ -186,6 +187,93 @@ static void build_codes(const uint8_t bits[16], const uint8_t *vals, HuffCodes *
     }
 }
 
+void jx_jfif_codes(uint32_t cl[4][256])
+{
+    HuffCodes h;
+    build_codes(kDcLumBits, kDcVals, &h);
+    memcpy(cl[0], h.cl, sizeof h.cl);
+    build_codes(kAcLumBits, kAcLumVals, &h);
+    memcpy(cl[1], h.cl, sizeof h.cl);
+    build_codes(kDcChrBits, kDcVals, &h);
+    memcpy(cl[2], h.cl, sizeof h.cl);
+    build_codes(kAcChrBits, kAcChrVals, &h);
+    memcpy(cl[3], h.cl, sizeof h.cl);
+}
+
+/* SOI, APP0, DQT x 2, SOF, DHT x 4, DRI (ri != 0), SOS: see csrc/jpgx_internal.h */
+size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
+                      uint8_t *out, size_t cap)
+{
+    int qs[2][8][8];
+    if (jpgx_scale_table(0, quality, qs[0]) || jpgx_scale_table(1, quality, qs[1])) return 0;
+    static const int scan[8][8] = JX_SCAN_ORDER_INIT;
+    const int hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;   /* Y sampling */
+    Out o = {out, 0, cap, 0};
+    put_u16(&o, 0xffd8);                                   /* SOI */
+    put_u16(&o, 0xffe0);                                   /* APP0 JFIF 1.01 */
+    put_u16(&o, 16);
+    put_byte(&o, 'J'); put_byte(&o, 'F'); put_byte(&o, 'I'); put_byte(&o, 'F'); put_byte(&o, 0);
+    put_u16(&o, 0x0101);
+    put_byte(&o, 0);
+    put_u16(&o, 1);
+    put_u16(&o, 1);
+    put_byte(&o, 0); put_byte(&o, 0);
+    /* DQT: the divisors applied.  For q <= 23 some exceed 255 (q = 1: 6050); baseline allows
+     * only 8-bit tables, so then both tables are written with 16-bit precision (Pq = 1) and
+     * the frame is extended sequential (SOF1, same Huffman coding), as libjpeg does. */
+    int wide = 0;
+    for (int t = 0; t < 2; t++)
+        for (int i = 0; i < 64; i++)
+            if (qs[t][i / 8][i % 8] > 255) wide = 1;
+    for (int t = 0; t < 2; t++) {
+        int zz[64];
+        for (int v = 0; v < 8; v++)
+            for (int u = 0; u < 8; u++) {
+                const int q = qs[t][u][v];                 /* coefficient (row v, col u) was
+                                                              divided by Qs[u][v] */
+                zz[scan[v][u]] = q < 1 ? 1 : q;
+            }
+        put_u16(&o, 0xffdb);
+        put_u16(&o, (unsigned)(2 + 1 + 64 * (wide ? 2 : 1)));
+        put_byte(&o, (uint8_t)(wide << 4 | t));
+        for (int k = 0; k < 64; k++) {
+            if (wide) put_u16(&o, (unsigned)zz[k]);
+            else put_byte(&o, (uint8_t)zz[k]);
+        }
+    }
+    put_u16(&o, wide ? 0xffc1 : 0xffc0);                   /* SOF1 / SOF0 */
+    put_u16(&o, 8 + 3 * 3);
+    put_byte(&o, 8);
+    put_u16(&o, (unsigned)height);
+    put_u16(&o, (unsigned)width);
+    put_byte(&o, 3);
+    for (int c = 0; c < 3; c++) {
+        put_byte(&o, (uint8_t)(c + 1));
+        put_byte(&o, (uint8_t)(c ? 0x11 : (hs << 4 | vs)));   /* 0x11, 0x21 or 0x22 */
+        put_byte(&o, (uint8_t)(c ? 1 : 0));
+    }
+    put_dht(&o, 0x00, kDcLumBits, kDcVals);
+    put_dht(&o, 0x10, kAcLumBits, kAcLumVals);
+    put_dht(&o, 0x01, kDcChrBits, kDcVals);
+    put_dht(&o, 0x11, kAcChrBits, kAcChrVals);
+    if (ri) {                                              /* DRI (T.81 B.2.4.4) */
+        put_u16(&o, 0xffdd);
+        put_u16(&o, 4);
+        put_u16(&o, ri);
+    }
+    put_u16(&o, 0xffda);                                   /* SOS */
+    put_u16(&o, 6 + 2 * 3);
+    put_byte(&o, 3);
+    for (int c = 0; c < 3; c++) {
+        put_byte(&o, (uint8_t)(c + 1));
+        put_byte(&o, (uint8_t)(c ? 0x11 : 0x00));
+    }
+    put_byte(&o, 0);
+    put_byte(&o, 63);
+    put_byte(&o, 0);
+    return o.n;
+}
+
 /* worst-case coded bytes of one block, stuffing included */
 #define JX_BLOCK_MAX (2 * (22 + 63 * 26 + 11 + 8) / 8 + 16)
 
@@ -331,10 +419,7 @@ int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, 
         return JPGX_EARG;
     const int hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;   /* Y sampling */
     if (width % (8 * hs) || height % (8 * vs)) return JPGX_EGEOMETRY;
-    int qs[2][8][8];
-    if (jpgx_scale_table(0, quality, qs[0]) || jpgx_scale_table(1, quality, qs[1]))
-        return JPGX_EQUALITY;
-    static const int scan[8][8] = JX_SCAN_ORDER_INIT;
+    if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
 
     Scan S;
     S.coef = coef;
@@ -365,75 +450,18 @@ int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, 
     S.rows_per_interval = rr ? rr : S.mrows;
     S.nintervals = (S.mrows + S.rows_per_interval - 1) / S.rows_per_interval;
     if ((size_t)T > S.nintervals) T = (long)S.nintervals;
-    build_codes(kDcLumBits, kDcVals, &S.dc[0]);
-    build_codes(kDcChrBits, kDcVals, &S.dc[1]);
-    build_codes(kAcLumBits, kAcLumVals, &S.ac[0]);
-    build_codes(kAcChrBits, kAcChrVals, &S.ac[1]);
+    uint32_t cl[4][256];
+    jx_jfif_codes(cl);
+    memcpy(S.dc[0].cl, cl[0], sizeof cl[0]);
+    memcpy(S.ac[0].cl, cl[1], sizeof cl[1]);
+    memcpy(S.dc[1].cl, cl[2], sizeof cl[2]);
+    memcpy(S.ac[1].cl, cl[3], sizeof cl[3]);
 
     /* headers */
     Out o = {out, 0, cap, 0};
-    put_u16(&o, 0xffd8);                                   /* SOI */
-    put_u16(&o, 0xffe0);                                   /* APP0 JFIF 1.01 */
-    put_u16(&o, 16);
-    put_byte(&o, 'J'); put_byte(&o, 'F'); put_byte(&o, 'I'); put_byte(&o, 'F'); put_byte(&o, 0);
-    put_u16(&o, 0x0101);
-    put_byte(&o, 0);
-    put_u16(&o, 1);
-    put_u16(&o, 1);
-    put_byte(&o, 0); put_byte(&o, 0);
-    /* DQT: the divisors applied.  For q <= 23 some exceed 255 (q = 1: 6050); baseline allows
-     * only 8-bit tables, so then both tables are written with 16-bit precision (Pq = 1) and
-     * the frame is extended sequential (SOF1, same Huffman coding), as libjpeg does. */
-    int wide = 0;
-    for (int t = 0; t < 2; t++)
-        for (int i = 0; i < 64; i++)
-            if (qs[t][i / 8][i % 8] > 255) wide = 1;
-    for (int t = 0; t < 2; t++) {
-        int zz[64];
-        for (int v = 0; v < 8; v++)
-            for (int u = 0; u < 8; u++) {
-                const int q = qs[t][u][v];                 /* coefficient (row v, col u) was
-                                                              divided by Qs[u][v] */
-                zz[scan[v][u]] = q < 1 ? 1 : q;
-            }
-        put_u16(&o, 0xffdb);
-        put_u16(&o, (unsigned)(2 + 1 + 64 * (wide ? 2 : 1)));
-        put_byte(&o, (uint8_t)(wide << 4 | t));
-        for (int k = 0; k < 64; k++) {
-            if (wide) put_u16(&o, (unsigned)zz[k]);
-            else put_byte(&o, (uint8_t)zz[k]);
-        }
-    }
-    put_u16(&o, wide ? 0xffc1 : 0xffc0);                   /* SOF1 / SOF0 */
-    put_u16(&o, 8 + 3 * 3);
-    put_byte(&o, 8);
-    put_u16(&o, (unsigned)height);
-    put_u16(&o, (unsigned)width);
-    put_byte(&o, 3);
-    for (int c = 0; c < 3; c++) {
-        put_byte(&o, (uint8_t)(c + 1));
-        put_byte(&o, (uint8_t)(c ? 0x11 : (hs << 4 | vs)));   /* 0x11, 0x21 or 0x22 */
-        put_byte(&o, (uint8_t)(c ? 1 : 0));
-    }
-    put_dht(&o, 0x00, kDcLumBits, kDcVals);
-    put_dht(&o, 0x10, kAcLumBits, kAcLumVals);
-    put_dht(&o, 0x01, kDcChrBits, kDcVals);
-    put_dht(&o, 0x11, kAcChrBits, kAcChrVals);
-    if (rr) {                                              /* DRI (T.81 B.2.4.4) */
-        put_u16(&o, 0xffdd);
-        put_u16(&o, 4);
-        put_u16(&o, (unsigned)(rr * S.cpr));
-    }
-    put_u16(&o, 0xffda);                                   /* SOS */
-    put_u16(&o, 6 + 2 * 3);
-    put_byte(&o, 3);
-    for (int c = 0; c < 3; c++) {
-        put_byte(&o, (uint8_t)(c + 1));
-        put_byte(&o, (uint8_t)(c ? 0x11 : 0x00));
-    }
-    put_byte(&o, 0);
-    put_byte(&o, 63);
-    put_byte(&o, 0);
+    o.n = jx_jfif_header(width, height, quality, sample_ratio, (unsigned)(rr * S.cpr), out, cap);
+    if (!o.n) return JPGX_EQUALITY;
+    if (o.n > cap) o.overflow = 1;
 
     /* the scan: thread t codes intervals [t NI / T, (t + 1) NI / T) into its own buffer */
     Job *jobs = (Job *)calloc((size_t)T, sizeof(Job));

@@ -43,6 +43,7 @@ EXPORTS = [
     "jpgx_entropy_stats_gpu", "jpgx_entropy_workspace_size_batch", "jpgx_entropy_stats_gpu_batch",
     "jpgx_host_create", "jpgx_host_destroy", "jpgx_host_blocks",
     "jpgx_host_register", "jpgx_host_unregister", "jpgx_host_release",
+    "jpgx_jfif_gpu_workspace_size", "jpgx_jfif_gpu",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -115,6 +116,9 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_entropy_workspace_size_batch.argtypes = [sz, sz, sz]
     L.jpgx_entropy_workspace_size_batch.restype = sz
     L.jpgx_entropy_stats_gpu_batch.argtypes = [vp, sz, sz, sz, sz, vp, vp, vp, vp, sz, vp]
+    L.jpgx_jfif_gpu_workspace_size.argtypes = [i, i, i, i, sz, sz]
+    L.jpgx_jfif_gpu_workspace_size.restype = sz
+    L.jpgx_jfif_gpu.argtypes = [vp, sz, sz, i, i, i, i, i, vp, sz, sz, vp, vp, sz, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -307,6 +311,68 @@ def entropy_stats_gpu_batch(d_coef, nb_y: int, nb_c: int, stream=None):
                                             dc.data_ptr(), hist.data_ptr(), ws.data_ptr(), ws.numel(),
                                             _stream_ptr(stream)), "jpgx_entropy_stats_gpu_batch")
     return dc, hist
+
+
+def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 0,
+             restart_rows: int = -1, cap: int | None = None, stream=None):
+    """The JFIF files of a frame batch, coded on the device (jpgx_jfif_gpu): d_coef int16
+    [nframes][...] as encode_blocks / blocks_gpu write each frame ([3][nb][64], or Y | Cb | Cr with
+    FLAG_SUBSAMPLE for sample_ratio 1, 2; each frame contiguous, frames d_coef.stride(0) elements
+    apart) -> (out uint8 [nframes][cap], lens int64 [nframes]): frame f's file is
+    out[f, :lens[f]], byte for byte compat.write_jfif_ex(coef, ..., restart_rows, nthreads=1)
+    (restart_rows -1: one MCU row per interval).  cap: bytes per frame (default as
+    compat.write_jfif_ex); when a frame needs more, one retry with the capacity the library
+    reports (that reads lens back, a synchronisation)."""
+    import torch
+    if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda:
+        raise ValueError("jfif_gpu: d_coef must be a device tensor")
+    if d_coef.dtype != torch.int16 or d_coef.dim() < 2:
+        raise ValueError("jfif_gpu: d_coef must be an int16 [nframes][...] tensor")
+    if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
+        raise ValueError("jfif_gpu: bad geometry or sample_ratio")
+    nb = (width // 8) * (height // 8)
+    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, FLAG_SUBSAMPLE if sample_ratio else 0)
+    per_frame = (nb + 2 * nbc) * 64
+    if not d_coef[0].is_contiguous() or d_coef[0].numel() < per_frame:
+        raise ValueError("jfif_gpu: each frame must be contiguous and hold nb + 2 nbc blocks")
+    nf = d_coef.shape[0]
+    fstride = d_coef.stride(0) if nf > 1 else d_coef[0].numel()
+    if d_coef.data_ptr() % 16 or fstride % 64:
+        raise ValueError("jfif_gpu: 16-byte aligned frames, a stride of whole blocks")
+    dev = d_coef.device
+    cap = int(cap) if cap else max(1 << 20, per_frame // 2)
+    for attempt in range(2):
+        out = torch.empty((nf, cap), dtype=torch.uint8, device=dev)
+        lens = torch.empty(nf, dtype=torch.int64, device=dev)
+        need = int(lib.jpgx_jfif_gpu_workspace_size(width, height, sample_ratio, restart_rows, nf, cap))
+        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        _check(lib.jpgx_jfif_gpu(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
+                                 restart_rows, out.data_ptr(), cap, cap, lens.data_ptr(), ws.data_ptr(),
+                                 ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
+        if stream is not None:
+            stream.synchronize()
+        host = lens.cpu()
+        if attempt or not bool((host < 0).any()):
+            break
+        cap = int((host[host < 0] & ((1 << 62) - 1)).max())   # bit 63: the capacity that suffices
+    return out, lens
+
+
+def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restart_rows: int = -1) -> bytes:
+    """One device image (H, W, 3 uint8 torch tensor on a GPU) -> its JFIF file: encode_blocks, then
+    jfif_gpu, then a device-to-host copy of the file's bytes.  With FLAG_SUBSAMPLE and sample_ratio
+    1 / 2 the file is 4:2:2 / 4:2:0, otherwise 4:4:4."""
+    import torch
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+        raise ValueError("encode_jpeg: rgb must be a device tensor")
+    H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    sub = sample_ratio if flags & FLAG_SUBSAMPLE else 0
+    coef = encode_blocks(rgb, quality, sample_ratio, flags=flags if sub else flags & ~FLAG_SUBSAMPLE)
+    out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows)
+    n = int(lens[0])
+    if n < 0:
+        raise JpgxError(EARG, "jpgx_jfif_gpu (capacity)")
+    return out[0, :n].cpu().numpy().tobytes()
 
 
 def split_sub(out, nb: int, nbc: int):

@@ -1,0 +1,159 @@
+"""Time the device JFIF coder (jpgx_jfif_gpu) on the hot path's own output and write
+profiles/jfif_gpu.json: 8 x 4K frames, q90, 4:4:4, one MCU row per restart interval, coefficients
+from the transform kernel, for two inputs -- the flagship's splitmix noise (every coefficient
+nonzero: the coder's worst case) and a photo-like frame (flat 8 x 8 tiles plus +-6 of noise).
+Per input:
+  coder_us        jpgx_jfif_gpu per batch, HIP events around 10 calls, 5 rounds after 0.5 s of
+                  settling (all rounds listed, sorted)
+  bytes           what the algorithm needs (coefficients once + files once) and what this design
+                  moves (coefficients twice, offsets written and read, the unstuffed stream written
+                  and read twice, files once), each over the minimum time
+  host_route_s    the route to the same bytes without the device coder: the coefficients copied to
+                  the host (into pinned memory: the best case) + jpgx_write_jfif_ex, restart_rows 1,
+                  16 threads, frame after frame; best of 2
+  speedup         host_route_s / coder time
+  xform_us, xform_plus_coder_us   the transform alone and transform + coder per batch (events)
+  bytes_equal     every frame's device bytes == the host writer's
+Usage (GPU box): python tools/jfif_gpu_bench.py [OUT.json]"""
+import json
+import os
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "jpeg-encoder-and-decoder_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import jpgx  # noqa: E402
+import jpgx.compat as C  # noqa: E402
+
+W, H, F, Q = 3840, 2160, 8, 90
+HOST_THREADS = 16
+
+
+def timed(fn, calls=10, rounds=5, settle=0.5):
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < settle:
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3 / calls)
+    return sorted(ts)
+
+
+def measure(name, d_rgb, dev):
+    nb = (W // 8) * (H // 8)
+    per = 3 * nb * 64
+    coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+    p = jpgx.default_params(W, H, Q, 0)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+
+    def xform():
+        jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+
+    xform()
+    torch.cuda.synchronize()
+    # the capacity: ask with a small one, take what the library reports
+    _, lens = jpgx.jfif_gpu(coef, W, H, Q, 0, 1, cap=1 << 20)
+    cap = (int(lens.max()) + 4095) // 4096 * 4096
+    out = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+    lens = torch.empty(F, dtype=torch.int64, device=dev)
+    wsb = int(jpgx.lib.jpgx_jfif_gpu_workspace_size(W, H, 0, 1, F, cap))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def coder():
+        rc = jpgx.lib.jpgx_jfif_gpu(coef.data_ptr(), per, F, W, H, Q, 0, 1, out.data_ptr(), cap, cap,
+                                    lens.data_ptr(), ws.data_ptr(), wsb, stream)
+        assert rc == 0, rc
+
+    def both():
+        xform()
+        coder()
+
+    coder()
+    torch.cuda.synchronize()
+    n = lens.cpu().numpy()
+    assert (n > 0).all(), n
+    first = [out[f, :n[f]].cpu().numpy().tobytes() for f in range(F)]
+    t_coder = timed(coder)
+    t_xform = timed(xform)
+    t_both = timed(both)
+    repeat_equal = all(out[f, :n[f]].cpu().numpy().tobytes() == first[f] for f in range(F))
+
+    # the host route
+    pinned = torch.empty((F, per), dtype=torch.int16).pin_memory()
+    host_s, d2h_s, files = [], [], None
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pinned.copy_(coef)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        hc = pinned.numpy()
+        files = [C.write_jfif_ex(hc[f].reshape(-1, 64), W, H, Q, 0, restart_rows=1, nthreads=HOST_THREADS,
+                                 cap=cap) for f in range(F)]
+        t2 = time.perf_counter()
+        d2h_s.append(t1 - t0)
+        host_s.append(t2 - t0)
+    equal = all(files[f] == first[f] for f in range(F))
+
+    file_bytes = int(n.sum())
+    unstuffed = file_bytes                       # within a per cent: stuffing and markers
+    alg = F * per * 2 + file_bytes
+    moved = 2 * F * per * 2 + 2 * 4 * F * 3 * nb + 3 * unstuffed + file_bytes
+    tmin = t_coder[0]
+    return {
+        "input": name, "file_bytes_per_frame": [int(x) for x in n],
+        "coder_us": t_coder, "xform_us": t_xform, "xform_plus_coder_us": t_both,
+        "coder_over_xform": t_coder[2] / t_xform[2],
+        "bytes": {"algorithmic": alg, "moved_by_design": moved,
+                  "algorithmic_GBps": alg / tmin / 1e3, "moved_GBps": moved / tmin / 1e3},
+        "gpx_per_s": F * W * H / tmin / 1e3,
+        "host_route_s": min(host_s), "host_route_d2h_s": min(d2h_s), "host_threads": HOST_THREADS,
+        "speedup": min(host_s) / (t_coder[2] * 1e-6),
+        "bytes_equal": bool(equal), "repeat_equal": bool(repeat_equal),
+    }
+
+
+def main():
+    dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "profiles", "jfif_gpu.json")
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = torch.device("cuda:0")
+    res = {"what": "tools/jfif_gpu_bench.py", "width": W, "height": H, "frames": F, "quality": Q,
+           "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
+           "version": jpgx.version(), "runs": []}
+    d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+    for f in range(F):
+        jpgx.gen_splitmix_gpu(d[f], 1000 + f)
+    res["runs"].append(measure("splitmix noise (the flagship's input)", d, dev))
+    print(json.dumps(res["runs"][-1]), flush=True)
+    g = torch.Generator(device=dev).manual_seed(7)
+    tiles = torch.randint(0, 256, (F, H // 8, W // 8, 3), generator=g, dtype=torch.uint8, device=dev)
+    big = tiles.repeat_interleave(8, 1).repeat_interleave(8, 2).to(torch.int16)
+    big += torch.randint(-6, 7, big.shape, generator=g, dtype=torch.int16, device=dev)
+    d.copy_(big.clamp_(0, 255))
+    del big, tiles
+    res["runs"].append(measure("flat 8x8 tiles + noise of +-6", d, dev))
+    print(json.dumps(res["runs"][-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    with open(dst, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    ok = all(r["bytes_equal"] and r["repeat_equal"] for r in res["runs"])
+    print("bytes equal:", ok)
+    sys.exit(0 if ok else 1)
+
+
+if __name__ == "__main__":
+    main()
