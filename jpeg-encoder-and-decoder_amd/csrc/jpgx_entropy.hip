@@ -31,11 +31,11 @@
  * grid, each frame's recurrence starting from its own carry-in -- one frame per launch leaves the
  * chip mostly idle (49.8 MB of 4K coefficients is ~10 us of HBM time against ~3 launches).
  */
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 
 #include "jpgx_internal.h"
+#include "jx_hip.h"
 
 namespace {
 
@@ -430,8 +430,6 @@ __global__ __launch_bounds__(kChunk) void k_ent_hist(const Chunks c)
     }
 }
 
-int hip_rc2(hipError_t e) { return e == hipSuccess ? JPGX_OK : JPGX_EHIP; }
-
 size_t nchunks_of(size_t nb_y, size_t nb_c)
 {
     return (nb_y + kCB - 1) / kCB + 2 * ((nb_c + kCB - 1) / kCB);
@@ -497,7 +495,7 @@ int jpgx_entropy_stats_gpu_batch(const int16_t *d_coef, size_t coef_frame_stride
             ((uintptr_t)d_dc & 15) == 0;
     hipLaunchKernelGGL(k_ent_dc, dim3(c.ndcg * (unsigned)nframes), dim3(kChunk), 0, s, c);
     hipLaunchKernelGGL(k_ent_hist, dim3(kRows, (unsigned)nframes), dim3(kChunk), 0, s, c);
-    return hip_rc2(hipGetLastError());
+    return jx_hip_rc(hipGetLastError());
 }
 
 int jpgx_entropy_stats_gpu(const int16_t *d_coef, size_t nb_y, size_t nb_c, const int32_t *carry,

@@ -16,7 +16,6 @@
  * the caller's buffers are already page-locked (hipHostMalloc'd or jpgx_host_register'ed) the
  * chunks are copied directly, with no host copy at all.
  */
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -25,11 +24,9 @@
 #include <thread>
 #include <vector>
 
-#include "jpgx.h"
+#include "jx_hip.h"
 
 namespace {
-
-int hip_rc(hipError_t e) { return e == hipSuccess ? JPGX_OK : JPGX_EHIP; }
 
 constexpr size_t kChunkInBytes = 4u << 20;   /* auto chunk: about 4 MB of RGB per chunk */
 
@@ -104,12 +101,12 @@ void shard_free(Shard &s)
 /* streams/events once; buffers grown to the chunk size (device + pinned staging) */
 int shard_reserve(Shard &s, size_t in_bytes, size_t out_bytes, bool staged)
 {
-    int rc = hip_rc(hipSetDevice(s.dev));
+    int rc = jx_hip_rc(hipSetDevice(s.dev));
     if (rc) return rc;
     if (!s.ready) {
         for (int b = 0; b < 2 && !rc; b++) {
-            rc = hip_rc(hipStreamCreateWithFlags(&s.st[b], hipStreamNonBlocking));
-            if (!rc) rc = hip_rc(hipEventCreateWithFlags(&s.ev[b], hipEventDisableTiming));
+            rc = jx_hip_rc(hipStreamCreateWithFlags(&s.st[b], hipStreamNonBlocking));
+            if (!rc) rc = jx_hip_rc(hipEventCreateWithFlags(&s.ev[b], hipEventDisableTiming));
         }
         s.ready = true;                        /* partial creation is freed by shard_free */
         if (rc) return rc;
@@ -199,10 +196,10 @@ int enqueue_chunk(Shard &s, const Image &im, const Chunk &c, int b, size_t dpitc
     const size_t row_bytes = (size_t)im.width * 3;
     const uint8_t *src = im.rgb + ((size_t)c.c0 * 8 - c.halo) * im.pitch;
     int rc = im.direct
-                 ? hip_rc(hipMemcpy2DAsync(s.d_in[b], dpitch, src, im.pitch, row_bytes, c.rows_px,
-                                           hipMemcpyHostToDevice, s.st[b]))
-                 : hip_rc(hipMemcpyAsync(s.d_in[b], s.h_in[b], dpitch * c.rows_px,
-                                         hipMemcpyHostToDevice, s.st[b]));
+                 ? jx_hip_rc(hipMemcpy2DAsync(s.d_in[b], dpitch, src, im.pitch, row_bytes, c.rows_px,
+                                              hipMemcpyHostToDevice, s.st[b]))
+                 : jx_hip_rc(hipMemcpyAsync(s.d_in[b], s.h_in[b], dpitch * c.rows_px,
+                                            hipMemcpyHostToDevice, s.st[b]));
     if (rc) return rc;
     jpgx_frames fr;
     memset(&fr, 0, sizeof fr);
@@ -217,19 +214,19 @@ int enqueue_chunk(Shard &s, const Image &im, const Chunk &c, int b, size_t dpitc
     rc = jpgx_blocks_gpu(&fr, im.p, s.d_in[b] + c.halo * dpitch, s.d_out[b], nullptr, 0, s.st[b]);
     if (rc) return rc;
     if (im.direct) {
-        rc = hip_rc(hipMemcpyAsync(im.out + c.y_dst * 64, s.d_out[b], c.nb * 64 * sizeof(int16_t),
-                                   hipMemcpyDeviceToHost, s.st[b]));
+        rc = jx_hip_rc(hipMemcpyAsync(im.out + c.y_dst * 64, s.d_out[b], c.nb * 64 * sizeof(int16_t),
+                                      hipMemcpyDeviceToHost, s.st[b]));
         for (int ch = 1; ch < 3 && !rc; ch++)
-            rc = hip_rc(hipMemcpyAsync(im.out + (im.nb + (size_t)(ch - 1) * im.nbc + c.c_dst) * 64,
-                                       s.d_out[b] + (c.nb + (size_t)(ch - 1) * c.nbc) * 64,
-                                       c.nbc * 64 * sizeof(int16_t), hipMemcpyDeviceToHost,
-                                       s.st[b]));
+            rc = jx_hip_rc(hipMemcpyAsync(im.out + (im.nb + (size_t)(ch - 1) * im.nbc + c.c_dst) * 64,
+                                          s.d_out[b] + (c.nb + (size_t)(ch - 1) * c.nbc) * 64,
+                                          c.nbc * 64 * sizeof(int16_t), hipMemcpyDeviceToHost,
+                                          s.st[b]));
     } else {
-        rc = hip_rc(hipMemcpyAsync(s.h_out[b], s.d_out[b], (c.nb + 2 * c.nbc) * 64 * sizeof(int16_t),
-                                   hipMemcpyDeviceToHost, s.st[b]));
+        rc = jx_hip_rc(hipMemcpyAsync(s.h_out[b], s.d_out[b], (c.nb + 2 * c.nbc) * 64 * sizeof(int16_t),
+                                      hipMemcpyDeviceToHost, s.st[b]));
     }
     if (rc) return rc;
-    return hip_rc(hipEventRecord(s.ev[b], s.st[b]));
+    return jx_hip_rc(hipEventRecord(s.ev[b], s.st[b]));
 }
 
 /* shard k's block rows [r0, r1), chunk by chunk, two slots in flight */
@@ -251,7 +248,7 @@ int run_shard(Shard &s, const Image &im, int r0, int r1, int chunk_rows, int uni
     for (size_t i = 0; i < n + 2 && !rc; i++) {
         const int b = (int)(i & 1);
         if (i >= 2) {                          /* chunk i-2 done: its slot is free */
-            rc = hip_rc(hipEventSynchronize(s.ev[b]));
+            rc = jx_hip_rc(hipEventSynchronize(s.ev[b]));
             if (rc) break;
             if (!im.direct) scatter_out(im, chunks[i - 2], s.h_out[b]);
         }
@@ -378,13 +375,13 @@ int jpgx_host_register(void *ptr, size_t bytes)
 {
     if (!ptr || !bytes) return JPGX_EARG;
     if (jpgx_device_count() < 1) return JPGX_ENODEV;
-    return hip_rc(hipHostRegister(ptr, bytes, hipHostRegisterPortable));
+    return jx_hip_rc(hipHostRegister(ptr, bytes, hipHostRegisterPortable));
 }
 
 int jpgx_host_unregister(void *ptr)
 {
     if (!ptr) return JPGX_EARG;
-    return hip_rc(hipHostUnregister(ptr));
+    return jx_hip_rc(hipHostUnregister(ptr));
 }
 
 void jpgx_host_release(void)

@@ -1,7 +1,8 @@
 /*
- * jpgx_internal.h -- launch-argument layouts shared by the host plan (jpgx_plan.cpp) and
- * the gfx950 kernels (jpgx_kernels.hip).  Passed by value as kernel arguments so the
- * per-coefficient tables are read with scalar loads (wave-uniform).
+ * jpgx_internal.h -- what the library's translation units share: the launch arguments the device
+ * C ABI (jpgx_device.hip) passes by value to the kernels of either implementation (jpgx_mx.hip;
+ * jpgx_kernels.hip in the test-only library), the table layouts the host plan (jpgx_plan.cpp)
+ * fills, and the internal entry points.  No HIP types: jpgx_plan.cpp is built without them (jx_hip.h).
  */
 #ifndef JPGX_INTERNAL_H
 #define JPGX_INTERNAL_H
@@ -85,12 +86,13 @@ struct jx_mxtab {
     double r[2][64];        /* fl(fl(1/4 a(u) a(v)) / q[t][u*8+v]): the exact pass's fast decision */
 };
 
+/* built by blocks_gpu (jpgx_device.hip) for either launcher; every kernel's by-value argument */
 struct jx_xform_args {
     struct jx_geom g;
     int quality;            /* index into the device table                                */
     int force_exact;        /* JPGX_FLAG_FORCE_EXACT: flag every coefficient              */
-    int luma_only;          /* k_xform: channel 0 only (chroma from k_chroma)             */
-    int sub;                /* k_chroma: 1 = true 4:2:2, 2 = true 4:2:0                   */
+    int luma_only;          /* true 4:2:x; read by k_xform only: Y only, chroma from k_chroma */
+    int sub;                /* set by jx_launch_alt for k_chroma: 1 = true 4:2:2, 2 = 4:2:0   */
 };
 
 
@@ -125,6 +127,9 @@ long long jx_selftest_mx420(long long nblocks, unsigned long long seed, int qual
  * 2: k_mxs420); the workgroup image it would upload for (force, quality), host only */
 int jx_launch_mx(const struct jx_xform_args *xa, int sr, void *stream, void *ev_start, void *ev_stop);
 long long jx_mx_image(int sr, int force, int quality, void *dst, long long cap);
+/* the second implementation's launcher (jpgx_kernels.hip, libjpgx_alt.so only): k_xform, and for
+ * sr 1 / 2 k_chroma<sr> over the nbc chroma blocks of each frame */
+int jx_launch_alt(const struct jx_xform_args *xa, int sr, size_t nbc, void *stream, void *ev_start, void *ev_stop);
 /* the JFIF writer's tables and header bytes (host/jpgx_jfif.c), shared by jpgx_write_jfif_ex and
  * the device coder (csrc/jpgx_jfif.hip).
  * jx_jfif_codes: the canonical Huffman codes of the Annex K.3 tables (T.81 Annex C) indexed by

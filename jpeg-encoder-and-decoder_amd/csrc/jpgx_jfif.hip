@@ -23,11 +23,11 @@
  * (jx_jfif_codes, jx_jfif_header) as by-value kernel arguments: nothing is copied with a memcpy,
  * the call is asynchronous, capturable and keeps no state.
  */
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 
 #include "jpgx_internal.h"
+#include "jx_hip.h"
 
 namespace {
 
@@ -550,7 +550,7 @@ int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframe
     hipLaunchKernelGGL(k_jf_pack, per_interval, dim3(kT), 0, s, a, tabs);
     hipLaunchKernelGGL(k_jf_frame, per_frame, dim3(kT), 0, s, a, hdr);
     hipLaunchKernelGGL(k_jf_stuff, per_interval, dim3(kT), 0, s, a);
-    return hipGetLastError() == hipSuccess ? JPGX_OK : JPGX_EHIP;
+    return jx_hip_rc(hipGetLastError());
 }
 
 }  /* extern "C" */

@@ -1,5 +1,8 @@
 /*
- * jpgx_kernels.hip -- gfx950 kernels of the block-transform hot path + the device C-ABI.
+ * jpgx_kernels.hip -- the second, all-VALU implementation of the block transform: k_xform,
+ * k_chroma<1|2>, their per-quality tables and their launcher jx_launch_alt.  TEST-ONLY: linked
+ * into the cross-check library (libjpgx_alt.so) alone, where csrc/jpgx_device.hip calls
+ * jx_launch_alt in place of the product's jx_launch_mx; the parity tests run both.
  *
  * k_xform (all-VALU; one lane = one 8x8 block, all 3 channels)
  *   HBM -> VGPR: each lane loads its block's 8 pixel rows (8 x 24 B; a wave covers 64
@@ -18,26 +21,24 @@
  *   colour conversion in its operand order, -128, the 64-term sum x-outer / y-inner with
  *   (X*c_u[x])*c_v[y] and the glibc cosine doubles, ((0.25*a_u)*a_v)*s, true double division
  *   by the transposed table entry, round() half away from zero.
- * k_chroma<1|2>: true 4:2:2 / 4:2:0 chroma of the test-only cross-check library; k_xform does Y.
- * k_mx / k_mx422 / k_mx420 (csrc/jpgx_mx.hip): the product kernels (4:4:4, true 4:2:2 / 4:2:0)
+ * k_chroma<1|2>: true 4:2:2 / 4:2:0 chroma; k_xform does Y.
+ * k_mxs / k_mxs422 / k_mxs420 (csrc/jpgx_mx.hip): the product kernels (4:4:4, true 4:2:2 / 4:2:0)
  *   with the colour conversion and row DCT on the matrix cores.
  *
  * Compiled with FP contraction off; the fast path uses explicit fmaf.  Variants of k_xform
  * measured slower are kept out of this file: tools/probes/k_xform_variants.patch (git history: 63924df).
  */
-#include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "jpgx_internal.h"
 #include "jx_consts.h"
+#include "jx_hip.h"
 #include "xform_math.h"
 
 #pragma clang fp contract(off)
@@ -691,59 +692,13 @@ __global__ __launch_bounds__(JX_WG, 3) void k_chroma(const jx_xform_args a)
     }
 }
 
-__device__ __forceinline__ uint8_t splitmix_byte(uint64_t seed, uint64_t k)
-{
-    uint64_t z = seed + (k + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (uint8_t)(z >> 56);
-}
-
-__global__ void k_gen_splitmix(uint8_t *dst, size_t n, uint64_t seed)
-{
-    const size_t stride = (size_t)gridDim.x * blockDim.x * 16;
-    for (size_t k0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 16; k0 < n; k0 += stride) {
-        if (k0 + 16 <= n && (((uintptr_t)(dst + k0)) & 15) == 0) {
-            uint32_t w[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                w[j] = 0;
-#pragma unroll
-                for (int i = 0; i < 4; i++)
-                    w[j] |= (uint32_t)splitmix_byte(seed, k0 + 4 * j + i) << (8 * i);
-            }
-            *(u32x4 *)(dst + k0) = u32x4{w[0], w[1], w[2], w[3]};
-        } else {
-            for (size_t k = k0; k < k0 + 16 && k < n; k++) dst[k] = splitmix_byte(seed, k);
-        }
-    }
-}
-
-__global__ void k_gen_tie(uint8_t *dst, int W, int H)
-{
-    const size_t npx = (size_t)W * H;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += stride) {
-        const size_t y = i / W, x = i - y * W;
-        const size_t bi = (y / 8) * (W / 8) + x / 8;
-        const uint8_t v = (uint8_t)(97 + 2 * (bi % 40));
-        dst[3 * i] = v;
-        dst[3 * i + 1] = v;
-        dst[3 * i + 2] = v;
-    }
-}
-
-int hip_rc(hipError_t e) { return e == hipSuccess ? JPGX_OK : JPGX_EHIP; }
-
-constexpr int kMaxDev = 64;
-std::once_flag g_tab_once[kMaxDev];
-int g_tab_rc[kMaxDev];
+std::once_flag g_tab_once[JX_MAX_DEV];
+int g_tab_rc[JX_MAX_DEV];
 
 int tables_for_current_device()
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return JPGX_ENODEV;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= JX_MAX_DEV) return JPGX_ENODEV;
     std::call_once(g_tab_once[dev], [dev]() {
         std::vector<jx_qtab> host(JX_MAXQ + 1);
         std::vector<jx_limtab> band(2 * (JX_MAXQ + 1));
@@ -780,26 +735,26 @@ int tables_for_current_device()
                             bf.lim[ch][u][v] = -1.0f;
                         }
             }
-        g_tab_rc[dev] = hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_qtab), host.data(),
-                                                 host.size() * sizeof(jx_qtab)));
+        g_tab_rc[dev] = jx_hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_qtab), host.data(),
+                                                    host.size() * sizeof(jx_qtab)));
         if (!g_tab_rc[dev])
-            g_tab_rc[dev] = hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_limsub), bsub.data(),
-                                                     bsub.size() * sizeof(jx_limtab)));
+            g_tab_rc[dev] = jx_hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_limsub), bsub.data(),
+                                                        bsub.size() * sizeof(jx_limtab)));
         if (!g_tab_rc[dev])
-            g_tab_rc[dev] = hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_lim), band.data(),
-                                                     band.size() * sizeof(jx_limtab)));
+            g_tab_rc[dev] = jx_hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(g_lim), band.data(),
+                                                        band.size() * sizeof(jx_limtab)));
     });
     return g_tab_rc[dev];
 }
 
 /* resident waves of k_xform on the current device (persistent grid size) */
-int g_resident_waves[kMaxDev];
-std::once_flag g_res_once[kMaxDev];
+int g_resident_waves[JX_MAX_DEV];
+std::once_flag g_res_once[JX_MAX_DEV];
 
 int resident_waves()
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= JX_MAX_DEV) return 0;
     std::call_once(g_res_once[dev], [dev]() {
         int cus = 0, per_cu = 0;
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -812,174 +767,48 @@ int resident_waves()
     return g_resident_waves[dev];
 }
 
-/* Dispatch.  The product library (libjpgx.so) runs one kernel per mode (jx_launch_mx): k_mxs for
- * 4:4:4, k_mxs422 / k_mxs420 for true 4:2:2 / 4:2:0.  The test-only cross-check library
- * (libjpgx_alt.so, built from the same sources with -DJPGX_ALT_DISPATCH) runs the second
- * implementations instead: k_xform for 4:4:4 and k_xform (Y) + k_chroma<1|2> for true 4:2:x. */
-#ifndef JPGX_ALT_DISPATCH
-#define JPGX_ALT_DISPATCH 0
-#endif
-constexpr bool kAltDispatch = JPGX_ALT_DISPATCH != 0;
-constexpr size_t kMaxPitch = (size_t)1 << 27;     /* 16 rows x pitch + 256 < 2^32 */
+/* persistent grid: one wave per resident slot, at most one per tile of 64 blocks */
+unsigned grid_for(size_t blocks)
+{
+    const size_t ntiles = (blocks + 63) / 64;
+    const size_t waves = std::min<size_t>(ntiles, (size_t)std::max(resident_waves(), 4));
+    return (unsigned)((waves + JX_WG / 64 - 1) / (JX_WG / 64));
+}
 
 }  // namespace
 
-static int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb, int16_t *d_out,
-                      void *d_workspace, size_t workspace_bytes, void *stream, void *event_after, void *ev_start,
-                      void *ev_stop);
-
-extern "C" {
-
-int jpgx_blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb,
-                    int16_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
+/* k_xform over every block of the stripe (Y only when sr != 0: xa->luma_only), then for sr 1 / 2
+ * k_chroma<sr> over each frame's nbc chroma blocks; ev_start / ev_stop (hipEvent_t or null) around them */
+extern "C" int jx_launch_alt(const jx_xform_args *xa, int sr, size_t nbc, void *stream, void *ev_start, void *ev_stop)
 {
-    return jpgx_blocks_gpu_ev(fr, p, d_rgb, d_out, d_workspace, workspace_bytes, stream, nullptr);
-}
-
-int jpgx_blocks_gpu_ev(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb,
-                       int16_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream,
-                       void *event_after)
-{
-    return blocks_gpu(fr, p, d_rgb, d_out, d_workspace, workspace_bytes, stream, event_after, nullptr, nullptr);
-}
-
-int jpgx_blocks_gpu_timed(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb,
-                          int16_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream,
-                          void *ev_start, void *ev_stop)
-{
-    if (!ev_start || !ev_stop) return JPGX_EARG;
-    return blocks_gpu(fr, p, d_rgb, d_out, d_workspace, workspace_bytes, stream, nullptr, ev_start, ev_stop);
-}
-
-}  /* extern "C" */
-
-static int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb, int16_t *d_out,
-                      void *d_workspace, size_t workspace_bytes, void *stream, void *event_after, void *ev_start,
-                      void *ev_stop)
-{
-    if (!fr || !p) return JPGX_EARG;
-    int rc = jpgx_validate(fr->width, fr->height, p);
+    int rc = tables_for_current_device();
     if (rc) return rc;
-    if (fr->row_begin < 0 || fr->row_end > fr->height / 8 || fr->row_begin > fr->row_end ||
-        fr->nframes < 1)
-        return JPGX_EARG;
-    const bool sub = (p->flags & JPGX_FLAG_SUBSAMPLE) != 0;
-    if (sub && p->sample_ratio == 0) return JPGX_ESAMPLE;
-    if (sub && p->sample_ratio == 2 && ((fr->row_begin | fr->row_end) & 1)) return JPGX_EARG;
-    if (fr->row_begin == fr->row_end) return JPGX_OK;
-    if (!d_rgb || !d_out) return JPGX_EARG;
-    if (fr->in_pitch < (size_t)fr->width * 3 || fr->in_pitch % 8 || fr->in_frame_stride % 8 ||
-        ((uintptr_t)d_rgb & 7) || ((uintptr_t)d_out & 15) || fr->out_frame_stride % 8)
-        return JPGX_EARG;
-    /* the MFMA kernels address a step's pixel rows (up to 16 of them) with 32-bit lane offsets */
-    if (fr->in_pitch > kMaxPitch) return JPGX_EARG;
-    const int bpr = fr->width / 8;
-    const size_t nb = (size_t)(fr->row_end - fr->row_begin) * bpr;
-    const size_t total = nb * fr->nframes;
-    if (total + 64 >= (1ull << 32)) return JPGX_EARG;
-    const size_t nbc = sub ? jpgx_chroma_blocks(fr->width, fr->row_begin, fr->row_end,
-                                                p->sample_ratio, p->flags)
-                           : nb;
-    if (fr->nframes > 1 && fr->out_frame_stride < (nb + 2 * nbc) * 64) return JPGX_EARG;
-    if (fr->nframes > 1 && fr->in_frame_stride < fr->in_pitch * (size_t)(fr->row_end - fr->row_begin) * 8)
-        return JPGX_EARG;
-    if (workspace_bytes < jpgx_workspace_size(fr) || ((uintptr_t)d_workspace & 15))
-        return JPGX_EWORKSPACE;
-
-    jx_xform_args xa;
-    memset(&xa, 0, sizeof xa);
-    jx_geom &g = xa.g;
-    g.rgb = d_rgb;
-    g.out = d_out;
-    g.in_pitch = (long long)fr->in_pitch;
-    g.in_fstride = (long long)fr->in_frame_stride;
-    g.out_fstride = (long long)fr->out_frame_stride;
-    g.bpr = bpr;
-    g.nb = (int)nb;
-    g.nframes = fr->nframes;
-    g.row0 = fr->row_begin;
-    g.dnb = jx_udiv_make((uint32_t)nb);
-    g.dbpr = jx_udiv_make((uint32_t)bpr);
-    g.mpr = (uint32_t)bpr / 2u;
-    g.nmcu = (uint32_t)(nb / (size_t)bpr / 2u) * g.mpr;
-    g.dmpr = jx_udiv_make(g.mpr ? g.mpr : 1u);
-    g.dnmcu = jx_udiv_make(g.nmcu ? g.nmcu : 1u);
-    jx_under_dwords(p->underflow, g.under);
-    rc = tables_for_current_device();
-    if (rc) return rc;
-    xa.quality = p->quality;
-    xa.force_exact = (p->flags & JPGX_FLAG_FORCE_EXACT) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
-    xa.luma_only = sub ? 1 : 0;
-    if (!kAltDispatch) {
-        /* one pass on the matrix cores, exact pass inside (csrc/jpgx_mx.hip): k_mxs, or k_mxs422 /
-         * k_mxs420 for true 4:2:2 / 4:2:0 */
-        rc = jx_launch_mx(&xa, sub ? p->sample_ratio : 0, stream, ev_start, ev_stop);
-        if (!rc && event_after) rc = hip_rc(hipEventRecord((hipEvent_t)event_after, s));
-        return rc;
-    }
-    /* k_xform: persistent, one wave per resident slot (at most one per tile) */
-    const size_t ntiles = (total + 63) / 64;
-    const size_t waves = std::min<size_t>(ntiles, (size_t)std::max(resident_waves(), 4));
-    const unsigned grid = (unsigned)((waves + JX_WG / 64 - 1) / (JX_WG / 64));
-    if (ev_start) {                                   /* the test library: events around its kernels */
-        rc = hip_rc(hipEventRecord((hipEvent_t)ev_start, s));
+    const size_t nb = (size_t)xa->g.nb, nframes = (size_t)xa->g.nframes;
+    const unsigned grid = grid_for(nb * nframes);
+    if (ev_start) {
+        rc = jx_hip_rc(hipEventRecord((hipEvent_t)ev_start, s));
         if (rc) return rc;
     }
-    hipLaunchKernelGGL(k_xform, dim3(grid), dim3(JX_WG), 0, s, xa);
-    rc = hip_rc(hipGetLastError());
+    hipLaunchKernelGGL(k_xform, dim3(grid), dim3(JX_WG), 0, s, *xa);
+    rc = jx_hip_rc(hipGetLastError());
     if (rc) return rc;
-    if (sub) {
+    if (sr) {
         /* true 4:2:2 / 4:2:0 chroma: Cb at out + nb*64, Cr at out + (nb + nbc)*64 per frame */
-        jx_xform_args xc = xa;
+        jx_xform_args xc = *xa;
         xc.luma_only = 0;
-        xc.sub = p->sample_ratio;
-        xc.g.bpr = fr->width / 16;
+        xc.sub = sr;
+        xc.g.bpr = xa->g.bpr / 2;
         xc.g.nb = (int)nbc;
-        xc.g.out = d_out + (long long)nb * 64 - (long long)nbc * 64;
-        const size_t ctiles = (nbc * fr->nframes + 63) / 64;
-        const size_t cw = std::min<size_t>(ctiles, (size_t)std::max(resident_waves(), 4));
-        const unsigned cgrid = (unsigned)((cw + JX_WG / 64 - 1) / (JX_WG / 64));
-        if (p->sample_ratio == 1)
+        xc.g.out = xa->g.out + (long long)nb * 64 - (long long)nbc * 64;
+        const unsigned cgrid = grid_for(nbc * nframes);
+        if (sr == 1)
             hipLaunchKernelGGL(k_chroma<1>, dim3(cgrid), dim3(JX_WG), 0, s, xc);
         else
             hipLaunchKernelGGL(k_chroma<2>, dim3(cgrid), dim3(JX_WG), 0, s, xc);
-        rc = hip_rc(hipGetLastError());
+        rc = jx_hip_rc(hipGetLastError());
         if (rc) return rc;
     }
-    if (ev_stop) rc = hip_rc(hipEventRecord((hipEvent_t)ev_stop, s));
-    if (!rc && event_after) rc = hip_rc(hipEventRecord((hipEvent_t)event_after, s));
+    if (ev_stop) rc = jx_hip_rc(hipEventRecord((hipEvent_t)ev_stop, s));
     return rc;
 }
-
-extern "C" {
-
-int jpgx_gen_splitmix_gpu(uint8_t *d_dst, size_t nbytes, uint64_t seed, void *stream)
-{
-    if (!d_dst) return JPGX_EARG;
-    if (!nbytes) return JPGX_OK;
-    const size_t threads = (nbytes + 15) / 16;
-    const unsigned grid = (unsigned)std::min<size_t>((threads + 255) / 256, 65536);
-    hipLaunchKernelGGL(k_gen_splitmix, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_dst,
-                       nbytes, seed);
-    return hip_rc(hipGetLastError());
-}
-
-int jpgx_gen_tie_gpu(uint8_t *d_dst, int width, int height, void *stream)
-{
-    if (!d_dst || width <= 0 || height <= 0 || width % 8 || height % 8) return JPGX_EARG;
-    const size_t npx = (size_t)width * height;
-    const unsigned grid = (unsigned)std::min<size_t>((npx + 255) / 256, 65536);
-    hipLaunchKernelGGL(k_gen_tie, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_dst, width,
-                       height);
-    return hip_rc(hipGetLastError());
-}
-
-int jpgx_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-}  /* extern "C" */

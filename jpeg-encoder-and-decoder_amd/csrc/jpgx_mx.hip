@@ -58,6 +58,7 @@
 
 #include "jpgx_internal.h"
 #include "jx_consts.h"
+#include "jx_hip.h"
 #include "xform_math.h"
 
 #pragma clang fp contract(off)
@@ -2055,10 +2056,6 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
     step(std::integral_constant<unsigned, 3>{});
 }
 
-int mx_rc(hipError_t e) { return e == hipSuccess ? JPGX_OK : JPGX_EHIP; }
-
-constexpr int kMaxDev = 64;
-
 /* a float <= lim^2 (-1 where lim < 0: every coefficient flagged) */
 float mx_lsq(float lim)
 {
@@ -2269,16 +2266,16 @@ int mx_build_images(std::vector<typename K::Img> &img, std::vector<uint16_t> &op
 template <class K>
 int mx_tables_for_current_device()
 {
-    static std::once_flag once[kMaxDev];
-    static int rcs[kMaxDev];
+    static std::once_flag once[JX_MAX_DEV];
+    static int rcs[JX_MAX_DEV];
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) return JPGX_ENODEV;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= JX_MAX_DEV) return JPGX_ENODEV;
     std::call_once(once[dev], [dev]() {
         std::vector<typename K::Img> img;
         std::vector<uint16_t> ops;
         int rc = mx_build_images<K>(img, ops, 1, JX_MAXQ);
-        if (!rc) rc = mx_rc(hipMemcpyToSymbol(HIP_SYMBOL(K::symbol()), img.data(), img.size() * sizeof(img[0])));
-        if (!rc) rc = mx_rc(K::upload_operands((const mx_tile *)ops.data()));
+        if (!rc) rc = jx_hip_rc(hipMemcpyToSymbol(HIP_SYMBOL(K::symbol()), img.data(), img.size() * sizeof(img[0])));
+        if (!rc) rc = jx_hip_rc(K::upload_operands((const mx_tile *)ops.data()));
         rcs[dev] = rc;
     });
     return rcs[dev];
@@ -2309,7 +2306,7 @@ extern "C" int jx_launch_mx(const jx_xform_args *xa, int sr, void *stream, void 
         const size_t waves = (units + K::per_wave - 1) / K::per_wave;
         mx_launch_k(K::kernel(), dim3((unsigned)((waves + K::wpg - 1) / K::wpg)), dim3(64 * K::wpg), (hipStream_t)stream,
                     ev_start, ev_stop, *xa);
-        return mx_rc(hipGetLastError());
+        return jx_hip_rc(hipGetLastError());
     });
 }
 

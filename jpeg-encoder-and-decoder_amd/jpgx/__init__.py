@@ -136,9 +136,11 @@ _alt = None
 
 
 def alt_library() -> ctypes.CDLL:
-    """The TEST-ONLY cross-check build (lib/libjpgx_alt.so: k_xform for 4:4:4, k_xform +
-    k_chroma for true 4:2:x), loaded on first use.  Tests swap it in for `lib` to run every
-    parity check on the second implementation; the product never loads it."""
+    """The TEST-ONLY cross-check library (lib/libjpgx_alt.so), loaded on first use: the same C
+    ABI, with csrc/jpgx_device.hip calling the second implementation (csrc/jpgx_kernels.hip,
+    linked into this library only: k_xform for 4:4:4, k_xform + k_chroma for true 4:2:x) where
+    the product calls the MFMA kernels.  Tests swap it in for `lib` to run every parity check on
+    the second implementation; the product never loads it."""
     global _alt
     if _alt is None:
         _alt = _load(ALT_LIB_PATH)

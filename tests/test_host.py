@@ -26,6 +26,48 @@ def test_exports_every_declared_symbol():
         assert hasattr(jpgx.lib, name), name
 
 
+def test_both_libraries_export_the_whole_abi():
+    for lib in (jpgx.lib, jpgx.alt_library()):
+        for name in jpgx.EXPORTS + jpgx.COMPAT_EXPORTS:
+            assert hasattr(lib, name), (lib._name, name)
+
+
+def test_second_implementation_is_in_the_test_library_only():
+    """The all-VALU kernels and their tables (csrc/jpgx_kernels.hip) are linked into
+    lib/libjpgx_alt.so alone; the device C ABI (csrc/jpgx_device.hip) and the MFMA kernels are in
+    both libraries."""
+    prod, alt = (open(os.path.join(PKG, "lib", n), "rb").read() for n in ("libjpgx.so", "libjpgx_alt.so"))
+    for s in (b"k_xform", b"k_chroma", b"g_qtab", b"g_limsub"):
+        assert s not in prod, s
+    for s in (b"k_xform", b"k_chroma"):
+        assert s in alt, s
+    for s in (b"k_mxs", b"k_gen_splitmix"):
+        assert s in prod and s in alt, s
+
+
+def test_variant_script_builds_a_loadable_library():
+    """tools/build_variants.sh drives the package Makefile (its own build directory, extra flags):
+    the variant it writes has every export and loads like the product (one full compile)."""
+    import shutil
+    import subprocess
+    name = "export_probe"
+    out = os.path.join(PKG, "lib", "variants", "libjpgx_%s.so" % name)
+    bld = os.path.join(PKG, "build", "variants")
+    try:
+        subprocess.run([os.path.join(REPO, "tools", "build_variants.sh"), name, "-DJPGX_VARIANT_PROBE=1"],
+                       check=True, capture_output=True, env=dict(os.environ, MAKEFLAGS="-j8"))
+        lib = jpgx._load(out)
+        for sym in jpgx.EXPORTS + jpgx.COMPAT_EXPORTS:
+            assert hasattr(lib, sym), sym
+        for s in (name + ".s", name + "_k.s"):
+            assert os.path.getsize(os.path.join(bld, s)) > 0, s
+    finally:
+        shutil.rmtree(os.path.join(bld, name), ignore_errors=True)
+        for f in (out, os.path.join(bld, name + ".s"), os.path.join(bld, name + "_k.s")):
+            if os.path.exists(f):
+                os.remove(f)
+
+
 def test_version_and_devices():
     assert "gfx950" in jpgx.version()
     assert jpgx.device_count() >= 0
