@@ -166,11 +166,13 @@ def _gap_rule_hist(coef):
     return h
 
 
-@pytest.mark.parametrize("kind", ["dense", "sparse", "long_runs", "extremes"])
-def test_device_gap_rule_matches_oracle(kind):
-    """The histogram rule the GPU kernel uses, against the oracle's sequential huffman.c loop."""
+KINDS = ["dense", "sparse", "long_runs", "extremes"]
+
+
+def _synthetic(kind, nb=3000):
+    """int16 [3][nb][64] coefficients no transform produces: the data of
+    test_device_gap_rule_matches_oracle and of the GPU tests on the same kinds."""
     rng = np.random.default_rng({"dense": 1, "sparse": 2, "long_runs": 3, "extremes": 4}[kind])
-    nb = 3000
     if kind == "dense":
         c = rng.integers(-300, 301, (3, nb, 64))
     elif kind == "sparse":
@@ -182,7 +184,13 @@ def test_device_gap_rule_matches_oracle(kind):
                 c[0, b, i] = c[1, b, (i * 7) % 64] = c[2, b, 63 - i] = rng.integers(1, 9) * rng.choice([-1, 1])
     else:                                         # int16 extremes: classes up to 16
         c = rng.choice(np.array([0, 1, -1, 32767, -32768, 2048, -2047]), (3, nb, 64))
-    c = c.astype(np.int16)
+    return c.astype(np.int16)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_device_gap_rule_matches_oracle(kind):
+    """The histogram rule the GPU kernel uses, against the oracle's sequential huffman.c loop."""
+    c = _synthetic(kind)
     _, hist = O.entropy_stats(c)
     for ch, row in ((0, 1), (1, 3)):
         blocks = c[0] if ch == 0 else c[1:].reshape(-1, 64)
@@ -277,3 +285,81 @@ def test_batch_entry_point_rejects_too_many_frames():
     p16 = ctypes.addressof(ws) + (-ctypes.addressof(ws)) % 16
     assert L.jpgx_entropy_stats_gpu_batch(p16, 3 * 64, 65536, nb, nb, None, p16, p16, p16, need,
                                           None) == jpgx.EARG
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", KINDS)
+def test_gpu_stats_synthetic_kinds(cuda, kind):
+    """k_ent_ac and the DC kernels on data the transform never gives them (AC classes up to 16,
+    runs of 16 and more zeros, all-zero blocks, DC differences of int16 extremes), at 3,000 blocks per
+    channel, at one block per channel and at nb_y = 257, nb_c = 65."""
+    for nb_y, nb_c in ((3000, 3000), (1, 1), (257, 65)):
+        assert (nb_y + 2 * nb_c) % 3 == 0
+        coef = _synthetic(kind, (nb_y + 2 * nb_c) // 3).reshape(-1, 64)
+        dc, hist = _gpu_stats(coef, nb_y, nb_c, cuda)
+        rdc, rhist = O.entropy_stats(coef, nb_y, nb_c)
+        assert np.array_equal(dc, rdc), (kind, nb_y, nb_c)
+        assert np.array_equal(hist, rhist), (kind, nb_y, nb_c, np.argwhere(hist != rhist)[:8].tolist())
+
+
+@pytest.mark.gpu
+def test_gpu_stats_batch_synthetic_kinds(cuda):
+    """The batch call on three frames of one kind each (two batches, so all four kinds), frames a
+    padded stride apart."""
+    import torch
+    nb = 1000
+    for first in (0, 1):
+        frames = [_synthetic(k, nb).reshape(-1, 64) for k in KINDS[first:first + 3]]
+        pad = torch.full((3, 3 * nb + 7, 64), 0x0101, dtype=torch.int16, device=cuda)
+        for f in range(3):
+            pad[f, :3 * nb] = torch.from_numpy(frames[f]).to(cuda)
+        dcb, hb = jpgx.entropy_stats_gpu_batch(pad[:, :3 * nb], nb, nb)
+        for f in range(3):
+            rdc, rh = O.entropy_stats(frames[f], nb, nb)
+            assert np.array_equal(dcb[f].cpu().numpy(), rdc), KINDS[first + f]
+            assert np.array_equal(hb[f].cpu().numpy(), rh), KINDS[first + f]
+
+
+LARGE_DC = (65000, 16250)
+
+
+def _large_dc():
+    """Y DCs alternating +32767 / -32768 over 65,000 blocks, chroma the same over 16,250 per
+    channel, every AC zero.  The reference differences in place (dpcm.c:10-20: d[i] = c[i] -
+    d[i-1], the previous DIFFERENCE), so |d| grows by about 32767.5 per block, to about 2.13e9 in
+    Y: DC class 31, still inside int32.  Class 32 (INT_MIN) would take signed overflow in the
+    oracle's C arithmetic, which is undefined: left out."""
+    nb_y, nb_c = LARGE_DC
+    coef = np.zeros((nb_y + 2 * nb_c, 64), np.int16)
+    for off, n in ((0, nb_y), (nb_y, nb_c), (nb_y + nb_c, nb_c)):
+        coef[off:off + n:2, 0] = 32767
+        coef[off + 1:off + n:2, 0] = -32768
+    return coef
+
+
+def test_large_dc_case_stays_in_int32():
+    """The recurrence in int64 numpy: it reaches class 31 without leaving int32, and the oracle's
+    int arithmetic gives the same."""
+    nb_y, nb_c = LARGE_DC
+    coef = _large_dc()
+    want = np.empty(nb_y + 2 * nb_c, np.int64)
+    for off, n in ((0, nb_y), (nb_y, nb_c), (nb_y + nb_c, nb_c)):
+        c = coef[off:off + n, 0].astype(np.int64)
+        sign = np.where(np.arange(n) % 2, -1, 1)
+        want[off:off + n] = sign * np.cumsum(sign * c)          # d[i] = c[i] - d[i-1], d[0] = c[0]
+        assert want[off + 1] == c[1] - c[0] and want[off + 2] == c[2] - want[off + 1]
+    assert np.abs(want).max() < 2 ** 31 and np.abs(want[:nb_y]).max() >= 2 ** 30    # class 31
+    assert 2.12e9 < np.abs(want[:nb_y]).max() < 2.14e9
+    dc, hist = O.entropy_stats(coef, nb_y, nb_c)
+    assert np.array_equal(dc.astype(np.int64), want)
+    assert hist[0, 31] > 0 and hist[0, :32].sum() == nb_y and hist[1, 0] == nb_y
+
+
+@pytest.mark.gpu
+def test_gpu_stats_large_dc(cuda):
+    nb_y, nb_c = LARGE_DC
+    coef = _large_dc()
+    dc, hist = _gpu_stats(coef, nb_y, nb_c, cuda)
+    rdc, rhist = O.entropy_stats(coef, nb_y, nb_c)
+    assert np.array_equal(dc, rdc), np.flatnonzero(dc != rdc)[:8].tolist()
+    assert np.array_equal(hist, rhist), np.argwhere(hist != rhist)[:8].tolist()

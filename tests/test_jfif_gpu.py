@@ -190,7 +190,7 @@ def test_all_zero_frame(cuda):
 
 
 @gpu
-@pytest.mark.parametrize("sr", [0, 2])
+@pytest.mark.parametrize("sr", [0, 1, 2])
 def test_hand_made_blocks(cuda, sr):
     W, H = 64, 32
     nb, nbc = _nblocks(W, H, sr)
@@ -214,18 +214,19 @@ def test_hand_made_blocks(cuda, sr):
 
 
 @gpu
-def test_stuffing_heavy_frame(cuda):
+@pytest.mark.parametrize("sr", [0, 2])
+def test_stuffing_heavy_frame(cuda, sr):
     W, H, q = 64, 96, 50
-    nb = (W // 8) * (H // 8)
+    nb, nbc = _nblocks(W, H, sr)
     vals = np.array([0, 0, 0, 1, -1, 1023, -1023, 32767, -32768, 2047, -2047], np.int16)
-    coef = np.ascontiguousarray(np.random.default_rng(0).choice(vals, (3 * nb, 64)))
-    ref = _host(coef, W, H, q, 0, 1)
+    coef = np.ascontiguousarray(np.random.default_rng(0).choice(vals, (nb + 2 * nbc, 64)))
+    ref = _host(coef, W, H, q, sr, 1)
     scan = _scan(ref)
     pairs = scan.count(b"\xff\x00")
     endings = sum(scan.count(b"\xff\x00\xff" + bytes([0xd0 + m])) for m in range(8))
     print(f"stuffed pairs {pairs}, intervals ending FF 00 FF Dn {endings}")
     assert pairs >= 1000 and endings >= 1          # a different numpy must not empty the case
-    assert _device(cuda, coef, W, H, q, 0, 1) == ref
+    assert _device(cuda, coef, W, H, q, sr, 1) == ref
 
 
 @gpu
