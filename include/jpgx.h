@@ -200,6 +200,25 @@ int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframe
                   size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
                   size_t workspace_bytes, void *stream);
 
+/* A flag of the JFIF writers (jpgx_jfif_gpu_ex, jpgx_write_jfif_opt): per-image Huffman tables by
+ * T.81 Annex K.2 from the image's own symbol counts instead of the Annex K.3 tables -- the same
+ * file with other DHT contents and a shorter scan. */
+#define JPGX_JFIF_OPTIMIZE 1u
+
+/* jpgx_jfif_gpu with jfif_flags.  0: exactly jpgx_jfif_gpu_workspace_size / jpgx_jfif_gpu (the same
+ * size, bytes and launches).  JPGX_JFIF_OPTIMIZE: frame f's file is, byte for byte, what
+ * jpgx_write_jfif_opt writes for its coefficients with the same restart_rows and flags; every
+ * frame of a batch gets its own tables.  The contract above holds as it stands (checks before any
+ * device call, asynchronous, capturable, stateless, the workspace -- symbol counts included --
+ * initialised by the call itself); in the overflow report "headers" is the frame's own header
+ * length.  Unknown flag bits: JPGX_EARG (size 0 from the size query). */
+size_t jpgx_jfif_gpu_workspace_size_ex(int width, int height, int sample_ratio, int restart_rows,
+                                       size_t nframes, size_t out_cap, unsigned jfif_flags);
+int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width,
+                     int height, int quality, int sample_ratio, int restart_rows,
+                     unsigned jfif_flags, uint8_t *d_out, size_t out_frame_stride, size_t out_cap,
+                     uint64_t *d_len, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* Synthetic frames, generated directly in device memory (SURVEY.md 8c generator G: byte k
  * of the buffer = splitmix64(seed + (k+1)*0x9E3779B97F4A7C15) >> 56). */
 int jpgx_gen_splitmix_gpu(uint8_t *d_dst, size_t nbytes, uint64_t seed, void *stream);

@@ -177,6 +177,16 @@ int jpgx_write_jfif_sub(const int16_t *coef, int width, int height, int quality,
 int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, int sample_ratio,
                        int restart_rows, int nthreads, uint8_t *out, size_t cap, size_t *len);
 
+/* The same with jfif_flags (include/jpgx.h).  0: jpgx_write_jfif_ex.  JPGX_JFIF_OPTIMIZE: the four
+ * DHT segments hold tables built by T.81 Annex K.2 from the image's own symbol counts (one
+ * counting pass over the coefficients on the same threads) and the scan is coded with them; the
+ * rest of the file is unchanged and it is never longer than the K.3 header allows for.  The bytes
+ * do not depend on `nthreads` for a fixed restart_rows >= 0 (-1, auto, chooses the interval from
+ * the thread count, as in jpgx_write_jfif_ex).  Unknown flag bits: JPGX_EARG. */
+int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality, int sample_ratio,
+                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out,
+                        size_t cap, size_t *len);
+
 /* encode_bmp_to_jpeg with flags: JPGX_FLAG_SUBSAMPLE and sample_ratio 1/2 write a truly
  * subsampled JFIF (extension); otherwise exactly jpgx_encode_bmp_to_jpeg.  GPU `device`. */
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

@@ -143,6 +143,28 @@ int jx_launch_alt(const struct jx_xform_args *xa, int sr, size_t nbc, void *stre
 void jx_jfif_codes(uint32_t cl[4][256]);
 size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
                       uint8_t *out, size_t cap);
+/* The same with the four DHT segments (DC luminance, AC luminance, DC chrominance, AC chrominance)
+ * holding bits[k] / vals[k] (bits NULL: the Annex K.3 tables, i.e. jx_jfif_header); *dht_at, when
+ * asked for, is where the first DHT segment begins: the bytes before it and the bytes after the
+ * fourth segment (DRI, SOS) do not depend on the tables.  The K.3 segments are JX_JFIF_DHT_STD
+ * bytes together; no table of jx_jfif_optimal is longer (DC <= 12 values, AC <= 162). */
+#define JX_JFIF_DHT_STD 432
+size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio, unsigned ri,
+                           const uint8_t bits[4][16], const uint8_t vals[4][256], uint8_t *out,
+                           size_t cap, size_t *dht_at);
+/* jx_jfif_optimal: a table for the symbol counts by T.81 Annex K.2, stated exactly because the
+ * device coder (k_jf_tables, csrc/jpgx_jfif.hip) reproduces it bit for bit.
+ * Figure K.1: freq[0..255] = counts, freq[256] = 1 (the reserved point: no code is all ones).
+ * v1 = the index of the least nonzero freq, on a tie the largest index; v2 = the same among the
+ * indices != v1; none: done.  freq[v1] += freq[v2], freq[v2] = 0 (64-bit sums); codesize + 1 along
+ * v1's `others` chain, the chain's end linked to v2, codesize + 1 along v2's chain.
+ * Figure K.2: the number of codes of each size (sizes up to 256: the array is sized by the symbol
+ * count, not by 32).  Figure K.3: from the deepest size i down to 17, while bits[i] > 0:
+ * j = i - 2 stepped down to the first nonzero bits[j]; bits[i] -= 2, bits[i - 1]++,
+ * bits[j + 1] += 2, bits[j]--.  Then the reserved point leaves the largest nonzero size <= 16.
+ * Figure K.4: vals = the symbols 0..255 with codesize > 0, ordered by codesize, then by value.
+ * Returns the number of values (0 when every count is 0). */
+int jx_jfif_optimal(const uint64_t counts[256], uint8_t bits[16], uint8_t vals[256]);
 #ifdef __cplusplus
 }
 #endif

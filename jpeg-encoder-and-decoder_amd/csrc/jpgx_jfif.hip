@@ -22,6 +22,15 @@
  * writer does.  The code tables and the header bytes come from the host writer's own functions
  * (jx_jfif_codes, jx_jfif_header) as by-value kernel arguments: nothing is copied with a memcpy,
  * the call is asynchronous, capturable and keeps no state.
+ *
+ * With JPGX_JFIF_OPTIMIZE (jpgx_jfif_gpu_ex; the bytes of jpgx_write_jfif_opt) every frame gets
+ * Huffman tables of its own, and three launches come first:
+ *   k_jf_zero   the frame's symbol counts to zero
+ *   k_jf_count  k_jf_len's walk, counting the symbols instead of their bits
+ *   k_jf_tables per table: T.81 Annex K.2 exactly as jx_jfif_optimal (host/jpgx_jfif.c) -> the
+ *               frame's code tables, DHT segments and their lengths in the workspace
+ * k_jf_len, k_jf_pack and k_jf_frame are templates over where tables and header come from: the
+ * launch's by-value arguments (the standard path, the same code as before) or the frame's workspace.
  */
 #include <stdint.h>
 #include <string.h>
@@ -39,9 +48,9 @@ struct JfTabs {                         /* code << 8 | length */
     uint32_t ac[2][256];                /* [luma, chroma][run << 4 | category] */
 };
 
-struct JfHdr {
-    uint8_t b[JX_JFIF_HDR_MAX];
-};
+constexpr int kDhtSlot = 192;           /* bytes kept per DHT segment (at most 21 + 162) */
+constexpr int kHdrPre = 320;            /* SOI .. SOF: at most 2 + 18 + 2 x 133 + 19 bytes */
+constexpr int kHdrSuf = 32;             /* DRI, SOS: 6 + 14 bytes */
 
 struct JfArgs {
     const int16_t *coef;                /* frame f: Y [nb][64] | Cb [nbc][64] | Cr [nbc][64] at f fstride */
@@ -63,6 +72,36 @@ struct JfArgs {
     uint8_t *out;
     unsigned long long ostride, ocap;
     unsigned long long *len;
+};
+
+struct JfHdr {
+    uint8_t b[JX_JFIF_HDR_MAX];
+    __device__ __forceinline__ uint32_t length(const JfArgs &a, uint32_t) const { return a.hdrlen; }
+    __device__ __forceinline__ uint8_t byte(uint32_t, uint32_t i) const { return b[i]; }
+};
+
+/* optimised mode: the frame's own DHT segments between the bytes that do not depend on them */
+struct JfHdrOpt {
+    uint8_t pre[kHdrPre], suf[kHdrSuf];
+    uint32_t npre, nsuf;
+    const uint8_t *dht;                 /* [nframes][4][kDhtSlot] */
+    const uint32_t *dhtlen;             /* [nframes][4] */
+    __device__ __forceinline__ uint32_t length(const JfArgs &, uint32_t f) const
+    {
+        const uint32_t *n = dhtlen + 4 * (size_t)f;
+        return npre + n[0] + n[1] + n[2] + n[3] + nsuf;
+    }
+    __device__ __forceinline__ uint8_t byte(uint32_t f, uint32_t i) const
+    {
+        if (i < npre) return pre[i];
+        i -= npre;
+        const uint32_t *n = dhtlen + 4 * (size_t)f;
+        for (uint32_t k = 0; k < 4; k++) {
+            if (i < n[k]) return dht[((size_t)f * 4 + k) * kDhtSlot + i];
+            i -= n[k];
+        }
+        return suf[i];
+    }
 };
 
 /* block (MCU m of interval iv, position j in the MCU) in the frame's coefficient array */
@@ -255,7 +294,26 @@ __device__ __forceinline__ void jf_tabs_to_lds(const JfTabs &t, uint32_t (*dc)[1
     __syncthreads();
 }
 
-__global__ __launch_bounds__(kT) void k_jf_len(const JfArgs a, const JfTabs tabs)
+/* optimised mode (JPGX_JFIF_OPTIMIZE): what the call's own kernels leave per frame in the workspace */
+struct JfOpt {
+    unsigned long long *counts;         /* [nframes][4][256] symbol counts: DC luma, AC luma, DC chroma, AC chroma */
+    JfTabs *tabs;                       /* [nframes] the frame's code tables */
+    uint8_t *dht;                       /* [nframes][4][kDhtSlot] the frame's DHT segments */
+    uint32_t *dhtlen;                   /* [nframes][4] their lengths */
+};
+
+/* the frame's tables in the workspace instead of the launch's by-value tables */
+struct JfTabsOf {
+    const JfTabs *p;
+};
+
+__device__ __forceinline__ void jf_tabs_to_lds(const JfTabsOf &t, uint32_t (*dc)[16], uint32_t (*ac)[256])
+{
+    jf_tabs_to_lds(t.p[blockIdx.y], dc, ac);
+}
+
+template <class Tabs>                   /* JfTabs: the launch's tables; JfTabsOf: the frame's own */
+__global__ __launch_bounds__(kT) void k_jf_len(const JfArgs a, const Tabs tabs)
 {
     __shared__ uint32_t tile[kT * kRow];
     __shared__ uint32_t dc[2][16], ac[2][256];
@@ -302,7 +360,8 @@ __global__ __launch_bounds__(kT) void k_jf_place(const JfArgs a)
     if (t == 0) a.ovf[f] = carry > a.uarea ? 1u : 0u;
 }
 
-__global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const JfTabs tabs)
+template <class Tabs>
+__global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const Tabs tabs)
 {
     __shared__ uint32_t tile[kT * kRow];
     __shared__ uint32_t dc[2][16], ac[2][256];
@@ -370,13 +429,15 @@ __global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const JfTabs tab
 /* per frame: where each interval's stuffed bytes go, the length (or the overflow report: bit 63 and
  * a capacity that suffices whatever the stuffing -- headers + 2 x unstuffed bytes + markers + EOI),
  * the header bytes and EOI */
-__global__ __launch_bounds__(kT) void k_jf_frame(const JfArgs a, const JfHdr hdr)
+template <class Hdr>                    /* JfHdr: one header for the batch; JfHdrOpt: the frame's own */
+__global__ __launch_bounds__(kT) void k_jf_frame(const JfArgs a, const Hdr hdr)
 {
     __shared__ unsigned long long wtot[kT / 64];
     __shared__ uint32_t fits;
     const uint32_t f = blockIdx.x, t = threadIdx.x;
     const bool early = a.ovf[f] != 0;
-    unsigned long long carry = a.hdrlen, raw = 0;
+    const uint32_t hdrlen = hdr.length(a, f);
+    unsigned long long carry = hdrlen, raw = 0;
     for (uint32_t i0 = 0; i0 < a.ni; i0 += kT) {
         const uint32_t iv = i0 + t;
         unsigned long long sz = 0, un = 0;
@@ -396,12 +457,12 @@ __global__ __launch_bounds__(kT) void k_jf_frame(const JfArgs a, const JfHdr hdr
         const bool ok = !early && len <= a.ocap;
         fits = ok ? 1u : 0u;
         a.ovf[f] = ok ? 0u : 1u;
-        a.len[f] = ok ? len : (1ull << 63) | (a.hdrlen + 2 * raw + 2ull * (a.ni - 1) + 2);
+        a.len[f] = ok ? len : (1ull << 63) | (hdrlen + 2 * raw + 2ull * (a.ni - 1) + 2);
     }
     __syncthreads();
     if (!fits) return;
     uint8_t *out = a.out + (size_t)f * a.ostride;
-    for (uint32_t i = t; i < a.hdrlen; i += kT) out[i] = hdr.b[i];
+    for (uint32_t i = t; i < hdrlen; i += kT) out[i] = hdr.byte(f, i);
     if (t < 2) out[len - 2 + t] = t ? 0xd9 : 0xff;
 }
 
@@ -440,6 +501,210 @@ __global__ __launch_bounds__(kT) void k_jf_stuff(const JfArgs a)
     if (t < 2 && iv + 1 < a.ni) out[nbytes + carry + t] = t ? (uint8_t)(0xd0u + (iv & 7u)) : (uint8_t)0xff;
 }
 
+/* ---- optimised mode: the frame's symbol counts and its tables ------------------------------- */
+
+/* the counts start at zero in every call (a kernel, not a memset: capturable, and nothing depends
+ * on what the workspace held) */
+__global__ __launch_bounds__(kT) void k_jf_zero(const JfOpt o)
+{
+    unsigned long long *c = o.counts + (size_t)blockIdx.x * 1024;
+    for (uint32_t i = threadIdx.x; i < 1024u; i += kT) c[i] = 0;
+}
+
+constexpr int kBins = 2 * 16 + 2 * 256;  /* DC luma, DC chroma, AC luma, AC chroma */
+
+/* jf_code's walk, counting the symbols it codes: dc[category], ac[run << 4 | category] */
+__device__ __forceinline__ void jf_count(uint32_t *dc, uint32_t *ac, const uint32_t *row, uint64_t nz, int diff)
+{
+    uint32_t extra;
+    atomicAdd(dc + jf_category(diff, extra), 1u);
+    uint32_t prev = 0;
+    while (nz) {                        /* one symbol per turn: a ZRL while the run exceeds 15 */
+        const uint32_t k = (uint32_t)__builtin_ctzll(nz);
+        const uint32_t run = k - prev - 1u;
+        const bool zrl = run > 15u;
+        const uint32_t word = row[k >> 1];
+        int v = (k & 1u) ? (int)word >> 16 : (int)(int16_t)(word & 0xffffu);
+        v = v > 1023 ? 1023 : v;
+        v = v < -1023 ? -1023 : v;
+        const uint32_t s = jf_category(v, extra);
+        atomicAdd(ac + (zrl ? 0xf0u : (run << 4 | s)), 1u);
+        prev = zrl ? prev + 16u : k;
+        nz = zrl ? nz : nz & (nz - 1);
+    }
+    if (prev < 63u) atomicAdd(ac, 1u);
+}
+
+/* one workgroup per restart interval, as k_jf_len: the interval's symbols into LDS bins, the bins
+ * into the frame's counts with 64-bit atomic adds (integer sums: the order does not show).  One
+ * histogram for the workgroup: a copy per wave measured slower */
+__global__ __launch_bounds__(kT) void k_jf_count(const JfArgs a, const JfOpt o)
+{
+    __shared__ uint32_t tile[kT * kRow];
+    __shared__ uint32_t h[kBins];
+    const uint32_t iv = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    for (uint32_t i = t; i < (uint32_t)kBins; i += kT) h[i] = 0;
+    __syncthreads();
+    const uint32_t n = jf_nblk(a, iv);
+    for (uint32_t i = t; i < n; i += kT) {
+        int diff;
+        uint32_t ch;
+        const uint64_t nz = jf_load(a, f, iv, i, tile + t * kRow, diff, ch);
+        jf_count(h + 16u * ch, h + 32u + 256u * ch, tile + t * kRow, nz, diff);
+    }
+    __syncthreads();
+    unsigned long long *counts = o.counts + (size_t)f * 1024;
+    for (uint32_t i = t; i < (uint32_t)kBins; i += kT) {
+        const uint32_t c = h[i];
+        /* bins 0..31: DC [chroma][16] -> tables 0 / 2; then AC [chroma][256] -> tables 1 / 3 */
+        const uint32_t at = i < 32u ? (i >> 4) * 512u + (i & 15u) : 256u + ((i - 32u) >> 8) * 512u + ((i - 32u) & 255u);
+        if (c) atomicAdd(counts + at, (unsigned long long)c);
+    }
+}
+
+/* x of the lane a DPP control names (every lane is active where this is used) */
+template <int kCtrl>
+__device__ __forceinline__ unsigned long long jf_dpp(unsigned long long x)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)x, kCtrl, 0xf, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(x >> 32), kCtrl, 0xf, 0xf, false);
+    return (unsigned long long)hi << 32 | lo;
+}
+
+__device__ __forceinline__ unsigned long long jf_lane(unsigned long long x, int lane)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, lane);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(x >> 32), lane);
+    return (unsigned long long)hi << 32 | lo;
+}
+
+__device__ __forceinline__ unsigned long long jf_least(unsigned long long a, unsigned long long b) { return b < a ? b : a; }
+
+/* the wave's least key, the same in every lane (every lane active).  Within a row of 16 lanes the
+ * exchange is DPP (neighbours, pairs, the mirrored half row, the mirrored row: after each step the
+ * groups exchanged are uniform), the four rows meet through lane reads: no LDS round trip and no
+ * barrier, which is what a merge's time was made of */
+__device__ __forceinline__ unsigned long long jf_wave_min(unsigned long long key)
+{
+    key = jf_least(key, jf_dpp<0xb1>(key));                /* quad_perm [1, 0, 3, 2] */
+    key = jf_least(key, jf_dpp<0x4e>(key));                /* quad_perm [2, 3, 0, 1] */
+    key = jf_least(key, jf_dpp<0x141>(key));               /* row_half_mirror */
+    key = jf_least(key, jf_dpp<0x140>(key));               /* row_mirror */
+    return jf_least(jf_least(jf_lane(key, 0), jf_lane(key, 16)), jf_least(jf_lane(key, 32), jf_lane(key, 48)));
+}
+
+/* jx_jfif_optimal (host/jpgx_jfif.c, csrc/jpgx_internal.h) for table blockIdx.x of frame blockIdx.y,
+ * bit for bit.  The merges (Figure K.1) run on the first wave alone, in registers: lane l owns
+ * symbols l, l + 64, l + 128 and l + 192, every lane the reserved point 256.  A merge searches the
+ * least nonzero frequency twice (a wave reduction of keys freq << 9 | 256 - index: the least
+ * frequency, on a tie the largest index; a frame's symbols number below 2^34, so the key holds every
+ * sum).  A symbol's `others` chain is the set of symbols of its tree, so a lane keeps the tree each
+ * of its symbols is in and the two trees' members take their codesize + 1 at once.  Then the whole
+ * workgroup, a lane per symbol: the sizes are counted (Figure K.2), limited by one lane (K.3), the
+ * symbols ranked by (codesize, value) (K.4) and coded (Annex C); out go the packed codes, the DHT
+ * segment and its length. */
+__global__ __launch_bounds__(kT) void k_jf_tables(const JfOpt o)
+{
+    __shared__ uint32_t nsz[258], csz[kT + 1], first[17], upto[17], deepest;
+    __shared__ uint8_t vals[kT];
+    const uint32_t tb = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
+    for (uint32_t i = t; i < 258u; i += kT) nsz[i] = 0;
+    if (t == 0) deepest = 0;
+    if (t < 64u) {
+        constexpr unsigned long long kNone = ~0ull;
+        unsigned long long fr[4], fr256 = 1;
+        uint32_t tree[4], c[4], tree256 = 256u, c256 = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            fr[k] = o.counts[((size_t)f * 4 + tb) * 256 + t + 64u * k];
+            tree[k] = t + 64u * k;
+            c[k] = 0;
+        }
+        for (int it = 0; it < 256; it++) {                 /* 257 leaves: at most 256 merges */
+            unsigned long long key = fr256 ? fr256 << 9 : kNone;          /* 256 - 256 = 0: wins every tie */
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++)
+                if (fr[k]) key = jf_least(key, fr[k] << 9 | (256u - t - 64u * k));
+            const unsigned long long k1 = jf_wave_min(key);
+            const uint32_t v1 = 256u - (uint32_t)(k1 & 511u);
+            key = fr256 && v1 != 256u ? fr256 << 9 : kNone;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++)
+                if (fr[k] && t + 64u * k != v1) key = jf_least(key, fr[k] << 9 | (256u - t - 64u * k));
+            const unsigned long long k2 = jf_wave_min(key);
+            if (k2 == kNone) break;                        /* the same for every lane */
+            const uint32_t v2 = 256u - (uint32_t)(k2 & 511u);
+            const unsigned long long sum = (k1 >> 9) + (k2 >> 9);
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                if (t + 64u * k == v1) fr[k] = sum;
+                if (t + 64u * k == v2) fr[k] = 0;
+                if (tree[k] == v1 || tree[k] == v2) c[k]++, tree[k] = v1;
+            }
+            if (v1 == 256u) fr256 = sum;
+            if (v2 == 256u) fr256 = 0;
+            if (tree256 == v1 || tree256 == v2) c256++, tree256 = v1;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) csz[t + 64u * k] = c[k];
+        if (t == 0) csz[kT] = c256;
+    }
+    __syncthreads();                                       /* the code sizes; nsz is zero */
+    const uint32_t cs = csz[t];
+    if (cs) atomicAdd(nsz + cs, 1u), atomicMax(&deepest, cs);
+    if (t == 0 && csz[kT]) atomicAdd(nsz + csz[kT], 1u), atomicMax(&deepest, csz[kT]);
+    __syncthreads();
+    if (t == 0) {
+        for (uint32_t i = deepest; i > 16u; i--)
+            while (nsz[i] > 0) {
+                uint32_t j = i - 2u;
+                while (j > 0 && nsz[j] == 0) j--;
+                nsz[i] -= 2u;
+                nsz[i - 1u]++;
+                nsz[j + 1u] += 2u;
+                nsz[j]--;
+            }
+        uint32_t last = 16;
+        while (last > 0 && nsz[last] == 0) last--;
+        if (last) nsz[last]--;
+        uint32_t code = 0, k = 0;                          /* Annex C: the first code of each length */
+        for (uint32_t l = 1; l <= 16u; l++) {
+            first[l] = code;
+            k += nsz[l];
+            upto[l] = k;                                   /* values of length <= l */
+            code = (code + nsz[l]) << 1;
+        }
+    }
+    /* rank among the used symbols by (codesize, value) */
+    uint32_t rank = 0, used = 0;
+    for (uint32_t i = 0; i < (uint32_t)kT; i++) {
+        const uint32_t c = csz[i];
+        used += c ? 1u : 0u;
+        rank += c && (c < cs || (c == cs && i < t)) ? 1u : 0u;
+    }
+    __syncthreads();                                       /* first, upto and the limited nsz */
+    uint32_t cl = 0;
+    if (cs) {
+        uint32_t l = 1;
+        while (l < 16u && rank >= upto[l]) l++;
+        cl = (first[l] + rank - (l > 1u ? upto[l - 1u] : 0u)) << 8 | l;
+        vals[rank] = (uint8_t)t;
+    }
+    JfTabs *tabs = o.tabs + f;
+    if (tb & 1u) tabs->ac[tb >> 1][t] = cl;
+    else if (t < 16u) tabs->dc[tb >> 1][t] = cl;
+    __syncthreads();                                       /* vals */
+    uint8_t *dht = o.dht + ((size_t)f * 4 + tb) * kDhtSlot;
+    const uint32_t seg = 2u + 1u + 16u + used;             /* the segment's length field */
+    if (t < 21u) {
+        const uint32_t id = (tb & 1u) << 4 | tb >> 1;      /* 0x00, 0x10, 0x01, 0x11 */
+        dht[t] = t == 0 ? 0xff : t == 1 ? 0xc4 : t == 2 ? (uint8_t)(seg >> 8) : t == 3 ? (uint8_t)seg
+                 : t == 4 ? (uint8_t)id : (uint8_t)nsz[t - 4u];
+    }
+    if (t < used && 21u + t < (uint32_t)kDhtSlot) dht[21u + t] = vals[t];
+    if (t == 0) o.dhtlen[(size_t)f * 4 + tb] = min(2u + seg, (uint32_t)kDhtSlot);
+}
+
 size_t r16(size_t x) { return (x + 15) / 16 * 16; }
 
 /* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0 */
@@ -470,9 +735,10 @@ int jf_geometry(int width, int height, int sample_ratio, int restart_rows, size_
 
 struct JfLayout {
     size_t offs, ibits, nff, ustart, ostart, ovf, ustream, uarea, total;
+    size_t counts, tabs, dht, dhtlen;   /* JPGX_JFIF_OPTIMIZE only */
 };
 
-JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap)
+JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap, unsigned jfif_flags)
 {
     JfLayout l;
     size_t at = 0;
@@ -484,6 +750,13 @@ JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap)
     l.ovf = at, at += r16(nframes * sizeof(uint32_t));
     l.uarea = r16(out_cap) + 16 * (size_t)a.ni;
     l.ustream = at, at += nframes * l.uarea;
+    l.counts = l.tabs = l.dht = l.dhtlen = 0;
+    if (jfif_flags & JPGX_JFIF_OPTIMIZE) {
+        l.counts = at, at += r16(nframes * 4 * 256 * sizeof(unsigned long long));
+        l.tabs = at, at += r16(nframes * sizeof(JfTabs));
+        l.dht = at, at += r16(nframes * 4 * kDhtSlot);
+        l.dhtlen = at, at += r16(nframes * 4 * sizeof(uint32_t));
+    }
     l.total = at;
     return l;
 }
@@ -495,17 +768,34 @@ extern "C" {
 size_t jpgx_jfif_gpu_workspace_size(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
                                     size_t out_cap)
 {
+    return jpgx_jfif_gpu_workspace_size_ex(width, height, sample_ratio, restart_rows, nframes, out_cap, 0u);
+}
+
+size_t jpgx_jfif_gpu_workspace_size_ex(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
+                                       size_t out_cap, unsigned jfif_flags)
+{
     JfArgs a;
+    if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return 0;
     if (jf_geometry(width, height, sample_ratio, restart_rows, nframes, a)) return 0;
-    return jf_layout(a, nframes, out_cap).total;
+    return jf_layout(a, nframes, out_cap, jfif_flags).total;
 }
 
 int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
                   int quality, int sample_ratio, int restart_rows, uint8_t *d_out, size_t out_frame_stride,
                   size_t out_cap, uint64_t *d_len, void *d_workspace, size_t workspace_bytes, void *stream)
 {
+    return jpgx_jfif_gpu_ex(d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
+                            0u, d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
+}
+
+int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                     int quality, int sample_ratio, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
+                     size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
+                     size_t workspace_bytes, void *stream)
+{
     JfArgs a;
     memset(&a, 0, sizeof a);
+    if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return JPGX_EARG;
     if (!d_coef || !d_out || !d_len || !d_workspace || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_out & 15) ||
         ((uintptr_t)d_len & 7) || ((uintptr_t)d_workspace & 15))
         return JPGX_EARG;
@@ -515,10 +805,12 @@ int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframe
         return JPGX_EARG;
     JfHdr hdr;
     memset(&hdr, 0, sizeof hdr);
-    const size_t hl = jx_jfif_header(width, height, quality, sample_ratio, a.rpi * a.cpr, hdr.b, sizeof hdr.b);
+    size_t dht_at = 0;
+    const size_t hl = jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.cpr, NULL, NULL, hdr.b,
+                                          sizeof hdr.b, &dht_at);
     if (!hl) return JPGX_EQUALITY;
     if (hl > sizeof hdr.b) return JPGX_EARG;
-    const JfLayout l = jf_layout(a, nframes, out_cap);
+    const JfLayout l = jf_layout(a, nframes, out_cap, jfif_flags);
     if (workspace_bytes < l.total) return JPGX_EWORKSPACE;
     uint32_t cl[4][256];
     jx_jfif_codes(cl);
@@ -545,10 +837,38 @@ int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframe
     a.len = (unsigned long long *)d_len;
     hipStream_t s = (hipStream_t)stream;
     const dim3 per_interval(a.ni, (unsigned)nframes), per_frame((unsigned)nframes);
-    hipLaunchKernelGGL(k_jf_len, per_interval, dim3(kT), 0, s, a, tabs);
+    if (jfif_flags & JPGX_JFIF_OPTIMIZE) {
+        /* the standard header around its DHT segments: what every frame's header shares */
+        JfHdrOpt ho;
+        memset(&ho, 0, sizeof ho);
+        const size_t suf_at = dht_at + JX_JFIF_DHT_STD;
+        if (dht_at > sizeof ho.pre || suf_at > hl || hl - suf_at > sizeof ho.suf) return JPGX_EARG;
+        memcpy(ho.pre, hdr.b, dht_at);
+        memcpy(ho.suf, hdr.b + suf_at, hl - suf_at);
+        ho.npre = (uint32_t)dht_at;
+        ho.nsuf = (uint32_t)(hl - suf_at);
+        JfOpt o;
+        o.counts = (unsigned long long *)(ws + l.counts);
+        o.tabs = (JfTabs *)(ws + l.tabs);
+        o.dht = (uint8_t *)(ws + l.dht);
+        o.dhtlen = (uint32_t *)(ws + l.dhtlen);
+        ho.dht = o.dht;
+        ho.dhtlen = o.dhtlen;
+        const JfTabsOf tof{o.tabs};
+        hipLaunchKernelGGL(k_jf_zero, per_frame, dim3(kT), 0, s, o);
+        hipLaunchKernelGGL(k_jf_count, per_interval, dim3(kT), 0, s, a, o);
+        hipLaunchKernelGGL(k_jf_tables, dim3(4, (unsigned)nframes), dim3(kT), 0, s, o);
+        hipLaunchKernelGGL(k_jf_len<JfTabsOf>, per_interval, dim3(kT), 0, s, a, tof);
+        hipLaunchKernelGGL(k_jf_place, per_frame, dim3(kT), 0, s, a);
+        hipLaunchKernelGGL(k_jf_pack<JfTabsOf>, per_interval, dim3(kT), 0, s, a, tof);
+        hipLaunchKernelGGL(k_jf_frame<JfHdrOpt>, per_frame, dim3(kT), 0, s, a, ho);
+        hipLaunchKernelGGL(k_jf_stuff, per_interval, dim3(kT), 0, s, a);
+        return jx_hip_rc(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_jf_len<JfTabs>, per_interval, dim3(kT), 0, s, a, tabs);
     hipLaunchKernelGGL(k_jf_place, per_frame, dim3(kT), 0, s, a);
-    hipLaunchKernelGGL(k_jf_pack, per_interval, dim3(kT), 0, s, a, tabs);
-    hipLaunchKernelGGL(k_jf_frame, per_frame, dim3(kT), 0, s, a, hdr);
+    hipLaunchKernelGGL(k_jf_pack<JfTabs>, per_interval, dim3(kT), 0, s, a, tabs);
+    hipLaunchKernelGGL(k_jf_frame<JfHdr>, per_frame, dim3(kT), 0, s, a, hdr);
     hipLaunchKernelGGL(k_jf_stuff, per_interval, dim3(kT), 0, s, a);
     return jx_hip_rc(hipGetLastError());
 }

@@ -200,9 +200,66 @@ void jx_jfif_codes(uint32_t cl[4][256])
     memcpy(cl[3], h.cl, sizeof h.cl);
 }
 
+/* ---- per-image tables: ITU-T T.81 Annex K.2 (see csrc/jpgx_internal.h) ---------------------- */
+int jx_jfif_optimal(const uint64_t counts[256], uint8_t bits[16], uint8_t vals[256])
+{
+    uint64_t freq[257];
+    int codesize[257], others[257];
+    int nsz[258];                                          /* codes of each size: a tree of 257 leaves
+                                                              is at most 256 deep */
+    for (int i = 0; i < 256; i++) freq[i] = counts[i];
+    freq[256] = 1;                                         /* the reserved point: no code is all ones */
+    for (int i = 0; i < 257; i++) codesize[i] = 0, others[i] = -1;
+    for (;;) {                                             /* Figure K.1 */
+        int v1 = -1, v2 = -1;
+        for (int i = 0; i < 257; i++)                      /* the least, on a tie the largest index */
+            if (freq[i] && (v1 < 0 || freq[i] <= freq[v1])) v1 = i;
+        for (int i = 0; i < 257; i++)
+            if (freq[i] && i != v1 && (v2 < 0 || freq[i] <= freq[v2])) v2 = i;
+        if (v2 < 0) break;
+        freq[v1] += freq[v2];
+        freq[v2] = 0;
+        for (codesize[v1]++; others[v1] >= 0; codesize[v1]++) v1 = others[v1];
+        others[v1] = v2;
+        for (codesize[v2]++; others[v2] >= 0; codesize[v2]++) v2 = others[v2];
+    }
+    memset(nsz, 0, sizeof nsz);                            /* Figure K.2 */
+    int deepest = 0;
+    for (int i = 0; i < 257; i++)
+        if (codesize[i]) {
+            nsz[codesize[i]]++;
+            if (codesize[i] > deepest) deepest = codesize[i];
+        }
+    for (int i = deepest; i > 16; i--)                     /* Figure K.3 */
+        while (nsz[i] > 0) {
+            int j = i - 2;
+            while (j > 0 && nsz[j] == 0) j--;
+            nsz[i] -= 2;
+            nsz[i - 1]++;
+            nsz[j + 1] += 2;
+            nsz[j]--;
+        }
+    int last = 16;
+    while (last > 0 && nsz[last] == 0) last--;
+    if (last) nsz[last]--;                                 /* the reserved point leaves */
+    for (int i = 0; i < 16; i++) bits[i] = (uint8_t)nsz[i + 1];
+    int n = 0;                                             /* Figure K.4 */
+    for (int sz = 1; sz <= deepest; sz++)
+        for (int i = 0; i < 256; i++)
+            if (codesize[i] == sz) vals[n++] = (uint8_t)i;
+    return n;
+}
+
 /* SOI, APP0, DQT x 2, SOF, DHT x 4, DRI (ri != 0), SOS: see csrc/jpgx_internal.h */
 size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
                       uint8_t *out, size_t cap)
+{
+    return jx_jfif_header_tabs(width, height, quality, sample_ratio, ri, NULL, NULL, out, cap, NULL);
+}
+
+size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio, unsigned ri,
+                           const uint8_t bits[4][16], const uint8_t vals[4][256], uint8_t *out,
+                           size_t cap, size_t *dht_at)
 {
     int qs[2][8][8];
     if (jpgx_scale_table(0, quality, qs[0]) || jpgx_scale_table(1, quality, qs[1])) return 0;
@@ -252,10 +309,18 @@ size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsi
         put_byte(&o, (uint8_t)(c ? 0x11 : (hs << 4 | vs)));   /* 0x11, 0x21 or 0x22 */
         put_byte(&o, (uint8_t)(c ? 1 : 0));
     }
-    put_dht(&o, 0x00, kDcLumBits, kDcVals);
-    put_dht(&o, 0x10, kAcLumBits, kAcLumVals);
-    put_dht(&o, 0x01, kDcChrBits, kDcVals);
-    put_dht(&o, 0x11, kAcChrBits, kAcChrVals);
+    if (dht_at) *dht_at = o.n;
+    if (bits) {
+        put_dht(&o, 0x00, bits[0], vals[0]);
+        put_dht(&o, 0x10, bits[1], vals[1]);
+        put_dht(&o, 0x01, bits[2], vals[2]);
+        put_dht(&o, 0x11, bits[3], vals[3]);
+    } else {
+        put_dht(&o, 0x00, kDcLumBits, kDcVals);
+        put_dht(&o, 0x10, kAcLumBits, kAcLumVals);
+        put_dht(&o, 0x01, kDcChrBits, kDcVals);
+        put_dht(&o, 0x11, kAcChrBits, kAcChrVals);
+    }
     if (ri) {                                              /* DRI (T.81 B.2.4.4) */
         put_u16(&o, 0xffdd);
         put_u16(&o, 4);
@@ -333,6 +398,35 @@ static void encode_block(BW *w, const int16_t *z, int *pred, const HuffCodes *dc
     }
 }
 
+/* encode_block's walk, counting the symbols it codes instead of writing them: dc[category],
+ * ac[run << 4 | category] (ZRL 0xf0, EOB 0x00) */
+static void count_block(const int16_t *z, int *pred, uint64_t *dc, uint64_t *ac)
+{
+    uint32_t extra;
+    int diff = z[0] - *pred;
+    if (diff > 2047) diff = 2047;
+    if (diff < -2047) diff = -2047;
+    *pred = z[0];
+    dc[category(diff, &extra)]++;
+    uint64_t nz = nonzero_mask(z) & ~1ull;
+    int prev = 0;
+    while (nz) {
+        const int k = __builtin_ctzll(nz);
+        nz &= nz - 1;
+        int run = k - prev - 1;
+        prev = k;
+        int v = z[k];
+        if (v > 1023) v = 1023;
+        if (v < -1023) v = -1023;
+        while (run > 15) {
+            ac[0xf0]++;
+            run -= 16;
+        }
+        ac[run << 4 | category(v, &extra)]++;
+    }
+    if (prev < 63) ac[0x00]++;
+}
+
 size_t jpgx_jfif_bound(int width, int height)
 {
     if (width <= 0 || height <= 0) return 0;
@@ -385,17 +479,56 @@ static void code_intervals(const Scan *S, size_t i0, size_t i1, BW *w)
     }
 }
 
+/* the symbols of restart intervals [i0, i1) into cnt: DC luma, AC luma, DC chroma, AC chroma (Cb
+ * and Cr together), in code_intervals' order and with its predictor resets */
+static void count_intervals(const Scan *S, size_t i0, size_t i1, uint64_t (*cnt)[256])
+{
+    for (size_t iv = i0; iv < i1; iv++) {
+        int pred[3] = {0, 0, 0};
+        const size_t r0 = iv * S->rows_per_interval;
+        size_t r1 = r0 + S->rows_per_interval;
+        if (r1 > S->mrows) r1 = S->mrows;
+        for (size_t my = r0; my < r1; my++)
+            for (size_t mx = 0; mx < S->cpr; mx++) {
+                for (int dy = 0; dy < S->vs; dy++)
+                    for (int dx = 0; dx < S->hs; dx++) {
+                        const size_t yb = (my * S->vs + dy) * S->bpr + mx * S->hs + dx;
+                        count_block(S->coef + yb * 64, &pred[0], cnt[0], cnt[1]);
+                    }
+                const size_t cb = my * S->cpr + mx;
+                count_block(S->coef + (S->nb + cb) * 64, &pred[1], cnt[2], cnt[3]);
+                count_block(S->coef + (S->nb + S->nbc + cb) * 64, &pred[2], cnt[2], cnt[3]);
+            }
+    }
+}
+
 typedef struct {
     const Scan *S;
     size_t i0, i1;
     BW w;
+    uint64_t (*cnt)[256];                                  /* non-NULL: count, do not code */
 } Job;
 
 static void *job_main(void *arg)
 {
     Job *j = (Job *)arg;
-    code_intervals(j->S, j->i0, j->i1, &j->w);
+    if (j->cnt) count_intervals(j->S, j->i0, j->i1, j->cnt);
+    else code_intervals(j->S, j->i0, j->i1, &j->w);
     return NULL;
+}
+
+/* jobs 1 .. T - 1 on threads of their own, job 0 and whatever got no thread on the caller's */
+static void run_jobs(Job *jobs, pthread_t *tid, long T)
+{
+    long nthr = T;
+    for (long t = 1; t < T; t++)
+        if (pthread_create(&tid[t], NULL, job_main, &jobs[t])) {
+            nthr = t;
+            break;
+        }
+    job_main(&jobs[0]);
+    for (long t = nthr; t < T; t++) job_main(&jobs[t]);
+    for (long t = 1; t < nthr; t++) pthread_join(tid[t], NULL);
 }
 
 int jpgx_write_jfif(const int16_t *coef, int width, int height, int quality, uint8_t *out,
@@ -413,6 +546,15 @@ int jpgx_write_jfif_sub(const int16_t *coef, int width, int height, int quality,
 int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, int sample_ratio,
                        int restart_rows, int nthreads, uint8_t *out, size_t cap, size_t *len)
 {
+    return jpgx_write_jfif_opt(coef, width, height, quality, sample_ratio, restart_rows, nthreads, 0u, out,
+                               cap, len);
+}
+
+int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality, int sample_ratio,
+                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
+                        size_t *len)
+{
+    if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return JPGX_EARG;
     if (!coef || !out || width <= 0 || height <= 0 || width % 8 || height % 8 ||
         width > 65535 || height > 65535 || sample_ratio < 0 || sample_ratio > 2 ||
         restart_rows < -1 || nthreads < 0)
@@ -450,36 +592,58 @@ int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, 
     S.rows_per_interval = rr ? rr : S.mrows;
     S.nintervals = (S.mrows + S.rows_per_interval - 1) / S.rows_per_interval;
     if ((size_t)T > S.nintervals) T = (long)S.nintervals;
-    uint32_t cl[4][256];
-    jx_jfif_codes(cl);
-    memcpy(S.dc[0].cl, cl[0], sizeof cl[0]);
-    memcpy(S.ac[0].cl, cl[1], sizeof cl[1]);
-    memcpy(S.dc[1].cl, cl[2], sizeof cl[2]);
-    memcpy(S.ac[1].cl, cl[3], sizeof cl[3]);
+    const int opt = (jfif_flags & JPGX_JFIF_OPTIMIZE) != 0;
 
-    /* headers */
-    Out o = {out, 0, cap, 0};
-    o.n = jx_jfif_header(width, height, quality, sample_ratio, (unsigned)(rr * S.cpr), out, cap);
-    if (!o.n) return JPGX_EQUALITY;
-    if (o.n > cap) o.overflow = 1;
-
-    /* the scan: thread t codes intervals [t NI / T, (t + 1) NI / T) into its own buffer */
+    /* thread t takes intervals [t NI / T, (t + 1) NI / T) */
     Job *jobs = (Job *)calloc((size_t)T, sizeof(Job));
     pthread_t *tid = (pthread_t *)calloc((size_t)T, sizeof(pthread_t));
-    int rc = (jobs && tid) ? JPGX_OK : JPGX_ENOMEM;
-    long nthr = T;                                         /* jobs 1 .. nthr - 1 run on threads */
+    uint64_t (*cnt)[256] = opt ? (uint64_t (*)[256])calloc((size_t)T * 4, sizeof *cnt) : NULL;
+    int rc = (jobs && tid && (cnt || !opt)) ? JPGX_OK : JPGX_ENOMEM;
     for (long t = 0; t < T && !rc; t++) {
         jobs[t].S = &S;
         jobs[t].i0 = (size_t)t * S.nintervals / (size_t)T;
         jobs[t].i1 = (size_t)(t + 1) * S.nintervals / (size_t)T;
-        if (t == 0 || t >= nthr) continue;                 /* the calling thread codes job 0 */
-        if (pthread_create(&tid[t], NULL, job_main, &jobs[t])) nthr = t;   /* no thread: code it here */
     }
+
+    /* the tables: Annex K.3's, or Annex K.2's from the image's own symbols (each thread counts the
+     * intervals it will code; integer sums, so the thread count does not show) */
+    uint8_t (*bits)[16] = NULL, (*vals)[256] = NULL;
+    uint8_t obits[4][16], ovals[4][256];
+    if (opt && !rc) {
+        for (long t = 0; t < T; t++) jobs[t].cnt = cnt + 4 * t;
+        run_jobs(jobs, tid, T);
+        for (long t = 1; t < T; t++)
+            for (int k = 0; k < 4; k++)
+                for (int s = 0; s < 256; s++) cnt[k][s] += cnt[4 * t + k][s];
+        memset(ovals, 0, sizeof ovals);
+        for (int k = 0; k < 4; k++) {
+            HuffCodes *h = k == 0 ? &S.dc[0] : k == 1 ? &S.ac[0] : k == 2 ? &S.dc[1] : &S.ac[1];
+            jx_jfif_optimal(cnt[k], obits[k], ovals[k]);
+            build_codes(obits[k], ovals[k], h);
+        }
+        for (long t = 0; t < T; t++) jobs[t].cnt = NULL;
+        bits = obits;
+        vals = ovals;
+    } else if (!rc) {
+        uint32_t cl[4][256];
+        jx_jfif_codes(cl);
+        memcpy(S.dc[0].cl, cl[0], sizeof cl[0]);
+        memcpy(S.ac[0].cl, cl[1], sizeof cl[1]);
+        memcpy(S.dc[1].cl, cl[2], sizeof cl[2]);
+        memcpy(S.ac[1].cl, cl[3], sizeof cl[3]);
+    }
+
+    /* headers */
+    Out o = {out, 0, cap, 0};
     if (!rc) {
-        job_main(&jobs[0]);
-        for (long t = nthr; t < T; t++) job_main(&jobs[t]);   /* the jobs no thread took */
+        o.n = jx_jfif_header_tabs(width, height, quality, sample_ratio, (unsigned)(rr * S.cpr),
+                                  (const uint8_t (*)[16])bits, (const uint8_t (*)[256])vals, out, cap, NULL);
+        if (!o.n) rc = JPGX_EQUALITY;
+        if (o.n > cap) o.overflow = 1;
     }
-    for (long t = 1; t < nthr; t++) pthread_join(tid[t], NULL);
+
+    /* the scan: every thread codes into its own buffer */
+    if (!rc) run_jobs(jobs, tid, T);
     for (long t = 0; t < T && !rc; t++)
         if (jobs[t].w.oom) rc = JPGX_ENOMEM;
     if (!rc) {
@@ -496,6 +660,7 @@ int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, 
         for (long t = 0; t < T; t++) free(jobs[t].w.p);
     free(jobs);
     free(tid);
+    free(cnt);
     return rc;
 }
 

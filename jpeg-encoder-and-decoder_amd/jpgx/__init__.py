@@ -26,6 +26,7 @@ HORIZONTAL_SUBSAMPLING = 1
 HORIZONTAL_VERTICAL_SUBSAMPLING = 2
 FLAG_FORCE_EXACT = 1
 FLAG_SUBSAMPLE = 2      # true 4:2:2 / 4:2:0 chroma (extension; see include/jpgx.h)
+JFIF_OPTIMIZE = 1       # a flag of the JFIF writers: per-image Huffman tables (JPGX_JFIF_OPTIMIZE)
 
 OK, EGEOMETRY, EQUALITY, ESAMPLE, EARG, EHIP, EWORKSPACE, ENODEV, ENOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 _ERRNAMES = {-1: "EGEOMETRY", -2: "EQUALITY", -3: "ESAMPLE", -4: "EARG", -5: "EHIP",
@@ -44,6 +45,7 @@ EXPORTS = [
     "jpgx_host_create", "jpgx_host_destroy", "jpgx_host_blocks",
     "jpgx_host_register", "jpgx_host_unregister", "jpgx_host_release",
     "jpgx_jfif_gpu_workspace_size", "jpgx_jfif_gpu",
+    "jpgx_jfif_gpu_workspace_size_ex", "jpgx_jfif_gpu_ex",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -52,7 +54,7 @@ COMPAT_EXPORTS = [
     "jpgx_fill_jpgdata", "jpgx_free_jpgdata", "jpgx_dpcm", "jpgx_dpcm_dc", "jpgx_bmp_read",
     "jpgx_free", "jpgx_encode_bmp", "jpgx_jfif_bound", "jpgx_write_jfif",
     "jpgx_encode_bmp_to_jpeg", "jpgx_write_jfif_sub", "jpgx_encode_bmp_to_jpeg_ex",
-    "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex",
+    "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex", "jpgx_write_jfif_opt",
 ]
 
 
@@ -119,6 +121,9 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_gpu_workspace_size.argtypes = [i, i, i, i, sz, sz]
     L.jpgx_jfif_gpu_workspace_size.restype = sz
     L.jpgx_jfif_gpu.argtypes = [vp, sz, sz, i, i, i, i, i, vp, sz, sz, vp, vp, sz, vp]
+    L.jpgx_jfif_gpu_workspace_size_ex.argtypes = [i, i, i, i, sz, sz, ctypes.c_uint]
+    L.jpgx_jfif_gpu_workspace_size_ex.restype = sz
+    L.jpgx_jfif_gpu_ex.argtypes = [vp, sz, sz, i, i, i, i, i, ctypes.c_uint, vp, sz, sz, vp, vp, sz, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -316,7 +321,7 @@ def entropy_stats_gpu_batch(d_coef, nb_y: int, nb_c: int, stream=None):
 
 
 def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 0,
-             restart_rows: int = -1, cap: int | None = None, stream=None):
+             restart_rows: int = -1, cap: int | None = None, stream=None, optimize: bool = False):
     """The JFIF files of a frame batch, coded on the device (jpgx_jfif_gpu): d_coef int16
     [nframes][...] as encode_blocks / blocks_gpu write each frame ([3][nb][64], or Y | Cb | Cr with
     FLAG_SUBSAMPLE for sample_ratio 1, 2; each frame contiguous, frames d_coef.stride(0) elements
@@ -324,7 +329,9 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     out[f, :lens[f]], byte for byte compat.write_jfif_ex(coef, ..., restart_rows, nthreads=1)
     (restart_rows -1: one MCU row per interval).  cap: bytes per frame (default as
     compat.write_jfif_ex); when a frame needs more, one retry with the capacity the library
-    reports (that reads lens back, a synchronisation)."""
+    reports (that reads lens back, a synchronisation).  optimize: JFIF_OPTIMIZE, every frame coded
+    with Huffman tables built from its own symbols (jpgx_jfif_gpu_ex), byte for byte
+    compat.write_jfif_ex(..., optimize=True)."""
     import torch
     if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda:
         raise ValueError("jfif_gpu: d_coef must be a device tensor")
@@ -343,14 +350,15 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
         raise ValueError("jfif_gpu: 16-byte aligned frames, a stride of whole blocks")
     dev = d_coef.device
     cap = int(cap) if cap else max(1 << 20, per_frame // 2)
+    jflags = JFIF_OPTIMIZE if optimize else 0
     for attempt in range(2):
         out = torch.empty((nf, cap), dtype=torch.uint8, device=dev)
         lens = torch.empty(nf, dtype=torch.int64, device=dev)
-        need = int(lib.jpgx_jfif_gpu_workspace_size(width, height, sample_ratio, restart_rows, nf, cap))
+        need = int(lib.jpgx_jfif_gpu_workspace_size_ex(width, height, sample_ratio, restart_rows, nf, cap, jflags))
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _check(lib.jpgx_jfif_gpu(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
-                                 restart_rows, out.data_ptr(), cap, cap, lens.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
+        _check(lib.jpgx_jfif_gpu_ex(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
+                                    restart_rows, jflags, out.data_ptr(), cap, cap, lens.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
         if stream is not None:
             stream.synchronize()
         host = lens.cpu()
@@ -360,17 +368,18 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     return out, lens
 
 
-def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restart_rows: int = -1) -> bytes:
+def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restart_rows: int = -1,
+                optimize: bool = False) -> bytes:
     """One device image (H, W, 3 uint8 torch tensor on a GPU) -> its JFIF file: encode_blocks, then
     jfif_gpu, then a device-to-host copy of the file's bytes.  With FLAG_SUBSAMPLE and sample_ratio
-    1 / 2 the file is 4:2:2 / 4:2:0, otherwise 4:4:4."""
+    1 / 2 the file is 4:2:2 / 4:2:0, otherwise 4:4:4.  optimize: per-image Huffman tables (jfif_gpu)."""
     import torch
     if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
         raise ValueError("encode_jpeg: rgb must be a device tensor")
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     sub = sample_ratio if flags & FLAG_SUBSAMPLE else 0
     coef = encode_blocks(rgb, quality, sample_ratio, flags=flags if sub else flags & ~FLAG_SUBSAMPLE)
-    out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows)
+    out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows, optimize=optimize)
     n = int(lens[0])
     if n < 0:
         raise JpgxError(EARG, "jpgx_jfif_gpu (capacity)")

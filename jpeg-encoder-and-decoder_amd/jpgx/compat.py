@@ -89,6 +89,8 @@ def _setup(L):
     L.jpgx_encode_bmp_to_jpeg.argtypes = [ctypes.c_char_p, ctypes.c_char_p, i, i]
     L.jpgx_write_jfif_ex.argtypes = [vp, i, i, i, i, i, i, vp, ctypes.c_size_t,
                                      ctypes.POINTER(ctypes.c_size_t)]
+    L.jpgx_write_jfif_opt.argtypes = [vp, i, i, i, i, i, i, ctypes.c_uint, vp, ctypes.c_size_t,
+                                      ctypes.POINTER(ctypes.c_size_t)]
     L.jpgx_encode_rgb_to_jpeg.argtypes = [vp, i, i, ctypes.c_size_t, ctypes.c_char_p, i, i,
                                           ctypes.c_uint, i]
 
@@ -237,17 +239,20 @@ def write_jfif(coef: np.ndarray, width: int, height: int, quality: int) -> bytes
 
 
 def write_jfif_ex(coef: np.ndarray, width: int, height: int, quality: int, sample_ratio: int = 0,
-                  restart_rows: int = -1, nthreads: int = 0, cap: int | None = None) -> bytes:
+                  restart_rows: int = -1, nthreads: int = 0, cap: int | None = None,
+                  optimize: bool = False) -> bytes:
     """jpgx_write_jfif_ex: restart intervals of `restart_rows` MCU rows (-1 auto, 0 none) coded on
     `nthreads` host threads (0: one per CPU).  `cap`: output buffer size (default: grown on
-    demand from the size the library reports)."""
+    demand from the size the library reports).  optimize: jpgx_write_jfif_opt with
+    JPGX_JFIF_OPTIMIZE, Huffman tables built from the image's own symbols."""
     coef = np.ascontiguousarray(coef, np.int16)
     n = ctypes.c_size_t()
     cap = cap or max(1 << 20, coef.size // 2)
     for _ in range(2):
         buf = np.empty(cap, np.uint8)
-        rc = lib.jpgx_write_jfif_ex(coef.ctypes.data, width, height, quality, sample_ratio,
-                                    restart_rows, nthreads, buf.ctypes.data, cap, ctypes.byref(n))
+        rc = lib.jpgx_write_jfif_opt(coef.ctypes.data, width, height, quality, sample_ratio,
+                                     restart_rows, nthreads, 1 if optimize else 0, buf.ctypes.data, cap,
+                                     ctypes.byref(n))
         if rc == 0:
             return buf[:n.value].tobytes()
         if rc != -4 or n.value <= cap:                      # JPGX_EARG with the size needed

@@ -1,0 +1,141 @@
+/* jfif_opt_san.c -- TEST INFRASTRUCTURE (tests/test_jfif_opt.py): the per-image Huffman tables
+ * (jx_jfif_optimal, jpgx_write_jfif_opt of host/jpgx_jfif.c) under -fsanitize=address,undefined, as
+ * a program of its own: the builder on one used symbol, two equal counts, 256 equal counts, many
+ * ties, a count above 2^32, random vectors and the Fibonacci vectors on 18 and 19 symbols (trees
+ * deeper than 16), each result checked for Kraft's sum, its lengths and its values; the optimised
+ * writer into exact-size, short and empty buffers, on 1 and 3 threads.
+ * Exit status 0 and "jfif_opt_san: clean" when everything holds. */
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "jpgx_compat.h"
+#include "../../jpeg-encoder-and-decoder_amd/csrc/jpgx_internal.h"
+
+#define CHECK(c)                                                           \
+    do {                                                                   \
+        if (!(c)) {                                                        \
+            fprintf(stderr, "jfif_opt_san: line %d: %s\n", __LINE__, #c);  \
+            return 1;                                                      \
+        }                                                                  \
+    } while (0)
+
+static uint64_t rnd_state = 0x9e3779b97f4a7c15ull;
+static uint64_t rnd(void)
+{
+    rnd_state = rnd_state * 6364136223846793005ull + 1442695040888963407ull;
+    return rnd_state >> 33;
+}
+
+/* the builder on counts, into exact-size arrays; returns nonzero when a property fails */
+static int table(const uint64_t *counts, uint8_t *bits_out)
+{
+    uint64_t *c = (uint64_t *)malloc(256 * sizeof *c);
+    uint8_t *bits = (uint8_t *)malloc(16), *vals = (uint8_t *)malloc(256);
+    CHECK(c && bits && vals);
+    memcpy(c, counts, 256 * sizeof *c);
+    const int n = jx_jfif_optimal(c, bits, vals);
+    int used = 0, total = 0;
+    unsigned long kraft = 0;
+    for (int s = 0; s < 256; s++) used += counts[s] != 0;
+    for (int l = 1; l <= 16; l++) {
+        total += bits[l - 1];
+        kraft += (unsigned long)bits[l - 1] << (16 - l);
+    }
+    CHECK(n == used && total == used);
+    CHECK(kraft <= 65535ul);                               /* the all-ones code stays free */
+    int seen[256] = {0};
+    for (int i = 0; i < n; i++) {
+        CHECK(counts[vals[i]] != 0 && !seen[vals[i]]);
+        seen[vals[i]] = 1;
+    }
+    if (bits_out) memcpy(bits_out, bits, 16);
+    free(c);
+    free(bits);
+    free(vals);
+    return 0;
+}
+
+int main(void)
+{
+    uint64_t c[256];
+    uint8_t bits[16];
+
+    memset(c, 0, sizeof c);                                /* nothing used */
+    CHECK(!table(c, bits));
+    for (int i = 0; i < 16; i++) CHECK(bits[i] == 0);
+    c[0x21] = 7;                                           /* one used symbol */
+    CHECK(!table(c, bits) && bits[0] == 1);
+    memset(c, 0, sizeof c);
+    c[3] = c[200] = 5;                                     /* two equal counts */
+    CHECK(!table(c, bits) && bits[0] == 1 && bits[1] == 1);
+    for (int i = 0; i < 256; i++) c[i] = 9;                /* all 256 equal */
+    CHECK(!table(c, bits));
+    memset(c, 0, sizeof c);
+    for (int i = 0; i < 256; i += 3) c[i] = 1 + rnd() % 3; /* many ties */
+    CHECK(!table(c, NULL));
+    for (int i = 0; i < 256; i++) c[i] = rnd() % 50;       /* counts above 2^32 */
+    c[17] = (1ull << 32) + 12345;
+    c[0] = 1ull << 40;
+    CHECK(!table(c, NULL));
+    for (int k = 0; k < 8; k++) {                          /* random vectors */
+        const int shift = 4 + (int)(rnd() % 28);
+        for (int i = 0; i < 256; i++) c[i] = rnd() % 5 < 3 ? rnd() >> shift : 0;
+        CHECK(!table(c, NULL));
+    }
+    for (int n = 18; n <= 19; n++) {                       /* 1, 2, 3, 5, 8, ...: depth n */
+        memset(c, 0, sizeof c);
+        uint64_t a = 1, b = 2;
+        for (int i = 0; i < n; i++) {
+            c[(i * 37 + 5) & 255] = a;
+            const uint64_t t = a + b;
+            a = b;
+            b = t;
+        }
+        CHECK(!table(c, bits));
+        CHECK(bits[13] == 0 && bits[14] == (n == 18 ? 2 : 1) && bits[15] == (n == 18 ? 3 : 5));
+    }
+
+    /* the optimised writer */
+    for (int sr = 0; sr <= 2; sr++)
+        for (int rr = 0; rr <= 2; rr++) {
+            const int W = 48, H = 32;
+            const size_t nb = (size_t)(W / 8) * (H / 8), nbc = sr == 0 ? nb : sr == 1 ? nb / 2 : nb / 4;
+            const size_t ncoef = (nb + 2 * nbc) * 64;
+            int16_t *coef = (int16_t *)malloc(ncoef * sizeof(int16_t));      /* exact size */
+            CHECK(coef);
+            for (size_t i = 0; i < ncoef; i++) {
+                const int r = (int)(rnd() % 64);
+                coef[i] = (int16_t)(i % 64 == 0 ? (int)(rnd() % 4096) - 2048 : r < 40 ? 0 : r < 62 ? r - 51 : (int)(rnd() % 4000) - 2000);
+            }
+            size_t len = 0, len3 = 0, lstd = 0;
+            uint8_t probe;
+            CHECK(jpgx_write_jfif_opt(coef, W, H, 60, sr, rr, 1, JPGX_JFIF_OPTIMIZE, &probe, 0, &len) == JPGX_EARG);
+            CHECK(len > 200 && len <= jpgx_jfif_bound(W, H));
+            uint8_t *exact = (uint8_t *)malloc(len), *shrt = (uint8_t *)malloc(len - 7), *thr = (uint8_t *)malloc(len);
+            CHECK(exact && shrt && thr);
+            CHECK(jpgx_write_jfif_opt(coef, W, H, 60, sr, rr, 1, JPGX_JFIF_OPTIMIZE, exact, len, &len3) == JPGX_OK);
+            CHECK(len3 == len && exact[0] == 0xff && exact[1] == 0xd8 && exact[len - 2] == 0xff && exact[len - 1] == 0xd9);
+            len3 = 0;
+            CHECK(jpgx_write_jfif_opt(coef, W, H, 60, sr, rr, 1, JPGX_JFIF_OPTIMIZE, shrt, len - 7, &len3) == JPGX_EARG);
+            CHECK(len3 == len && memcmp(shrt, exact, 200) == 0);             /* the header's bytes fit */
+            CHECK(jpgx_write_jfif_opt(coef, W, H, 60, sr, rr, 3, JPGX_JFIF_OPTIMIZE, thr, len, &len3) == JPGX_OK);
+            CHECK(len3 == len && memcmp(thr, exact, len) == 0);
+            /* flags 0 is jpgx_write_jfif_ex; unknown flags are refused */
+            CHECK(jpgx_write_jfif_ex(coef, W, H, 60, sr, rr, 1, &probe, 0, &lstd) == JPGX_EARG && lstd > 0);
+            uint8_t *s0 = (uint8_t *)malloc(lstd), *s1 = (uint8_t *)malloc(lstd);
+            CHECK(s0 && s1);
+            CHECK(jpgx_write_jfif_ex(coef, W, H, 60, sr, rr, 1, s0, lstd, &len3) == JPGX_OK && len3 == lstd);
+            CHECK(jpgx_write_jfif_opt(coef, W, H, 60, sr, rr, 1, 0u, s1, lstd, &len3) == JPGX_OK && len3 == lstd);
+            CHECK(memcmp(s0, s1, lstd) == 0);
+            CHECK(jpgx_write_jfif_opt(coef, W, H, 60, sr, rr, 1, 2u, s1, lstd, &len3) == JPGX_EARG);
+            free(s0);
+            free(s1);
+            free(exact);
+            free(shrt);
+            free(thr);
+            free(coef);
+        }
+    puts("jfif_opt_san: clean");
+    return 0;
+}

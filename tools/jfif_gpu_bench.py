@@ -14,7 +14,15 @@ Per input:
   speedup         host_route_s / coder time
   xform_us, xform_plus_coder_us   the transform alone and transform + coder per batch (events)
   bytes_equal     every frame's device bytes == the host writer's
-Usage (GPU box): python tools/jfif_gpu_bench.py [OUT.json]"""
+With --optimize the run compares the coder with per-image Huffman tables (JPGX_JFIF_OPTIMIZE,
+jpgx_jfif_gpu_ex) against the standard one, in the same session and on the same coefficients, and
+writes profiles/jfif_gpu_opt.json; per input:
+  coder_us, coder_opt_us, opt_over_std      the two coders' times per batch (as above) and the medians' ratio
+  file_bytes_per_frame, file_bytes_per_frame_opt, opt_bytes_over_std
+  xform_plus_coder_us, xform_plus_coder_opt_us
+  bytes_equal     every frame's optimised device bytes == jpgx_write_jfif_opt on 16 host threads
+  host_route_s    D2H copy + jpgx_write_jfif_opt, frame after frame; best of 2
+Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize] [OUT.json]"""
 import json
 import os
 import sys
@@ -126,17 +134,91 @@ def measure(name, d_rgb, dev):
     }
 
 
+def measure_opt(name, d_rgb, dev):
+    nb = (W // 8) * (H // 8)
+    per = 3 * nb * 64
+    coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+    p = jpgx.default_params(W, H, Q, 0)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+
+    def xform():
+        jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+
+    xform()
+    torch.cuda.synchronize()
+    _, lens = jpgx.jfif_gpu(coef, W, H, Q, 0, 1, cap=1 << 20)      # the standard file is the longer one
+    cap = (int(lens.max()) + 4095) // 4096 * 4096
+    out = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+    lens = torch.empty(F, dtype=torch.int64, device=dev)
+    wsb = int(jpgx.lib.jpgx_jfif_gpu_workspace_size_ex(W, H, 0, 1, F, cap, jpgx.JFIF_OPTIMIZE))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def coder(flags):
+        def run():
+            rc = jpgx.lib.jpgx_jfif_gpu_ex(coef.data_ptr(), per, F, W, H, Q, 0, 1, flags, out.data_ptr(), cap, cap,
+                                           lens.data_ptr(), ws.data_ptr(), wsb, stream)
+            assert rc == 0, rc
+        return run
+
+    def both(flags):
+        run = coder(flags)
+
+        def go():
+            xform()
+            run()
+        return go
+
+    res = {"input": name}
+    files = {}
+    for key, flags in (("", 0), ("_opt", jpgx.JFIF_OPTIMIZE)):
+        coder(flags)()
+        torch.cuda.synchronize()
+        n = lens.cpu().numpy()
+        assert (n > 0).all(), n
+        files[key] = [out[f, :n[f]].cpu().numpy().tobytes() for f in range(F)]
+        res["file_bytes_per_frame" + key] = [int(x) for x in n]
+        res["coder%s_us" % key] = timed(coder(flags))
+        res["xform_plus_coder%s_us" % key] = timed(both(flags))
+        res["repeat_equal" + key] = all(out[f, :n[f]].cpu().numpy().tobytes() == files[key][f] for f in range(F))
+    res["xform_us"] = timed(xform)
+    res["opt_over_std"] = res["coder_opt_us"][2] / res["coder_us"][2]
+    res["opt_bytes_over_std"] = sum(res["file_bytes_per_frame_opt"]) / sum(res["file_bytes_per_frame"])
+
+    pinned = torch.empty((F, per), dtype=torch.int16).pin_memory()
+    host_s, host = [], None
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pinned.copy_(coef)
+        torch.cuda.synchronize()
+        hc = pinned.numpy()
+        host = [C.write_jfif_ex(hc[f].reshape(-1, 64), W, H, Q, 0, restart_rows=1, nthreads=HOST_THREADS,
+                                cap=cap, optimize=True) for f in range(F)]
+        host_s.append(time.perf_counter() - t0)
+    res["host_route_s"] = min(host_s)
+    res["host_threads"] = HOST_THREADS
+    res["speedup"] = min(host_s) / (res["coder_opt_us"][2] * 1e-6)
+    res["bytes_equal"] = all(host[f] == files["_opt"][f] for f in range(F))
+    res["repeat_equal"] = bool(res.pop("repeat_equal") and res.pop("repeat_equal_opt"))
+    return res
+
+
 def main():
-    dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(REPO, "profiles", "jfif_gpu.json")
+    args = [a for a in sys.argv[1:] if a != "--optimize"]
+    optimize = len(args) != len(sys.argv) - 1
+    run = measure_opt if optimize else measure
+    dst = args[0] if args else os.path.join(REPO, "profiles", "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py", "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
     for f in range(F):
         jpgx.gen_splitmix_gpu(d[f], 1000 + f)
-    res["runs"].append(measure("splitmix noise (the flagship's input)", d, dev))
+    res["runs"].append(run("splitmix noise (the flagship's input)", d, dev))
     print(json.dumps(res["runs"][-1]), flush=True)
     g = torch.Generator(device=dev).manual_seed(7)
     tiles = torch.randint(0, 256, (F, H // 8, W // 8, 3), generator=g, dtype=torch.uint8, device=dev)
@@ -144,7 +226,7 @@ def main():
     big += torch.randint(-6, 7, big.shape, generator=g, dtype=torch.int16, device=dev)
     d.copy_(big.clamp_(0, 255))
     del big, tiles
-    res["runs"].append(measure("flat 8x8 tiles + noise of +-6", d, dev))
+    res["runs"].append(run("flat 8x8 tiles + noise of +-6", d, dev))
     print(json.dumps(res["runs"][-1]), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
     with open(dst, "w") as fh:
