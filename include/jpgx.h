@@ -51,6 +51,10 @@ extern "C" {
 #define JPGX_EWORKSPACE (-6) /* workspace smaller than jpgx_workspace_size()               */
 #define JPGX_ENODEV (-7)     /* no usable GPU                                              */
 #define JPGX_ENOMEM (-8)     /* host allocation failed                                     */
+#define JPGX_EJFIF_HEADER (-9)  /* JFIF decoder: SOI .. SOS is not a file this decoder reads, or
+                                   is not the geometry the caller stated                      */
+#define JPGX_EJFIF_SCAN (-10)   /* JFIF decoder: the entropy-coded data, its restart markers or
+                                   EOI are wrong                                              */
 
 /* Chroma sampling constants, src/headers/jpg_encode.h:13-15.  The reference does not
  * actually subsample (src/downsample.c:24-32): 1 and 2 only tighten the geometry rule
@@ -218,6 +222,38 @@ int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nfr
                      int height, int quality, int sample_ratio, int restart_rows,
                      unsigned jfif_flags, uint8_t *d_out, size_t out_frame_stride, size_t out_cap,
                      uint64_t *d_len, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The way back: the coefficients of a batch of baseline JFIF files in device
+ * memory -- entropy decoding only; dequantisation, IDCT and colour conversion are not part of it.
+ * Frame f's file is the d_len[f] bytes at d_files + f * file_stride, exactly what jpgx_jfif_gpu
+ * leaves (pass its d_out, out_frame_stride and d_len on); its coefficients go to d_coef + f *
+ * coef_frame_stride int16 elements (a multiple of 64, at least one frame) in the layout of
+ * jpgx_blocks_gpu: [3][nb][64] for sample_ratio 0, Y | Cb | Cr as JPGX_FLAG_SUBSAMPLE writes them
+ * for 1 (4:2:2) and 2 (4:2:0); its two quantisation tables (Y's, then the one Cb and Cr share;
+ * zig-zag order as in the file) to d_qt + f * 128 when d_qt is not NULL; its status to d_status[f].
+ * What is read: jpgx_read_jfif's files (include/jpgx_compat.h) -- baseline SOF0, or SOF1 with 8-bit
+ * samples; three components in one interleaved scan; DHT ids 0 and 1; any restart interval, none
+ * included (the file is then decoded by a single lane).  The caller states width, height and
+ * sample_ratio, so that every buffer can be sized without a look at the files.
+ * d_status[f]: 0; JPGX_EJFIF_HEADER -- d_len[f] has bit 63 set (jpgx_jfif_gpu's overflow report) or
+ * exceeds file_stride, the header is refused, or it states another geometry; JPGX_EJFIF_SCAN -- the
+ * restart markers' count or numbers, a missing EOI, or an interval that does not decode to exactly
+ * its MCUs.  The value equals jpgx_read_jfif's return for the same bytes.  A frame with status 0
+ * has every coefficient written, equal to jpgx_read_jfif's; a failed frame's coefficients are
+ * unspecified; nothing is written outside a frame's (nb + 2 nbc) * 64 elements, and a failed frame
+ * does not touch the others.  The bytes are untrusted: no read leaves a file's d_len[f] bytes.
+ * Returns JPGX_EARG for null or misaligned pointers (d_coef, d_workspace: 16 bytes; d_len: 8;
+ * d_status: 4; d_qt: 2), nframes 0 or above 65535, file_stride 0 or within 4 KiB of 4 GiB and above, a
+ * coef_frame_stride that is no multiple of 64 or below a frame; JPGX_EGEOMETRY for a width or height
+ * that is no multiple of the MCU; JPGX_EWORKSPACE below jpgx_jfif_decode_gpu_workspace_size()
+ * (file_cap = file_stride; 0 for bad arguments) -- all before the first device call.  Asynchronous
+ * on `stream`, capturable, no global state; the call initialises what it reads of the workspace. */
+size_t jpgx_jfif_decode_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes,
+                                           size_t file_cap);
+int jpgx_jfif_decode_gpu(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len,
+                         size_t nframes, int width, int height, int sample_ratio, int16_t *d_coef,
+                         size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status,
+                         void *d_workspace, size_t workspace_bytes, void *stream);
 
 /* Synthetic frames, generated directly in device memory (SURVEY.md 8c generator G: byte k
  * of the buffer = splitmix64(seed + (k+1)*0x9E3779B97F4A7C15) >> 56). */

@@ -187,6 +187,38 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
                         int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out,
                         size_t cap, size_t *len);
 
+/* ---- 6. The way back: a baseline JFIF file's coefficients (entropy decoding only) ------------- */
+
+typedef struct jpgx_jfif_info {
+    int width, height, sample_ratio;    /* 0: 4:4:4, 1: 4:2:2, 2: 4:2:0                        */
+    unsigned restart_interval;          /* DRI's MCUs per interval, 0: none                    */
+    size_t scan_offset, nb_y, nb_c;     /* the first entropy-coded byte; blocks of Y, of Cb    */
+} jpgx_jfif_info;
+
+/* The header walk alone (SOI .. SOS).  Returns 0, JPGX_EARG (null pointers), JPGX_EJFIF_HEADER. */
+int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info);
+
+/* The quantised coefficients of a baseline JFIF file, in the layout the writers above take:
+ * [3][nb][64] for 4:4:4, Y [nb][64] | Cb [nbc][64] | Cr [nbc][64] for 4:2:2 / 4:2:0 (zig-zag,
+ * raster blocks) -- what jpgx_write_jfif* were given wherever that was inside their clamps.
+ * Reads baseline SOF0 (SOF1 with 8-bit samples), three components in one interleaved scan, luma
+ * sampled 1x1, 2x1 or 2x2 and chroma 1x1 (Cb and Cr sharing a quantisation table), width and
+ * height multiples of the MCU, DQT with 8- or 16-bit entries, DHT ids 0 and 1, DRI; skips APPn and
+ * COM; everything else, a file shorter than its header included: JPGX_EJFIF_HEADER.
+ * The restart intervals are found by their markers (FF D0 .. D7 cannot occur inside entropy-coded
+ * data) and decoded on `nthreads` threads (0: one per online CPU, at most 64); the result does
+ * not depend on the thread count.  A file without DRI is one interval.  JPGX_EJFIF_SCAN: the
+ * markers are not (intervals - 1) in number or not numbered k mod 8, EOI does not end the file, or
+ * an interval does not decode to exactly its MCUs (a code that is in no table, a coefficient past
+ * index 63, a DC size above 11 or an AC size above 10, a DC outside int16, bytes that run out or
+ * are left over).  The bytes are untrusted: no read leaves [file, file + len), no write leaves the
+ * frame's coefficients.  coef_cap: int16 elements at coef, at least (nb + 2 nbc) * 64, else
+ * JPGX_EARG (*info is then filled, so the size can be asked for with coef_cap 0 and a non-null
+ * coef).  qt (may be NULL): Y's table, then the chroma table, zig-zag order as in the file.  info
+ * (may be NULL): filled whenever the header was accepted. */
+int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap,
+                   uint16_t qt[2][64], jpgx_jfif_info *info);
+
 /* encode_bmp_to_jpeg with flags: JPGX_FLAG_SUBSAMPLE and sample_ratio 1/2 write a truly
  * subsampled JFIF (extension); otherwise exactly jpgx_encode_bmp_to_jpeg.  GPU `device`. */
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

@@ -9,6 +9,8 @@ Reference mapping (matthewT53/JPEG-Encoder-and-Decoder):
                              (src/jpg_encode.c:32-44), output = JpgData.zig_zag_{Y,Cb,Cr}
     default_params        <- encode_bmp_to_jpeg(quality, sample_ratio) (src/jpg_encode.c:19)
     scale_table           <- scale_table (src/quantise.c:74-86)
+No counterpart in the reference (its decoder is an empty header): jfif_decode_gpu,
+decode_jpeg_coefficients -- baseline JFIF files back to the coefficients.
 """
 from __future__ import annotations
 
@@ -29,8 +31,9 @@ FLAG_SUBSAMPLE = 2      # true 4:2:2 / 4:2:0 chroma (extension; see include/jpgx
 JFIF_OPTIMIZE = 1       # a flag of the JFIF writers: per-image Huffman tables (JPGX_JFIF_OPTIMIZE)
 
 OK, EGEOMETRY, EQUALITY, ESAMPLE, EARG, EHIP, EWORKSPACE, ENODEV, ENOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
+EJFIF_HEADER, EJFIF_SCAN = -9, -10      # the JFIF decoder's two refusals (include/jpgx.h)
 _ERRNAMES = {-1: "EGEOMETRY", -2: "EQUALITY", -3: "ESAMPLE", -4: "EARG", -5: "EHIP",
-             -6: "EWORKSPACE", -7: "ENODEV", -8: "ENOMEM"}
+             -6: "EWORKSPACE", -7: "ENODEV", -8: "ENOMEM", -9: "EJFIF_HEADER", -10: "EJFIF_SCAN"}
 
 # every function include/jpgx.h and include/jpgx_compat.h declare (tests check the library
 # exports them all)
@@ -46,6 +49,7 @@ EXPORTS = [
     "jpgx_host_register", "jpgx_host_unregister", "jpgx_host_release",
     "jpgx_jfif_gpu_workspace_size", "jpgx_jfif_gpu",
     "jpgx_jfif_gpu_workspace_size_ex", "jpgx_jfif_gpu_ex",
+    "jpgx_jfif_decode_gpu_workspace_size", "jpgx_jfif_decode_gpu",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -55,6 +59,7 @@ COMPAT_EXPORTS = [
     "jpgx_free", "jpgx_encode_bmp", "jpgx_jfif_bound", "jpgx_write_jfif",
     "jpgx_encode_bmp_to_jpeg", "jpgx_write_jfif_sub", "jpgx_encode_bmp_to_jpeg_ex",
     "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex", "jpgx_write_jfif_opt",
+    "jpgx_jfif_info_of", "jpgx_read_jfif",
 ]
 
 
@@ -124,6 +129,9 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_gpu_workspace_size_ex.argtypes = [i, i, i, i, sz, sz, ctypes.c_uint]
     L.jpgx_jfif_gpu_workspace_size_ex.restype = sz
     L.jpgx_jfif_gpu_ex.argtypes = [vp, sz, sz, i, i, i, i, i, ctypes.c_uint, vp, sz, sz, vp, vp, sz, vp]
+    L.jpgx_jfif_decode_gpu_workspace_size.argtypes = [i, i, i, sz, sz]
+    L.jpgx_jfif_decode_gpu_workspace_size.restype = sz
+    L.jpgx_jfif_decode_gpu.argtypes = [vp, sz, vp, sz, i, i, i, vp, sz, vp, vp, vp, sz, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -384,6 +392,69 @@ def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restar
     if n < 0:
         raise JpgxError(EARG, "jpgx_jfif_gpu (capacity)")
     return out[0, :n].cpu().numpy().tobytes()
+
+
+def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 0, stream=None):
+    """The coefficients of a batch of baseline JFIF files in device memory (jpgx_jfif_decode_gpu;
+    entropy decoding only): d_files uint8 [nframes][cap] and lens int64 [nframes] as jfif_gpu returns
+    them, every file of the stated width, height and sample_ratio ->
+    (coef int16 [nframes][nb + 2 nbc][64], qt uint16 [nframes][2][64], status int32 [nframes]), all
+    on the device.  Frame f's layout is encode_blocks' ([3][nb][64] viewed as [3 nb][64] for
+    sample_ratio 0, Y | Cb | Cr for 1, 2); status[f] is 0, EJFIF_HEADER or EJFIF_SCAN, what
+    compat.read_jfif reports for the same bytes; a frame with a nonzero status has unspecified
+    coefficients.  Nothing is copied to the host and nothing waits."""
+    import torch
+    for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"jfif_decode_gpu: {name} must be a device tensor")
+        if t.dtype != dt:
+            raise ValueError(f"jfif_decode_gpu: {name} must be {dt}")
+    if d_files.dim() != 2 or lens.dim() != 1 or lens.shape[0] != d_files.shape[0] or d_files.shape[0] == 0:
+        raise ValueError("jfif_decode_gpu: d_files [nframes][cap] and lens [nframes]")
+    if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
+        raise ValueError("jfif_decode_gpu: each file must be contiguous")
+    if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
+        raise ValueError("jfif_decode_gpu: bad geometry or sample_ratio")
+    nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
+    fstride = int(d_files.stride(0)) if nf > 1 else cap
+    if fstride < cap:
+        raise ValueError("jfif_decode_gpu: overlapping files")
+    nb = (width // 8) * (height // 8)
+    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, FLAG_SUBSAMPLE if sample_ratio else 0)
+    dev = d_files.device
+    coef = torch.empty((nf, nb + 2 * nbc, 64), dtype=torch.int16, device=dev)
+    qt = torch.empty((nf, 2, 64), dtype=torch.uint16, device=dev)
+    status = torch.empty(nf, dtype=torch.int32, device=dev)
+    need = int(lib.jpgx_jfif_decode_gpu_workspace_size(width, height, sample_ratio, nf, fstride))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _check(lib.jpgx_jfif_decode_gpu(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, sample_ratio,
+                                    coef.data_ptr(), (nb + 2 * nbc) * 64, qt.data_ptr(), status.data_ptr(),
+                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu")
+    if stream is not None:
+        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
+    return coef, qt, status
+
+
+def decode_jpeg_coefficients(data: bytes, device):
+    """One baseline JFIF file in host memory -> its coefficients on `device`: the header walk on the
+    host for the geometry (compat.jfif_info), one host-to-device copy of the bytes, jfif_decode_gpu.
+    Returns compat.read_jfif's dict with device tensors: coef int16 ([3][nb][64] for 4:4:4,
+    [nb + 2 nbc][64] otherwise), qt uint16 [2][64], width, height, sample_ratio, restart_interval.
+    Raises JpgxError on a nonzero status (that reads the status back, a synchronisation)."""
+    import torch
+    from . import compat
+    info = compat.jfif_info(data)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("decode_jpeg_coefficients: device must be a GPU")
+    host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+    d_files = host.to(dev).reshape(1, -1)
+    lens = torch.tensor([len(data)], dtype=torch.int64, device=dev)
+    coef, qt, status = jfif_decode_gpu(d_files, lens, info["width"], info["height"], info["sample_ratio"])
+    _check(int(status[0]), "jpgx_jfif_decode_gpu")
+    out = coef[0].reshape(3, -1, 64) if info["sample_ratio"] == 0 else coef[0]
+    return dict(coef=out, qt=qt[0], width=info["width"], height=info["height"],
+                sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
 
 
 def split_sub(out, nb: int, nbc: int):

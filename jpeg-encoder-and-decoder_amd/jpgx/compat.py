@@ -50,6 +50,12 @@ class JpegData(ctypes.Structure):
                 ("chrom_DC", HuffmanData), ("chrom_AC", HuffmanData)]
 
 
+class JfifInfo(ctypes.Structure):
+    _fields_ = [("width", ctypes.c_int), ("height", ctypes.c_int), ("sample_ratio", ctypes.c_int),
+                ("restart_interval", ctypes.c_uint), ("scan_offset", ctypes.c_size_t),
+                ("nb_y", ctypes.c_size_t), ("nb_c", ctypes.c_size_t)]
+
+
 def _setup(L):
     d, i, vp = ctypes.c_double, ctypes.c_int, ctypes.c_void_p
     L.jpgx_new_block.restype = BlockPtr
@@ -93,6 +99,10 @@ def _setup(L):
                                       ctypes.POINTER(ctypes.c_size_t)]
     L.jpgx_encode_rgb_to_jpeg.argtypes = [vp, i, i, ctypes.c_size_t, ctypes.c_char_p, i, i,
                                           ctypes.c_uint, i]
+
+
+    L.jpgx_jfif_info_of.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(JfifInfo)]
+    L.jpgx_read_jfif.argtypes = [vp, ctypes.c_size_t, i, vp, ctypes.c_size_t, vp, ctypes.POINTER(JfifInfo)]
 
 
 _setup(lib)
@@ -274,6 +284,41 @@ def write_jfif_sub(coef: np.ndarray, width: int, height: int, quality: int,
                                    ctypes.c_size_t(cap), ctypes.byref(n)),
            "jpgx_write_jfif_sub")
     return bytes(buf[:n.value])
+
+
+def _info_dict(info: JfifInfo) -> dict:
+    return dict(width=info.width, height=info.height, sample_ratio=info.sample_ratio,
+                restart_interval=info.restart_interval, scan_offset=info.scan_offset,
+                nb_y=info.nb_y, nb_c=info.nb_c)
+
+
+def jfif_info(data) -> dict:
+    """jpgx_jfif_info_of: the header walk of a baseline JFIF file (bytes) -> width, height,
+    sample_ratio, restart_interval, scan_offset, nb_y, nb_c.  JpgxError(EJFIF_HEADER) when refused."""
+    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    info = JfifInfo()
+    _check(lib.jpgx_jfif_info_of(buf.ctypes.data, len(data), ctypes.byref(info)), "jpgx_jfif_info_of")
+    return _info_dict(info)
+
+
+def read_jfif(data, nthreads: int = 1) -> dict:
+    """jpgx_read_jfif: a baseline JFIF file (bytes) -> dict(coef, qt, width, height, sample_ratio,
+    restart_interval): coef int16 [3][nb][64] for 4:4:4, [nb + 2 nbc][64] (Y | Cb | Cr) for 4:2:2 /
+    4:2:0 -- what the writers above take; qt uint16 [2][64] (Y's table, the chroma table; zig-zag
+    order).  The restart intervals are decoded on `nthreads` threads (0: one per CPU).
+    JpgxError(EJFIF_HEADER / EJFIF_SCAN) when the file is refused."""
+    info = jfif_info(data)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    nblk = info["nb_y"] + 2 * info["nb_c"]
+    coef = np.empty((nblk, 64), np.int16)
+    qt = np.zeros((2, 64), np.uint16)
+    got = JfifInfo()
+    _check(lib.jpgx_read_jfif(buf.ctypes.data, len(buf), nthreads, coef.ctypes.data, coef.size,
+                              qt.ctypes.data, ctypes.byref(got)), "jpgx_read_jfif")
+    if info["sample_ratio"] == 0:
+        coef = coef.reshape(3, info["nb_y"], 64)
+    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
+                sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
 
 
 def encode_bmp_to_jpeg_ex(src: str, dst: str, quality: int, sample_ratio: int, flags: int,

@@ -22,7 +22,15 @@ writes profiles/jfif_gpu_opt.json; per input:
   xform_plus_coder_us, xform_plus_coder_opt_us
   bytes_equal     every frame's optimised device bytes == jpgx_write_jfif_opt on 16 host threads
   host_route_s    D2H copy + jpgx_write_jfif_opt, frame after frame; best of 2
-Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize] [OUT.json]"""
+With --decode the run times the way back (jpgx_jfif_decode_gpu) on the files the
+coder writes from the same coefficients and writes profiles/jfif_gpu_dec.json; per input:
+  decode_us       jpgx_jfif_decode_gpu per batch (events, as above; all rounds, sorted)
+  host_route_s    the route without it: the files copied to pinned host memory + jpgx_read_jfif on 16
+                  threads, frame after frame; best of 2 (host_route_d2h_s: the copy alone)
+  device_over_host   decode time (median) / host_route_s: above 1, the host route is the faster one
+  intervals       restart intervals of the batch = the lanes that work
+  coefficients_equal   every frame's status 0 and its coefficients == the ones that were coded
+Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode] [OUT.json]"""
 import json
 import os
 import sys
@@ -205,14 +213,76 @@ def measure_opt(name, d_rgb, dev):
     return res
 
 
+def measure_dec(name, d_rgb, dev):
+    nb = (W // 8) * (H // 8)
+    per = 3 * nb * 64
+    coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+    p = jpgx.default_params(W, H, Q, 0)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+    jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+    torch.cuda.synchronize()
+    _, lens = jpgx.jfif_gpu(coef, W, H, Q, 0, 1, cap=1 << 20)
+    cap = (int(lens.max()) + 4095) // 4096 * 4096
+    files, lens = jpgx.jfif_gpu(coef, W, H, Q, 0, 1, cap=cap)
+    n = lens.cpu().numpy()
+    assert (n > 0).all(), n
+    back = torch.empty((F, per), dtype=torch.int16, device=dev)
+    qt = torch.empty((F, 2, 64), dtype=torch.uint16, device=dev)
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    wsb = int(jpgx.lib.jpgx_jfif_decode_gpu_workspace_size(W, H, 0, F, cap))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def dec():
+        rc = jpgx.lib.jpgx_jfif_decode_gpu(files.data_ptr(), cap, lens.data_ptr(), F, W, H, 0, back.data_ptr(), per,
+                                           qt.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb, stream)
+        assert rc == 0, rc
+
+    back.fill_(0x5A5A)
+    dec()
+    torch.cuda.synchronize()
+    equal = bool((status == 0).all()) and bool(torch.equal(back, coef))
+    t_dec = timed(dec)
+    equal = equal and bool((status == 0).all()) and bool(torch.equal(back, coef))
+
+    pinned = torch.empty((F, cap), dtype=torch.uint8).pin_memory()
+    host_s, d2h_s, host_equal = [], [], True
+    hc = coef.cpu().numpy()
+    got = [np.empty(per, np.int16) for _ in range(F)]
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pinned.copy_(files)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for f in range(F):                           # the library itself on the pinned bytes: no copy in between
+            rc = jpgx.lib.jpgx_read_jfif(pinned.data_ptr() + f * cap, int(n[f]), HOST_THREADS, got[f].ctypes.data,
+                                         per, None, None)
+            assert rc == 0, rc
+        t2 = time.perf_counter()
+        d2h_s.append(t1 - t0)
+        host_s.append(t2 - t0)
+        host_equal = host_equal and all(np.array_equal(got[f], hc[f]) for f in range(F))
+    return {
+        "input": name, "file_bytes_per_frame": [int(x) for x in n], "intervals": F * (H // 8),
+        "decode_us": t_dec, "gpx_per_s": F * W * H / t_dec[0] / 1e3,
+        "host_route_s": min(host_s), "host_route_d2h_s": min(d2h_s), "host_threads": HOST_THREADS,
+        "device_over_host": t_dec[2] * 1e-6 / min(host_s),
+        "coefficients_equal": bool(equal), "host_coefficients_equal": bool(host_equal),
+        "bytes_equal": bool(equal and host_equal), "repeat_equal": bool(equal),
+    }
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--optimize"]
-    optimize = len(args) != len(sys.argv) - 1
-    run = measure_opt if optimize else measure
-    dst = args[0] if args else os.path.join(REPO, "profiles", "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
+    args = [a for a in sys.argv[1:] if a not in ("--optimize", "--decode")]
+    optimize, decoding = "--optimize" in sys.argv[1:], "--decode" in sys.argv[1:]
+    run = measure_dec if decoding else measure_opt if optimize else measure
+    dst = args[0] if args else os.path.join(
+        REPO, "profiles", "jfif_gpu_dec.json" if decoding else "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py" + (" --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
