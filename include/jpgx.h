@@ -255,6 +255,43 @@ int jpgx_jfif_decode_gpu(const uint8_t *d_files, size_t file_stride, const uint6
                          size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status,
                          void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* The pixel half of the way back: coefficients to interleaved RGB, entirely on the
+ * device.  The pixels are those of libjpeg's default decoder for the same coefficients and tables:
+ * the 13-bit fixed-point ("islow") inverse DCT, the triangle-filter ("fancy") chroma upsampling for
+ * 4:2:2 / 4:2:0 and the 16-bit fixed-point colour conversion -- pure int32 arithmetic that wraps,
+ * stated in DESIGN.md 4.9 and equal, byte for byte, to jpgx_pixels_host (jpgx_compat.h).
+ * d_coef, coef_frame_stride, width, height and sample_ratio mean what they mean for
+ * jpgx_jfif_decode_gpu ([3][nb][64] for sample_ratio 0, Y | Cb | Cr as JPGX_FLAG_SUBSAMPLE writes
+ * them for 1 and 2).  d_qt: [2][64] tables in zig-zag order (Y's, then the one Cb and Cr share),
+ * frame f's pair at d_qt + f * qt_frame_stride: 128 is what jpgx_jfif_decode_gpu leaves, 0 means one
+ * pair for the whole batch.  d_status may be NULL; otherwise a frame with d_status[f] != 0 is skipped
+ * and none of its output bytes are written, so that jpgx_jfif_decode_gpu -> jpgx_pixels_gpu chains
+ * on a stream with no host round trip.  Frame f's pixels: top-down rows out_pitch bytes apart at
+ * d_rgb + f * out_frame_stride, byte 0 of a pixel = R = the byte the forward path reads as plane 0;
+ * only bytes [0, 3 width) of a row are written.  Workspace: jpgx_pixels_gpu_workspace_size() bytes
+ * (0 for sample_ratio 0, d_workspace may then be NULL; the chroma sample planes otherwise, 16-byte
+ * aligned; 0 from the query for bad arguments).
+ * JPGX_EARG: null d_coef, d_qt or d_rgb; d_coef not 16-byte, d_qt not 2-byte, d_status not 4-byte,
+ * d_rgb not 8-byte aligned; nframes 0 or above 65535; a coef_frame_stride that is no multiple of 64
+ * or below a frame; qt_frame_stride in [1, 127]; out_pitch below 3 width or no multiple of 8;
+ * out_frame_stride below out_pitch * height or no multiple of 8; a needed workspace that is null or
+ * misaligned.  JPGX_ESAMPLE: sample_ratio outside 0..2.  JPGX_EGEOMETRY: width or height no multiple
+ * of the MCU.  JPGX_EWORKSPACE: workspace_bytes below the query's size.  All before the first device
+ * call.  The coefficients and tables are untrusted: they only change values, never an address.
+ * Asynchronous on `stream`, capturable, no global state, no memset; the call writes whatever it
+ * reads of the workspace. */
+size_t jpgx_pixels_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes);
+int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes,
+                    int width, int height, int sample_ratio,
+                    const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                    uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
+                    void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* The two tables exactly as the JFIF writers put them into DQT for `quality` (the divisors the
+ * forward path applied, zig-zag order): jpgx_blocks_gpu's output can be turned into pixels without
+ * writing a file.  JPGX_EQUALITY outside 1..97, JPGX_EARG for a null qt. */
+int jpgx_jfif_qt(int quality, uint16_t qt[2][64]);
+
 /* Synthetic frames, generated directly in device memory (SURVEY.md 8c generator G: byte k
  * of the buffer = splitmix64(seed + (k+1)*0x9E3779B97F4A7C15) >> 56). */
 int jpgx_gen_splitmix_gpu(uint8_t *d_dst, size_t nbytes, uint64_t seed, void *stream);

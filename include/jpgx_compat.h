@@ -219,6 +219,16 @@ int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info);
 int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap,
                    uint16_t qt[2][64], jpgx_jfif_info *info);
 
+/* The host twin of jpgx_pixels_gpu (include/jpgx.h): one frame's coefficients, in
+ * the layout jpgx_read_jfif returns, and its two zig-zag tables -> interleaved top-down RGB rows
+ * `pitch` bytes apart (only bytes [0, 3 width) of a row are written).  The same arithmetic from the
+ * same source (csrc/jx_idct.h): libjpeg's default decoder's pixels.  Runs over MCU rows on
+ * `nthreads` threads (0: one per online CPU, at most 64); the result does not depend on the thread
+ * count.  Returns 0, JPGX_EARG (null pointers, pitch < 3 width, nthreads < 0), JPGX_ESAMPLE,
+ * JPGX_EGEOMETRY, JPGX_ENOMEM. */
+int jpgx_pixels_host(const int16_t *coef, int width, int height, int sample_ratio,
+                     const uint16_t qt[2][64], uint8_t *rgb, size_t pitch, int nthreads);
+
 /* encode_bmp_to_jpeg with flags: JPGX_FLAG_SUBSAMPLE and sample_ratio 1/2 write a truly
  * subsampled JFIF (extension); otherwise exactly jpgx_encode_bmp_to_jpeg.  GPU `device`. */
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

@@ -1,0 +1,357 @@
+/*
+ * jpgx_pixels.hip -- coefficients to pixels on the device: jpgx_pixels_gpu.
+ * Dequantisation, the fixed-point inverse DCT, the chroma upsampling and the colour conversion of
+ * libjpeg's default decoder; the arithmetic is jx_idct.h's, the source the host twin
+ * (jpgx_pixels_host.cpp) compiles.  Integer VALU only.
+ *
+ *   k_px444      4:4:4, fused: coefficients in, RGB out
+ *   k_px_chroma  4:2:2 / 4:2:0: Cb and Cr to uint8 sample planes in the workspace
+ *   k_px_sub     4:2:2 / 4:2:0: Y transformed, the chroma samples read with their clamped halo
+ *                from the workspace, upsampled, converted
+ *
+ * One-wave workgroups.  A wave takes runs of 8 consecutive blocks of a block row: a block is 128
+ * contiguous bytes, so the run is one 16-byte load per lane and channel, lane = (block, 8 zig-zag
+ * positions).  The lane dequantises its 8 coefficients (its 8 table entries per table stay in its
+ * registers for all its runs) and scatters them to their natural places in LDS; pass 1 runs with
+ * lane = (block, column) in place, pass 2 with lane = (block, row), which then holds 8 samples of
+ * every channel, converts them and stages its 24 bytes in LDS, from where each pixel row of the
+ * run (192 contiguous bytes) leaves in 8-byte stores.
+ *
+ * LDS image of a channel (dwords): A(b, r, c) = 64 b + 8 (r ^ (b & 3)) + (c ^ 2 (b & 2)).
+ *   pass 1, ds_read_b32 / ds_write_b32 (32 banks, 32-lane groups; a group is 4 blocks x 8 columns of
+ *     one r): bank = 8 ((r ^ b) & 3) + (c ^ ...): the 4 blocks take the 4 different r ^ b, the 8
+ *     columns the 8 different c: no conflict;
+ *   pass 2, 2 x ds_read_b128 (64 banks, the 16-lane groups {0-3, 12-15, 20-27} ... of the hardware: two
+ *     blocks' rows 0-3 and two blocks' rows 4-7, whose r ^ (b & 3) coincide pairwise): the pair
+ *     differs in b & 2 and so reads opposite halves of the 8-dword row: no conflict.
+ * Every global index comes from the checked geometry, blockIdx and the lane: the data only ever
+ * become values.  No global state, no memset; capturable.
+ */
+#include <stdint.h>
+#include <string.h>
+
+#include "jx_hip.h"
+#include "jx_idct.h"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr uint32_t kRunsPerWave = 4;    /* a wave takes this many consecutive runs: its tables and addresses serve them
+                                           all, and a pixel row's 4 x 192 bytes are whole 128-byte lines from one wave */
+constexpr uint32_t kStageRow = 208;     /* bytes between the staged pixel rows of a run: 192 + 16, which
+                                           puts the 8 rows' first dwords on 8 different groups of 4 banks */
+
+__constant__ uint8_t kZZ[64] = JXI_ZZ_INIT;
+
+struct PxArgs {
+    const int16_t *coef;
+    unsigned long long cstride;         /* int16 elements between frames */
+    const uint16_t *qt;
+    unsigned long long qstride;         /* uint16 elements between the frames' table pairs, 0: one pair */
+    const int32_t *status;              /* NULL, or [nframes]: nonzero = skip the frame */
+    uint8_t *rgb;
+    unsigned long long pitch, ostride;
+    uint8_t *planes;                    /* workspace [nframes][2][8 cbh][8 cbw] (4:2:x) */
+    jxi_geom g;
+};
+
+union V4 {
+    uint4 v;
+    uint16_t h[8];
+};
+
+/* what a lane keeps for all its runs */
+struct Lane {
+    uint32_t b, j;                      /* lane = (block of the run, 8 zig-zag positions / column / row) */
+    uint32_t at[8];                     /* dword index in a channel's image of zig-zag position 8 j + i */
+    V4 q[2];                            /* its 8 entries of the two tables */
+    bool fast;                          /* the same for the whole wave: no entry of the frame's tables above 63, so
+                                           every |coefficient * entry| <= 2^15 * 63 < 2^21 (jxi_idct8's M24) */
+};
+
+__device__ __forceinline__ uint32_t px_at(uint32_t b, uint32_t r, uint32_t c)
+{
+    return 64u * b + 8u * (r ^ (b & 3u)) + (c ^ ((b & 2u) << 1));
+}
+
+__device__ __forceinline__ void px_lane(const PxArgs &a, uint32_t f, Lane &L)
+{
+    L.b = threadIdx.x >> 3;
+    L.j = threadIdx.x & 7u;
+    const uint16_t *qt = a.qt + (size_t)f * a.qstride;
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int i = 0; i < 8; i++) L.q[t].h[i] = qt[t * 64 + L.j * 8 + i];
+    uint32_t qor = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) qor |= (uint32_t)L.q[0].h[i] | (uint32_t)L.q[1].h[i];
+    L.fast = __all(qor < 64u);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t nat = kZZ[L.j * 8 + i];
+        L.at[i] = px_at(L.b, nat >> 3, nat & 7u);
+    }
+}
+
+/* NCH channels of a run of n <= 8 blocks: src[ch] points at the run's first block.  Leaves
+ * s[ch][0..7], the 0..255 samples of row L.j of block L.b.  img: NCH x 512 dwords of LDS. */
+template <int NCH>
+__device__ __forceinline__ void px_transform(const int16_t *const (&src)[NCH], const int (&tab)[NCH], uint32_t n,
+                                             const Lane &L, uint32_t *img, uint32_t (&s)[NCH][8])
+{
+    const bool live = L.b < n;
+    V4 in[NCH];
+    if (live) {
+#pragma unroll
+        for (int ch = 0; ch < NCH; ch++) in[ch].v = *(const uint4 *)(src[ch] + (size_t)threadIdx.x * 8);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                img[ch * 512 + L.at[i]] = jxi_dequant((int16_t)in[ch].h[i], L.q[tab[ch]].h[i]);
+    }
+    /* the 24-bit multiplier serves pass 1 where the tables are small (quality 75 and better) or, with
+     * larger entries, where every coefficient of the run is: every file that was coded from an image.
+     * Either way the same for the whole wave. */
+    bool small = L.fast;
+    if (!small) {
+        uint32_t big = 0;               /* the OR of d + 2^15: below 2^16 while every d of this lane is JXI_SMALL */
+        if (live) {
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+                for (int i = 0; i < 8; i++) big |= jxi_dequant((int16_t)in[ch].h[i], L.q[tab[ch]].h[i]) + 0x8000u;
+        }
+        small = __all(big < 0x10000u);
+    }
+    __syncthreads();
+    /* pass 1: lane = (block, column j), in place */
+    const uint32_t col = px_at(L.b, 0, L.j);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        uint32_t v[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) v[r] = img[ch * 512 + (col ^ (8u * r))];
+        if (small) jxi_idct8<1>(v, JXI_PASS1_SHIFT);
+        else jxi_idct8<0>(v, JXI_PASS1_SHIFT);
+#pragma unroll
+        for (int r = 0; r < 8; r++) img[ch * 512 + (col ^ (8u * r))] = v[r];
+    }
+    __syncthreads();
+    /* pass 2: lane = (block, row j); the halves of its row are swapped where b & 2 */
+    const uint32_t row = px_at(L.b, L.j, 0);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        const uint4 lo = *(const uint4 *)(img + ch * 512 + row), hi = *(const uint4 *)(img + ch * 512 + (row ^ 4u));
+        uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        jxi_idct8<1>(v, JXI_PASS2_SHIFT);       /* inputs inside +-2^20 whatever the data (jx_idct.h) */
+#pragma unroll
+        for (int c = 0; c < 8; c++) s[ch][c] = jxi_range(v[c]);
+    }
+    __syncthreads();                    /* the image is free: the staging buffer lies in it */
+}
+
+/* lane (b, row j) has the 8 pixels of its row: 24 bytes to the staging buffer, then pixel row r of
+ * the run, 24 n bytes at out + r * pitch, leaves in 8-byte pieces; lanes beyond the run store nothing */
+__device__ __forceinline__ void px_store(const uint32_t (&y)[8], const uint32_t (&cb)[8], const uint32_t (&cr)[8],
+                                         uint32_t n, const Lane &L, uint8_t *stage, uint8_t *out, size_t pitch)
+{
+    uint32_t px[24];
+#pragma unroll
+    for (int x = 0; x < 8; x++) jxi_rgb(y[x], cb[x], cr[x], &px[3 * x], &px[3 * x + 1], &px[3 * x + 2]);
+    uint2 *dst = (uint2 *)(stage + L.j * kStageRow + L.b * 24u);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        uint2 w;
+        w.x = px[8 * k] | px[8 * k + 1] << 8 | px[8 * k + 2] << 16 | px[8 * k + 3] << 24;
+        w.y = px[8 * k + 4] | px[8 * k + 5] << 8 | px[8 * k + 6] << 16 | px[8 * k + 7] << 24;
+        dst[k] = w;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const uint32_t piece = threadIdx.x + 64u * k, r = piece / 24u, c = piece % 24u;
+        if (c < 3u * n) *(uint2 *)(out + (size_t)r * pitch + c * 8u) = *(const uint2 *)(stage + r * kStageRow + c * 8u);
+    }
+    __syncthreads();                    /* the staging buffer is free for the next run's image */
+}
+
+__device__ __forceinline__ bool px_skip(const PxArgs &a, uint32_t f) { return a.status && a.status[f] != 0; }
+
+/* five waves per SIMD: 82 VGPRs without a spill, where the allocator left to itself takes 99 (four waves) */
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void k_px444(const PxArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t img[3 * 512];
+    const uint32_t f = blockIdx.z, by = blockIdx.y;
+    if (px_skip(a, f)) return;          /* the same for the whole workgroup */
+    Lane L;
+    px_lane(a, f, L);
+    const uint32_t nruns = (a.g.bw + 7u) / 8u;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride;
+    uint8_t *out = a.rgb + (size_t)f * a.ostride + (size_t)by * 8u * a.pitch;
+    const int tab[3] = {0, 1, 1};
+    for (uint32_t run = blockIdx.x * kRunsPerWave; run < min(nruns, (blockIdx.x + 1u) * kRunsPerWave); run++) {
+        const uint32_t n = min(8u, a.g.bw - run * 8u);
+        const size_t blk = (size_t)by * a.g.bw + (size_t)run * 8u;
+        const int16_t *const src[3] = {frame + blk * 64, frame + ((size_t)a.g.nb + blk) * 64,
+                                       frame + (2 * (size_t)a.g.nb + blk) * 64};
+        uint32_t s[3][8];
+        px_transform<3>(src, tab, n, L, img, s);
+        px_store(s[0], s[1], s[2], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch);
+    }
+}
+
+__global__ __launch_bounds__(kWave) void k_px_chroma(const PxArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t img[2 * 512];
+    const uint32_t f = blockIdx.z, by = blockIdx.y;     /* a chroma block row */
+    if (px_skip(a, f)) return;
+    Lane L;
+    px_lane(a, f, L);
+    const uint32_t nruns = (a.g.cbw + 7u) / 8u;
+    const size_t wc = (size_t)a.g.cbw * 8u, plane = wc * a.g.cbh * 8u;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride + (size_t)a.g.nb * 64;
+    uint8_t *out = a.planes + (size_t)f * 2u * plane + ((size_t)by * 8u + L.j) * wc;
+    const int tab[2] = {1, 1};
+    for (uint32_t run = blockIdx.x * kRunsPerWave; run < min(nruns, (blockIdx.x + 1u) * kRunsPerWave); run++) {
+        const uint32_t n = min(8u, a.g.cbw - run * 8u);
+        const size_t blk = (size_t)by * a.g.cbw + (size_t)run * 8u;
+        const int16_t *const src[2] = {frame + blk * 64, frame + ((size_t)a.g.nbc + blk) * 64};
+        uint32_t s[2][8];
+        px_transform<2>(src, tab, n, L, img, s);
+        if (L.b < n) {
+#pragma unroll
+            for (int ch = 0; ch < 2; ch++) {
+                uint2 w;
+                w.x = s[ch][0] | s[ch][1] << 8 | s[ch][2] << 16 | s[ch][3] << 24;
+                w.y = s[ch][4] | s[ch][5] << 8 | s[ch][6] << 16 | s[ch][7] << 24;
+                *(uint2 *)(out + ch * plane + (size_t)run * 64u + L.b * 8u) = w;
+            }
+        }
+    }
+}
+
+/* samples i0 - 1 .. i0 + 4 of a plane row, the two outer indices clamped to the row */
+__device__ __forceinline__ void px_row6(const uint8_t *row, uint32_t i0, uint32_t wc, uint32_t (&p)[6])
+{
+    const uint32_t w = *(const uint32_t *)(row + i0);   /* i0 is a multiple of 4, as are wc and the plane's base */
+    p[0] = row[i0 ? i0 - 1u : 0u];
+    p[1] = w & 255u;
+    p[2] = w >> 8 & 255u;
+    p[3] = w >> 16 & 255u;
+    p[4] = w >> 24;
+    p[5] = row[i0 + 4u < wc ? i0 + 4u : wc - 1u];
+}
+
+template <int V2>
+__global__ __launch_bounds__(kWave) void k_px_sub(const PxArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t img[512];
+    const uint32_t f = blockIdx.z, by = blockIdx.y;     /* a Y block row */
+    if (px_skip(a, f)) return;
+    Lane L;
+    px_lane(a, f, L);
+    const uint32_t nruns = (a.g.bw + 7u) / 8u;
+    const uint32_t wc = a.g.cbw * 8u, hc = a.g.cbh * 8u;
+    const size_t plane = (size_t)wc * hc;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride;
+    const uint8_t *planes = a.planes + (size_t)f * 2u * plane;
+    uint8_t *out = a.rgb + (size_t)f * a.ostride + (size_t)by * 8u * a.pitch;
+    /* the chroma rows of this lane's pixel row: the near one and, for 4:2:0, the far one, clamped */
+    const uint32_t y = by * 8u + L.j;
+    const uint32_t cy = V2 ? y >> 1 : y;
+    const uint32_t far = !V2 ? cy : (y & 1u) ? (cy + 1u < hc ? cy + 1u : cy) : (cy ? cy - 1u : 0u);
+    const int tab[1] = {0};
+    for (uint32_t run = blockIdx.x * kRunsPerWave; run < min(nruns, (blockIdx.x + 1u) * kRunsPerWave); run++) {
+        const uint32_t n = min(8u, a.g.bw - run * 8u);
+        const int16_t *const src[1] = {frame + ((size_t)by * a.g.bw + (size_t)run * 8u) * 64};
+        uint32_t s[1][8], up[2][8];
+        px_transform<1>(src, tab, n, L, img, s);
+        const uint32_t i0 = run * 32u + L.b * 4u;       /* the lane's 4 chroma samples; below wc while L.b < n */
+#pragma unroll
+        for (int ch = 0; ch < 2; ch++) {
+            uint32_t p[6] = {0, 0, 0, 0, 0, 0};
+            if (L.b < n) {
+                px_row6(planes + ch * plane + (size_t)cy * wc, i0, wc, p);
+                if (V2) {
+                    uint32_t q[6];
+                    px_row6(planes + ch * plane + (size_t)far * wc, i0, wc, q);
+#pragma unroll
+                    for (int i = 0; i < 6; i++) p[i] = jxi_vsum(p[i], q[i]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                up[ch][2 * i] = jxi_up_even(p[i + 1], p[i], V2);
+                up[ch][2 * i + 1] = jxi_up_odd(p[i + 1], p[i + 2], V2);
+            }
+        }
+        px_store(s[0], up[0], up[1], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch);
+    }
+}
+
+size_t px_workspace(const jxi_geom &g, int sample_ratio, size_t nframes)
+{
+    return sample_ratio ? nframes * 2 * (size_t)g.nbc * 64 : 0;
+}
+
+unsigned px_grid_x(uint32_t blocks_per_row)
+{
+    const uint32_t nruns = (blocks_per_row + 7u) / 8u;
+    return (nruns + kRunsPerWave - 1) / kRunsPerWave;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jpgx_pixels_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes)
+{
+    jxi_geom g;
+    if (nframes == 0 || nframes > 65535 || jxi_geometry(width, height, sample_ratio, &g)) return 0;
+    return px_workspace(g, sample_ratio, nframes);
+}
+
+int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                    int sample_ratio, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                    uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride, void *d_workspace,
+                    size_t workspace_bytes, void *stream)
+{
+    PxArgs a;
+    memset(&a, 0, sizeof a);
+    if (!d_coef || !d_qt || !d_rgb || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_rgb & 7) || nframes == 0 || nframes > 65535)
+        return JPGX_EARG;
+    const int rc = jxi_geometry(width, height, sample_ratio, &a.g);
+    if (rc) return rc;
+    const size_t per = ((size_t)a.g.nb + 2 * (size_t)a.g.nbc) * 64;
+    if (coef_frame_stride % 64 || coef_frame_stride < per) return JPGX_EARG;
+    if (qt_frame_stride != 0 && qt_frame_stride < 128) return JPGX_EARG;
+    if (out_pitch < (size_t)width * 3 || out_pitch % 8) return JPGX_EARG;
+    if (out_frame_stride < out_pitch * (size_t)height || out_frame_stride % 8) return JPGX_EARG;
+    const size_t need = px_workspace(a.g, sample_ratio, nframes);
+    if (workspace_bytes < need) return JPGX_EWORKSPACE;
+    if (need && (!d_workspace || ((uintptr_t)d_workspace & 15))) return JPGX_EARG;
+    a.coef = d_coef;
+    a.cstride = coef_frame_stride;
+    a.qt = d_qt;
+    a.qstride = qt_frame_stride;
+    a.status = d_status;
+    a.rgb = d_rgb;
+    a.pitch = out_pitch;
+    a.ostride = out_frame_stride;
+    a.planes = (uint8_t *)d_workspace;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 ygrid(px_grid_x(a.g.bw), a.g.bh, (unsigned)nframes);
+    if (sample_ratio == 0) {
+        hipLaunchKernelGGL(k_px444, ygrid, dim3(kWave), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(k_px_chroma, dim3(px_grid_x(a.g.cbw), a.g.cbh, (unsigned)nframes), dim3(kWave), 0, s, a);
+        if (sample_ratio == 2) hipLaunchKernelGGL(k_px_sub<1>, ygrid, dim3(kWave), 0, s, a);
+        else hipLaunchKernelGGL(k_px_sub<0>, ygrid, dim3(kWave), 0, s, a);
+    }
+    return jx_hip_rc(hipGetLastError());
+}
+
+}  /* extern "C" */

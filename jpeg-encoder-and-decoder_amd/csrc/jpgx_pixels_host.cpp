@@ -1,0 +1,164 @@
+/*
+ * jpgx_pixels_host.cpp -- the host twin of the pixel kernels: jpgx_pixels_host
+ * (include/jpgx_compat.h).  The arithmetic is jx_idct.h's, the source the kernels
+ * (jpgx_pixels.hip) compile; this file adds the planes and the threads.  No HIP: built with g++,
+ * as jpgx_jfif_read.cpp.
+ *
+ * Two phases, each over MCU rows on the threads: every block of Y, Cb and Cr to its 0..255
+ * samples in three planes; then, pixel row by pixel row, the chroma upsampled (4:2:2 / 4:2:0)
+ * and the colour converted.  A thread writes only its own rows, so the result does not depend on
+ * the thread count.
+ */
+#include <pthread.h>
+#include <stdlib.h>
+#include <string.h>
+#include <unistd.h>
+
+#include "../../include/jpgx_compat.h"
+#include "jx_idct.h"
+
+namespace {
+
+const uint8_t kZZ[64] = JXI_ZZ_INIT;
+
+struct Ctx {
+    const int16_t *coef;
+    const uint16_t (*qt)[64];
+    jxi_geom g;
+    uint8_t *plane[3];              /* Y: 8 bh x 8 bw, Cb / Cr: 8 cbh x 8 cbw */
+    uint8_t *rgb;
+    size_t pitch;
+};
+
+struct Job {
+    const Ctx *c;
+    int phase;
+    uint32_t m0, m1;                /* MCU rows */
+};
+
+/* one block: dequantise, columns, rows, range limit */
+void block_samples(const int16_t *coef, const uint16_t *qt, uint8_t *dst, size_t dpitch)
+{
+    uint32_t d[64], v[8];
+    for (int k = 0; k < 64; k++) d[kZZ[k]] = jxi_dequant(coef[k], qt[k]);
+    for (int c = 0; c < 8; c++) {
+        for (int r = 0; r < 8; r++) v[r] = d[r * 8 + c];
+        jxi_idct8<0>(v, JXI_PASS1_SHIFT);
+        for (int r = 0; r < 8; r++) d[r * 8 + c] = v[r];
+    }
+    for (int r = 0; r < 8; r++) {
+        jxi_idct8<0>(d + r * 8, JXI_PASS2_SHIFT);
+        for (int c = 0; c < 8; c++) dst[r * dpitch + c] = (uint8_t)jxi_range(d[r * 8 + c]);
+    }
+}
+
+void samples_rows(const Ctx &c, uint32_t m0, uint32_t m1)
+{
+    const jxi_geom &g = c.g;
+    for (int ch = 0; ch < 3; ch++) {
+        const uint32_t bw = ch ? g.cbw : g.bw, per = ch ? 1u : g.vs;
+        const int16_t *src = c.coef + (ch == 0 ? 0 : ((size_t)g.nb + (size_t)(ch - 1) * g.nbc) * 64);
+        const size_t pp = (size_t)bw * 8;
+        for (uint32_t by = m0 * per; by < m1 * per; by++)
+            for (uint32_t bx = 0; bx < bw; bx++)
+                block_samples(src + ((size_t)by * bw + bx) * 64, c.qt[ch ? 1 : 0],
+                              c.plane[ch] + (size_t)by * 8 * pp + (size_t)bx * 8, pp);
+    }
+}
+
+void pixel_rows(const Ctx &c, uint32_t m0, uint32_t m1)
+{
+    const jxi_geom &g = c.g;
+    const uint32_t W = g.bw * 8, Wc = g.cbw * 8, Hc = g.cbh * 8;
+    const int v2 = g.vs == 2;
+    for (uint32_t y = m0 * 8 * g.vs; y < m1 * 8 * g.vs; y++) {
+        const uint8_t *yrow = c.plane[0] + (size_t)y * W;
+        uint8_t *out = c.rgb + (size_t)y * c.pitch;
+        const uint32_t cy = y / g.vs;
+        const uint32_t far = !v2 ? cy : (y & 1u) ? (cy + 1 < Hc ? cy + 1 : cy) : (cy ? cy - 1 : 0);
+        const uint8_t *n1 = c.plane[1] + (size_t)cy * Wc, *f1 = c.plane[1] + (size_t)far * Wc;
+        const uint8_t *n2 = c.plane[2] + (size_t)cy * Wc, *f2 = c.plane[2] + (size_t)far * Wc;
+        for (uint32_t x = 0; x < W; x++) {
+            uint32_t cb, cr, r, gg, b;
+            if (g.hs == 1) {
+                cb = n1[x];
+                cr = n2[x];
+            } else {
+                const uint32_t i = x >> 1;
+                const uint32_t j = (x & 1u) ? (i + 1 < Wc ? i + 1 : i) : (i ? i - 1 : 0);   /* clamped to the plane */
+                if (v2) {
+                    const uint32_t sc1 = jxi_vsum(n1[i], f1[i]), sn1 = jxi_vsum(n1[j], f1[j]);
+                    const uint32_t sc2 = jxi_vsum(n2[i], f2[i]), sn2 = jxi_vsum(n2[j], f2[j]);
+                    cb = (x & 1u) ? jxi_up_odd(sc1, sn1, 1) : jxi_up_even(sc1, sn1, 1);
+                    cr = (x & 1u) ? jxi_up_odd(sc2, sn2, 1) : jxi_up_even(sc2, sn2, 1);
+                } else {
+                    cb = (x & 1u) ? jxi_up_odd(n1[i], n1[j], 0) : jxi_up_even(n1[i], n1[j], 0);
+                    cr = (x & 1u) ? jxi_up_odd(n2[i], n2[j], 0) : jxi_up_even(n2[i], n2[j], 0);
+                }
+            }
+            jxi_rgb(yrow[x], cb, cr, &r, &gg, &b);
+            out[3 * x] = (uint8_t)r;
+            out[3 * x + 1] = (uint8_t)gg;
+            out[3 * x + 2] = (uint8_t)b;
+        }
+    }
+}
+
+void *run(void *arg)
+{
+    const Job *j = (const Job *)arg;
+    if (j->phase == 0) samples_rows(*j->c, j->m0, j->m1);
+    else pixel_rows(*j->c, j->m0, j->m1);
+    return NULL;
+}
+
+void run_phase(const Ctx &c, int phase, uint32_t nt)
+{
+    const uint32_t mrows = c.g.cbh;     /* MCU rows: a chroma block row each */
+    Job jobs[64];
+    pthread_t th[64];
+    bool started[64];
+    for (uint32_t t = 0; t < nt; t++) {
+        Job &j = jobs[t];
+        j.c = &c;
+        j.phase = phase;
+        j.m0 = (uint32_t)((uint64_t)mrows * t / nt);
+        j.m1 = (uint32_t)((uint64_t)mrows * (t + 1) / nt);
+        /* the last run on this thread; a thread that does not start is run here as well */
+        started[t] = t + 1 < nt && pthread_create(&th[t], NULL, run, &j) == 0;
+        if (!started[t]) run(&j);
+    }
+    for (uint32_t t = 0; t < nt; t++)
+        if (started[t]) pthread_join(th[t], NULL);
+}
+
+}  // namespace
+
+extern "C" int jpgx_pixels_host(const int16_t *coef, int width, int height, int sample_ratio, const uint16_t qt[2][64],
+                                uint8_t *rgb, size_t pitch, int nthreads)
+{
+    if (!coef || !qt || !rgb || nthreads < 0) return JPGX_EARG;
+    Ctx c;
+    memset(&c, 0, sizeof c);
+    const int rc = jxi_geometry(width, height, sample_ratio, &c.g);
+    if (rc) return rc;
+    if (pitch < (size_t)width * 3) return JPGX_EARG;
+    const size_t ny = (size_t)c.g.nb * 64, nc = (size_t)c.g.nbc * 64;
+    uint8_t *planes = (uint8_t *)malloc(ny + 2 * nc);
+    if (!planes) return JPGX_ENOMEM;
+    c.coef = coef;
+    c.qt = qt;
+    c.plane[0] = planes;
+    c.plane[1] = planes + ny;
+    c.plane[2] = planes + ny + nc;
+    c.rgb = rgb;
+    c.pitch = pitch;
+    long ncpu = nthreads ? nthreads : sysconf(_SC_NPROCESSORS_ONLN);
+    if (ncpu < 1) ncpu = 1;
+    if (ncpu > 64) ncpu = 64;
+    const uint32_t nt = (uint32_t)ncpu < c.g.cbh ? (uint32_t)ncpu : c.g.cbh;
+    run_phase(c, 0, nt);            /* joined: every plane is whole before a pixel row reads its neighbours */
+    run_phase(c, 1, nt);
+    free(planes);
+    return JPGX_OK;
+}

@@ -250,6 +250,23 @@ int jx_jfif_optimal(const uint64_t counts[256], uint8_t bits[16], uint8_t vals[2
     return n;
 }
 
+/* the two DQT tables of `quality`, zig-zag order: the divisors applied (include/jpgx.h) */
+int jpgx_jfif_qt(int quality, uint16_t qt[2][64])
+{
+    int qs[2][8][8];
+    static const int scan[8][8] = JX_SCAN_ORDER_INIT;
+    if (!qt) return JPGX_EARG;
+    if (jpgx_scale_table(0, quality, qs[0]) || jpgx_scale_table(1, quality, qs[1])) return JPGX_EQUALITY;
+    for (int t = 0; t < 2; t++)
+        for (int v = 0; v < 8; v++)
+            for (int u = 0; u < 8; u++) {
+                const int q = qs[t][u][v];                 /* coefficient (row v, col u) was
+                                                              divided by Qs[u][v] */
+                qt[t][scan[v][u]] = (uint16_t)(q < 1 ? 1 : q);
+            }
+    return JPGX_OK;
+}
+
 /* SOI, APP0, DQT x 2, SOF, DHT x 4, DRI (ri != 0), SOS: see csrc/jpgx_internal.h */
 size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
                       uint8_t *out, size_t cap)
@@ -261,9 +278,8 @@ size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio,
                            const uint8_t bits[4][16], const uint8_t vals[4][256], uint8_t *out,
                            size_t cap, size_t *dht_at)
 {
-    int qs[2][8][8];
-    if (jpgx_scale_table(0, quality, qs[0]) || jpgx_scale_table(1, quality, qs[1])) return 0;
-    static const int scan[8][8] = JX_SCAN_ORDER_INIT;
+    uint16_t zz[2][64];
+    if (jpgx_jfif_qt(quality, zz)) return 0;
     const int hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;   /* Y sampling */
     Out o = {out, 0, cap, 0};
     put_u16(&o, 0xffd8);                                   /* SOI */
@@ -280,22 +296,15 @@ size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio,
      * the frame is extended sequential (SOF1, same Huffman coding), as libjpeg does. */
     int wide = 0;
     for (int t = 0; t < 2; t++)
-        for (int i = 0; i < 64; i++)
-            if (qs[t][i / 8][i % 8] > 255) wide = 1;
+        for (int k = 0; k < 64; k++)
+            if (zz[t][k] > 255) wide = 1;
     for (int t = 0; t < 2; t++) {
-        int zz[64];
-        for (int v = 0; v < 8; v++)
-            for (int u = 0; u < 8; u++) {
-                const int q = qs[t][u][v];                 /* coefficient (row v, col u) was
-                                                              divided by Qs[u][v] */
-                zz[scan[v][u]] = q < 1 ? 1 : q;
-            }
         put_u16(&o, 0xffdb);
         put_u16(&o, (unsigned)(2 + 1 + 64 * (wide ? 2 : 1)));
         put_byte(&o, (uint8_t)(wide << 4 | t));
         for (int k = 0; k < 64; k++) {
-            if (wide) put_u16(&o, (unsigned)zz[k]);
-            else put_byte(&o, (uint8_t)zz[k]);
+            if (wide) put_u16(&o, (unsigned)zz[t][k]);
+            else put_byte(&o, (uint8_t)zz[t][k]);
         }
     }
     put_u16(&o, wide ? 0xffc1 : 0xffc0);                   /* SOF1 / SOF0 */

@@ -10,7 +10,8 @@ Reference mapping (matthewT53/JPEG-Encoder-and-Decoder):
     default_params        <- encode_bmp_to_jpeg(quality, sample_ratio) (src/jpg_encode.c:19)
     scale_table           <- scale_table (src/quantise.c:74-86)
 No counterpart in the reference (its decoder is an empty header): jfif_decode_gpu,
-decode_jpeg_coefficients -- baseline JFIF files back to the coefficients.
+decode_jpeg_coefficients -- baseline JFIF files back to the coefficients (DESIGN.md 4.8);
+pixels_gpu, decode_jpeg -- the coefficients to RGB, libjpeg's default decoder's pixels (4.9).
 """
 from __future__ import annotations
 
@@ -50,6 +51,7 @@ EXPORTS = [
     "jpgx_jfif_gpu_workspace_size", "jpgx_jfif_gpu",
     "jpgx_jfif_gpu_workspace_size_ex", "jpgx_jfif_gpu_ex",
     "jpgx_jfif_decode_gpu_workspace_size", "jpgx_jfif_decode_gpu",
+    "jpgx_pixels_gpu_workspace_size", "jpgx_pixels_gpu", "jpgx_jfif_qt",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -59,7 +61,7 @@ COMPAT_EXPORTS = [
     "jpgx_free", "jpgx_encode_bmp", "jpgx_jfif_bound", "jpgx_write_jfif",
     "jpgx_encode_bmp_to_jpeg", "jpgx_write_jfif_sub", "jpgx_encode_bmp_to_jpeg_ex",
     "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex", "jpgx_write_jfif_opt",
-    "jpgx_jfif_info_of", "jpgx_read_jfif",
+    "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_pixels_host",
 ]
 
 
@@ -132,6 +134,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_decode_gpu_workspace_size.argtypes = [i, i, i, sz, sz]
     L.jpgx_jfif_decode_gpu_workspace_size.restype = sz
     L.jpgx_jfif_decode_gpu.argtypes = [vp, sz, vp, sz, i, i, i, vp, sz, vp, vp, vp, sz, vp]
+    L.jpgx_pixels_gpu_workspace_size.argtypes = [i, i, i, sz]
+    L.jpgx_pixels_gpu_workspace_size.restype = sz
+    L.jpgx_pixels_gpu.argtypes = [vp, sz, sz, i, i, i, vp, sz, vp, vp, sz, sz, vp, sz, vp]
+    L.jpgx_jfif_qt.argtypes = [i, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -455,6 +461,98 @@ def decode_jpeg_coefficients(data: bytes, device):
     out = coef[0].reshape(3, -1, 64) if info["sample_ratio"] == 0 else coef[0]
     return dict(coef=out, qt=qt[0], width=info["width"], height=info["height"],
                 sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
+
+
+def jfif_qt(quality: int) -> np.ndarray:
+    """jpgx_jfif_qt: uint16 [2][64], the two tables the JFIF writers put into DQT for `quality`
+    (the divisors the forward path applied; zig-zag order)."""
+    qt = np.zeros((2, 64), np.uint16)
+    _check(lib.jpgx_jfif_qt(quality, qt.ctypes.data), "jpgx_jfif_qt")
+    return qt
+
+
+def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None, status=None, out=None,
+               pitch: int | None = None, stream=None):
+    """The pixels of a batch of coefficient frames (jpgx_pixels_gpu): d_coef int16
+    [nframes][...] as jfif_decode_gpu returns it (each frame contiguous, frames d_coef.stride(0)
+    elements apart), d_qt uint16 [nframes][2][64] (one pair per frame) or [2][64] (one for the batch),
+    status int32 [nframes] or None: a frame with a nonzero status is skipped, its output untouched.
+    Returns uint8 [nframes][H][W][3] on the device: a fresh tensor, or, with a pitch (bytes between
+    pixel rows, a multiple of 8, at least 3 W), a view of the padded buffer; out: a contiguous uint8
+    buffer of nframes * H * pitch bytes to use instead of a fresh one.  Nothing is copied to the host
+    and nothing waits."""
+    import torch
+    if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda or d_coef.dtype != torch.int16 or d_coef.dim() < 2:
+        raise ValueError("pixels_gpu: d_coef must be an int16 [nframes][...] device tensor")
+    if not isinstance(d_qt, torch.Tensor) or not d_qt.is_cuda or d_qt.dtype != torch.uint16 or not d_qt.is_contiguous():
+        raise ValueError("pixels_gpu: d_qt must be a contiguous uint16 device tensor")
+    if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
+        raise ValueError("pixels_gpu: bad geometry or sample_ratio")
+    nf = int(d_coef.shape[0])
+    nb = (width // 8) * (height // 8)
+    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, FLAG_SUBSAMPLE if sample_ratio else 0)
+    per = (nb + 2 * nbc) * 64
+    if not d_coef[0].is_contiguous() or d_coef[0].numel() < per:
+        raise ValueError("pixels_gpu: each frame must be contiguous and hold nb + 2 nbc blocks")
+    cstride = int(d_coef.stride(0)) if nf > 1 else int(d_coef[0].numel())
+    if d_qt.numel() == 128:
+        qstride = 0
+    elif d_qt.numel() == 128 * nf:
+        qstride = 128
+    else:
+        raise ValueError("pixels_gpu: d_qt must be [2][64] or [nframes][2][64]")
+    if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.int32
+                               or status.numel() != nf or not status.is_contiguous()):
+        raise ValueError("pixels_gpu: status must be a contiguous int32 [nframes] tensor")
+    pitch = 3 * width if pitch is None else int(pitch)
+    if pitch < 3 * width or pitch % 8:
+        raise ValueError("pixels_gpu: pitch must be a multiple of 8 and at least 3 * width")
+    dev = d_coef.device
+    if out is None:
+        out = torch.empty(nf * height * pitch, dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.numel() != nf * height * pitch):
+        raise ValueError("pixels_gpu: out must be a contiguous uint8 buffer of nframes * H * pitch bytes")
+    need = int(lib.jpgx_pixels_gpu_workspace_size(width, height, sample_ratio, nf))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _check(lib.jpgx_pixels_gpu(d_coef.data_ptr(), cstride, nf, width, height, sample_ratio, d_qt.data_ptr(), qstride,
+                               status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
+                               height * pitch, ws.data_ptr() if need else None, need, _stream_ptr(stream)),
+           "jpgx_pixels_gpu")
+    if stream is not None:
+        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
+    return out.view(nf, height, pitch)[:, :, :3 * width].unflatten(2, (width, 3))
+
+
+def decode_jpeg(data, device):
+    """Baseline JFIF file(s) in host memory -> RGB on `device`: decode_jpeg_coefficients' header step
+    on the host for the geometry, one host-to-device copy of the bytes, then jfif_decode_gpu and
+    pixels_gpu on one stream; the coefficients never leave the device.  data: bytes -> uint8 [H][W][3];
+    a list of files of one geometry -> [n][H][W][3].  The pixels are libjpeg's default decoder's.
+    Raises JpgxError for a frame whose status is nonzero (that reads the statuses back, a
+    synchronisation)."""
+    import torch
+    from . import compat
+    single = isinstance(data, (bytes, bytearray, memoryview))
+    files = [bytes(data)] if single else [bytes(d) for d in data]
+    if not files:
+        raise ValueError("decode_jpeg: no files")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("decode_jpeg: device must be a GPU")
+    info = compat.jfif_info(files[0])
+    W, H, sr = info["width"], info["height"], info["sample_ratio"]
+    cap = max(len(f) for f in files)
+    host = np.zeros((len(files), cap), np.uint8)
+    for k, f in enumerate(files):
+        host[k, :len(f)] = np.frombuffer(f, np.uint8)
+    d_files = torch.from_numpy(host).to(dev)
+    lens = torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
+    coef, qt, status = jfif_decode_gpu(d_files, lens, W, H, sr)
+    rgb = pixels_gpu(coef, W, H, sr, d_qt=qt, status=status)
+    for rc in status.cpu().tolist():
+        _check(int(rc), "jpgx_jfif_decode_gpu")
+    return rgb[0] if single else rgb
 
 
 def split_sub(out, nb: int, nbc: int):

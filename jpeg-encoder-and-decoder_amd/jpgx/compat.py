@@ -103,6 +103,7 @@ def _setup(L):
 
     L.jpgx_jfif_info_of.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(JfifInfo)]
     L.jpgx_read_jfif.argtypes = [vp, ctypes.c_size_t, i, vp, ctypes.c_size_t, vp, ctypes.POINTER(JfifInfo)]
+    L.jpgx_pixels_host.argtypes = [vp, i, i, i, vp, vp, ctypes.c_size_t, i]
 
 
 _setup(lib)
@@ -319,6 +320,24 @@ def read_jfif(data, nthreads: int = 1) -> dict:
         coef = coef.reshape(3, info["nb_y"], 64)
     return dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
                 sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
+
+
+def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt: np.ndarray,
+                nthreads: int = 0, pitch: int | None = None) -> np.ndarray:
+    """jpgx_pixels_host: one frame's coefficients (read_jfif's layout) and its uint16 [2][64] zig-zag
+    tables -> uint8 [H][W][3], libjpeg's default decoder's pixels, on `nthreads`
+    threads (0: one per CPU).  pitch: bytes between pixel rows of the buffer the result is a view of."""
+    coef = np.ascontiguousarray(coef, np.int16)
+    qt = np.ascontiguousarray(qt, np.uint16)
+    nb = (width // 8) * (height // 8)
+    nbc = (nb, nb // 2, nb // 4)[sample_ratio] if sample_ratio in (0, 1, 2) else nb
+    if qt.shape != (2, 64) or width <= 0 or height <= 0 or coef.size < (nb + 2 * nbc) * 64:
+        raise ValueError("pixels_host: qt [2][64], and coef must hold nb + 2 nbc blocks")
+    pitch = 3 * width if pitch is None else int(pitch)
+    buf = np.empty((height, max(pitch, 1)), np.uint8)
+    _check(lib.jpgx_pixels_host(coef.ctypes.data, width, height, sample_ratio, qt.ctypes.data, buf.ctypes.data,
+                                pitch, nthreads), "jpgx_pixels_host")
+    return buf[:, :3 * width].reshape(height, width, 3)
 
 
 def encode_bmp_to_jpeg_ex(src: str, dst: str, quality: int, sample_ratio: int, flags: int,

@@ -30,7 +30,18 @@ coder writes from the same coefficients and writes profiles/jfif_gpu_dec.json; p
   device_over_host   decode time (median) / host_route_s: above 1, the host route is the faster one
   intervals       restart intervals of the batch = the lanes that work
   coefficients_equal   every frame's status 0 and its coefficients == the ones that were coded
-Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode] [OUT.json]"""
+With --pixels the run times the pixel half of the way back (jpgx_pixels_gpu) on the
+transform's own coefficients with jpgx_jfif_qt's tables and writes profiles/jfif_gpu_px.json; per
+input and sample mode (4:4:4, and true 4:2:2 / 4:2:0 from JPGX_FLAG_SUBSAMPLE):
+  pixels_us       jpgx_pixels_gpu per batch (events, as above; all rounds, sorted); for 4:2:x both launches
+  bytes_per_px, fraction_of_8TBps   9 / 7 / 6 B per pixel (int16 coefficients in, RGB out) over the
+                  minimum time, as a fraction of 8 TB/s
+  xform_us, xform_fraction_of_8TBps   the forward transform kernel (k_mxs for 4:4:4) on the same box,
+                  same protocol, same bytes per pixel in the other direction
+  host_route_s    the route without it: the coefficients copied to pinned host memory +
+                  jpgx_pixels_host on 16 threads, frame after frame; best of 2 (host_route_d2h_s: the copy)
+  pixels_equal    every frame == jpgx_pixels_host, before and after the timed calls
+Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode | --pixels] [OUT.json]"""
 import json
 import os
 import sys
@@ -274,15 +285,88 @@ def measure_dec(name, d_rgb, dev):
     }
 
 
+def measure_px(name, d_rgb, dev):
+    nb = (W // 8) * (H // 8)
+    qt_host = jpgx.jfif_qt(Q)
+    d_qt = torch.from_numpy(qt_host.view(np.int16)).to(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"input": name, "modes": []}
+    for sr in (0, 1, 2):
+        flags = jpgx.FLAG_SUBSAMPLE if sr else 0
+        nbc = jpgx.chroma_blocks(W, 0, H // 8, sr, flags)
+        per = (nb + 2 * nbc) * 64
+        coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+        fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+        p = jpgx.default_params(W, H, Q, sr, flags=flags)
+        xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+
+        def xform():
+            jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+
+        xform()
+        torch.cuda.synchronize()
+        rgb = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        wsb = int(jpgx.lib.jpgx_pixels_gpu_workspace_size(W, H, sr, F))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+
+        def pixels():
+            rc = jpgx.lib.jpgx_pixels_gpu(coef.data_ptr(), per, F, W, H, sr, d_qt.data_ptr(), 0, None, rgb.data_ptr(),
+                                          3 * W, 3 * W * H, ws.data_ptr() if wsb else None, wsb, stream)
+            assert rc == 0, rc
+
+        # the host route, which is also the check
+        pinned = torch.empty((F, per), dtype=torch.int16).pin_memory()
+        want = np.empty((F, H, W, 3), np.uint8)
+        host_s, d2h_s = [], []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pinned.copy_(coef)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for f in range(F):                           # the library itself on the pinned coefficients
+                rc = jpgx.lib.jpgx_pixels_host(pinned.data_ptr() + f * per * 2, W, H, sr, qt_host.ctypes.data,
+                                               want[f].ctypes.data, 3 * W, HOST_THREADS)
+                assert rc == 0, rc
+            t2 = time.perf_counter()
+            d2h_s.append(t1 - t0)
+            host_s.append(t2 - t0)
+        d_want = torch.from_numpy(want).to(dev)
+        rgb.fill_(0)
+        pixels()
+        torch.cuda.synchronize()
+        equal = bool(torch.equal(rgb, d_want))
+        t_px = timed(pixels)
+        repeat = bool(torch.equal(rgb, d_want))
+        t_xform = timed(xform)
+        bpp = (9, 7, 6)[sr]
+        nbytes = F * W * H * bpp
+        res["modes"].append({
+            "sample_ratio": sr, "bytes_per_px": bpp, "pixels_us": t_px, "xform_us": t_xform,
+            "fraction_of_8TBps": nbytes / (t_px[0] * 1e-6) / 8e12,
+            "xform_fraction_of_8TBps": nbytes / (t_xform[0] * 1e-6) / 8e12,
+            "gpx_per_s": F * W * H / t_px[0] / 1e3,
+            "host_route_s": min(host_s), "host_route_d2h_s": min(d2h_s), "host_threads": HOST_THREADS,
+            "speedup": min(host_s) / (t_px[2] * 1e-6),
+            "pixels_equal": equal, "repeat_equal": repeat,
+        })
+        del coef, rgb, ws, d_want, pinned
+    res["bytes_equal"] = all(m["pixels_equal"] for m in res["modes"])
+    res["repeat_equal"] = all(m["repeat_equal"] for m in res["modes"])
+    return res
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--optimize", "--decode")]
-    optimize, decoding = "--optimize" in sys.argv[1:], "--decode" in sys.argv[1:]
-    run = measure_dec if decoding else measure_opt if optimize else measure
+    modes = ("--optimize", "--decode", "--pixels")
+    args = [a for a in sys.argv[1:] if a not in modes]
+    optimize, decoding, pixels = (m in sys.argv[1:] for m in modes)
+    run = measure_px if pixels else measure_dec if decoding else measure_opt if optimize else measure
     dst = args[0] if args else os.path.join(
-        REPO, "profiles", "jfif_gpu_dec.json" if decoding else "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
+        REPO, "profiles", "jfif_gpu_px.json" if pixels else "jfif_gpu_dec.json" if decoding else
+        "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py" + (" --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --pixels" if pixels else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
