@@ -130,16 +130,20 @@ long long jx_mx_image(int sr, int force, int quality, void *dst, long long cap);
 /* the second implementation's launcher (jpgx_kernels.hip, libjpgx_alt.so only): k_xform, and for
  * sr 1 / 2 k_chroma<sr> over the nbc chroma blocks of each frame */
 int jx_launch_alt(const struct jx_xform_args *xa, int sr, size_t nbc, void *stream, void *ev_start, void *ev_stop);
-/* the JFIF writer's tables and header bytes (host/jpgx_jfif.c), shared by jpgx_write_jfif_ex and
- * the device coder (csrc/jpgx_jfif.hip).
- * jx_jfif_codes: the canonical Huffman codes of the Annex K.3 tables (T.81 Annex C) indexed by
- * symbol, packed code << 8 | length; cl[0] DC luminance, cl[1] AC luminance, cl[2] DC chrominance,
- * cl[3] AC chrominance.
+/* the JFIF writer's tables and header bytes (host/jpgx_jfif.c), shared by the host scan writer
+ * (csrc/jpgx_jfif_write.cpp: jpgx_write_jfif_opt and the entry points before it) and the device
+ * coder (csrc/jpgx_jfif.hip).  What the two code with them -- a block's symbols, the clamps, the
+ * scan order -- is csrc/jx_jfif_enc.h, included by both.
+ * jx_jfif_build_codes: the canonical Huffman codes (T.81 Annex C) of the table bits[16] / vals,
+ * indexed by symbol, packed code << 8 | length (0: the table has no such symbol).
+ * jx_jfif_codes: the same for the Annex K.3 tables; cl[0] DC luminance, cl[1] AC luminance, cl[2] DC
+ * chrominance, cl[3] AC chrominance.
  * jx_jfif_header: SOI .. SOS for a width x height frame of `quality`, Y sampled hs x vs by
  * sample_ratio (0: 1x1, 1: 2x1, 2: 2x2), with a DRI segment of `ri` MCUs when ri != 0.  Writes
  * the first `cap` of them into out and returns their number (at most JX_JFIF_HDR_MAX; 0 when
  * the quality is outside 1..97). */
 #define JX_JFIF_HDR_MAX 768
+void jx_jfif_build_codes(const uint8_t bits[16], const uint8_t *vals, uint32_t cl[256]);
 void jx_jfif_codes(uint32_t cl[4][256]);
 size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
                       uint8_t *out, size_t cap);

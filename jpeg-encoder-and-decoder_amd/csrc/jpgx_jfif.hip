@@ -1,7 +1,9 @@
 /*
  * jpgx_jfif.hip -- the JFIF writer's scan on the device: the bytes of
- * jpgx_write_jfif_ex (host/jpgx_jfif.c) with restart intervals, for a batch of frames whose
- * coefficients are in device memory.
+ * jpgx_write_jfif_ex (csrc/jpgx_jfif_write.cpp) with restart intervals, for a batch of frames whose
+ * coefficients are in device memory.  A block's symbols, the clamps, the scan's geometry and its
+ * block order are jx_jfif_enc.h's, the routines the host writer runs; the kernels bring their own
+ * sinks for the symbols (BitCount, BitPack, SymCount).
  *
  * A restart interval is self-contained (DC predictors reset, byte aligned), so one workgroup
  * codes one interval, its lanes looping over the interval's blocks in scan order (MCU by MCU:
@@ -18,15 +20,15 @@
  *               RSTm markers), the frame's length or its overflow report, headers and EOI
  *   k_jf_stuff  per interval: unstuffed bytes -> file bytes with 0xFF 0x00 stuffing, RSTm
  * A lane keeps its block in LDS (its own 33-dword row: conflict-free when the lanes of a wave read
- * the same coefficient) and walks only the nonzero coefficients (a 64-bit mask, ctz), as the host
- * writer does.  The code tables and the header bytes come from the host writer's own functions
+ * the same coefficient) and walks only the nonzero coefficients (a 64-bit mask, ctz: jxe_walk).
+ * The code tables and the header bytes come from the host writer's own functions
  * (jx_jfif_codes, jx_jfif_header) as by-value kernel arguments: nothing is copied with a memcpy,
  * the call is asynchronous, capturable and keeps no state.
  *
  * With JPGX_JFIF_OPTIMIZE (jpgx_jfif_gpu_ex; the bytes of jpgx_write_jfif_opt) every frame gets
  * Huffman tables of its own, and three launches come first:
  *   k_jf_zero   the frame's symbol counts to zero
- *   k_jf_count  k_jf_len's walk, counting the symbols instead of their bits
+ *   k_jf_count  k_jf_len's walk with a sink that counts the symbols instead of their bits
  *   k_jf_tables per table: T.81 Annex K.2 exactly as jx_jfif_optimal (host/jpgx_jfif.c) -> the
  *               frame's code tables, DHT segments and their lengths in the workspace
  * k_jf_len, k_jf_pack and k_jf_frame are templates over where tables and header come from: the
@@ -37,6 +39,7 @@
 
 #include "jpgx_internal.h"
 #include "jx_hip.h"
+#include "jx_jfif_enc.h"
 
 namespace {
 
@@ -55,10 +58,8 @@ constexpr int kHdrSuf = 32;             /* DRI, SOS: 6 + 14 bytes */
 struct JfArgs {
     const int16_t *coef;                /* frame f: Y [nb][64] | Cb [nbc][64] | Cr [nbc][64] at f fstride */
     unsigned long long fstride;         /* int16 elements */
-    uint32_t hs, lum, bpm;              /* Y blocks per MCU row of blocks, per MCU; blocks per MCU */
-    uint32_t vs, bpr, cpr, mrows;       /* Y blocks per row, MCUs per row, MCU rows */
+    jxe_geom g;
     uint32_t rpi, ni;                   /* MCU rows per interval, intervals per frame */
-    uint32_t nb, nbc, nblkf;            /* blocks: Y, per chroma plane, per frame */
     uint32_t ivblk;                     /* blocks of a full interval */
     uint32_t hdrlen;
     uint32_t *offs;                     /* [nframes][nblkf] bit offset within the interval (scan order) */
@@ -104,41 +105,35 @@ struct JfHdrOpt {
     }
 };
 
-/* block (MCU m of interval iv, position j in the MCU) in the frame's coefficient array */
-__device__ __forceinline__ size_t jf_block(const JfArgs &a, uint32_t iv, uint32_t m, uint32_t j)
-{
-    const uint32_t mr = m / a.cpr, mx = m - mr * a.cpr, my = iv * a.rpi + mr;
-    if (j < a.lum) {
-        const uint32_t dy = j / a.hs, dx = j - dy * a.hs;
-        return (size_t)(my * a.vs + dy) * a.bpr + mx * a.hs + dx;
-    }
-    return (size_t)a.nb + (size_t)(j - a.lum) * a.nbc + (size_t)my * a.cpr + mx;
-}
-
 /* the interval's block count */
 __device__ __forceinline__ uint32_t jf_nblk(const JfArgs &a, uint32_t iv)
 {
     const uint32_t r0 = iv * a.rpi;
-    const uint32_t rows = min(a.rpi, a.mrows - r0);
-    return rows * a.cpr * a.bpm;
+    const uint32_t rows = min(a.rpi, a.g.mrows - r0);
+    return rows * a.g.cpr * a.g.bpm;
 }
 
 typedef uint32_t jf_u4 __attribute__((ext_vector_type(4)));
 
 /* scan-order block i of interval iv of frame f into this lane's LDS row; returns the mask of its
- * nonzero coefficients, the DC difference (clamped as the host writer clamps it) and whether it is
- * a chroma block */
+ * nonzero coefficients, the DC difference (jxe_dc_diff) and whether it is a chroma block */
 __device__ __forceinline__ uint64_t jf_load(const JfArgs &a, uint32_t f, uint32_t iv, uint32_t i, uint32_t *row,
                                             int &diff, uint32_t &chroma)
 {
-    const uint32_t m = i / a.bpm, j = i - m * a.bpm;
+    const jxe_geom &g = a.g;
+    const uint32_t m = i / g.bpm, j = i - m * g.bpm;
     const int16_t *base = a.coef + (size_t)f * a.fstride;
-    const int16_t *z = base + jf_block(a, iv, m, j) * 64;
+    /* position jj of the interval's MCU mm in the frame's coefficient array */
+    const auto at = [&](uint32_t mm, uint32_t jj) {
+        const uint32_t mr = mm / g.cpr;
+        return jxe_block(g, iv * a.rpi + mr, mm - mr * g.cpr, jj) * 64;
+    };
+    const int16_t *z = base + at(m, j);
     /* the previous block of the same component: the luma block before it in the MCU, else the
      * previous MCU's last luma block / same chroma block; none at the interval's first MCU */
     int pred = 0;
-    if (j > 0 && j < a.lum) pred = base[jf_block(a, iv, m, j - 1) * 64];
-    else if (m > 0) pred = base[jf_block(a, iv, m - 1, j == 0 ? a.lum - 1 : j) * 64];
+    if (j > 0 && j < g.lum) pred = base[at(m, j - 1)];
+    else if (m > 0) pred = base[at(m - 1, j == 0 ? g.lum - 1 : j)];
     uint64_t nz = 0;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
@@ -153,27 +148,29 @@ __device__ __forceinline__ uint64_t jf_load(const JfArgs &a, uint32_t f, uint32_
             nz |= two << (8 * r + 2 * e);
         }
     }
-    int d = (int)(int16_t)(row[0] & 0xffffu) - pred;
-    d = d > 2047 ? 2047 : d;
-    d = d < -2047 ? -2047 : d;
-    diff = d;
-    chroma = j >= a.lum ? 1u : 0u;
+    diff = jxe_dc_diff((int)(int16_t)(row[0] & 0xffffu), pred);
+    chroma = j >= g.lum ? 1u : 0u;
     return nz & ~1ull;
 }
 
-/* magnitude category and the value's additional bits (T.81 F.1.2.1) */
-__device__ __forceinline__ uint32_t jf_category(int v, uint32_t &extra)
-{
-    const uint32_t a = (uint32_t)(v < 0 ? -v : v);
-    const uint32_t s = a ? 32u - (uint32_t)__builtin_clz(a) : 0u;
-    extra = (uint32_t)(v < 0 ? v + (1 << s) - 1 : v) & ((1u << s) - 1u);
-    return s;
-}
+/* jxe_walk's view of a lane's block: its LDS row of packed pairs */
+struct JfRow {
+    const uint32_t *row;
+    __device__ __forceinline__ uint32_t fetch(uint32_t k) const { return row[k >> 1]; }
+    __device__ __forceinline__ int value(uint32_t word, uint32_t k) const
+    {
+        return (k & 1u) ? (int)word >> 16 : (int)(int16_t)(word & 0xffffu);
+    }
+};
+
+/* jxe_walk's sinks on the device hold the block's two code tables in LDS (code << 8 | length) */
 
 /* counts bits */
 struct BitCount {
+    const uint32_t *dct, *act;
     uint32_t n;
-    __device__ __forceinline__ void put(uint32_t, uint32_t nb) { n += nb; }
+    __device__ __forceinline__ void dc(uint32_t s, uint32_t) { n += (dct[s] & 0xffu) + s; }
+    __device__ __forceinline__ void ac(uint32_t sym, uint32_t s, uint32_t) { n += (act[sym] & 0xffu) + s; }
 };
 
 /* writes bits MSB first from a bit offset.  The words a block covers whole are its own (plain
@@ -184,6 +181,7 @@ struct BitCount {
  * (eight and more blocks share a word).  Only the last lane's last word
  * has no slot: it is shared with the next pass and goes to memory with an atomicOr. */
 struct BitPack {
+    const uint32_t *dct, *act;
     uint32_t *wp;
     uint32_t *slots;                    /* the workgroup's LDS slots */
     uint32_t head, tail;                /* slots of the first and the last word; tail ~0: none */
@@ -214,6 +212,9 @@ struct BitPack {
             wp++;
         }
     }
+    __device__ __forceinline__ void code(uint32_t c, uint32_t s, uint32_t extra) { put((c >> 8) << s | extra, (c & 0xffu) + s); }
+    __device__ __forceinline__ void dc(uint32_t s, uint32_t extra) { code(dct[s], s, extra); }
+    __device__ __forceinline__ void ac(uint32_t sym, uint32_t s, uint32_t extra) { code(act[sym], s, extra); }
     __device__ __forceinline__ void close()
     {
         if (!nacc) return;
@@ -224,43 +225,12 @@ struct BitPack {
     }
 };
 
-/* one block's Huffman-coded data (T.81 F.1.2), as encode_block of host/jpgx_jfif.c */
-template <class W>
-__device__ __forceinline__ void jf_code(W &w, const uint32_t *row, uint64_t nz, int diff, const uint32_t *dc,
-                                        const uint32_t *ac)
-{
-    uint32_t extra;
-    uint32_t s = jf_category(diff, extra);
-    uint32_t c = dc[s];
-    w.put((c >> 8) << s | extra, (c & 0xffu) + s);
-    uint32_t prev = 0;
-    uint32_t k = nz ? (uint32_t)__builtin_ctzll(nz) : 0u;
-    uint32_t word = row[k >> 1];
-    while (nz) {                        /* one code per turn: a ZRL while the run exceeds 15 */
-        const uint32_t run = k - prev - 1u;
-        const bool zrl = run > 15u;
-        /* the next turn's coefficient is read under this turn's table lookup */
-        const uint64_t nzn = zrl ? nz : nz & (nz - 1);
-        const uint32_t kn = nzn ? (uint32_t)__builtin_ctzll(nzn) : 0u;
-        const uint32_t wordn = row[kn >> 1];
-        int v = (k & 1u) ? (int)word >> 16 : (int)(int16_t)(word & 0xffffu);
-        v = v > 1023 ? 1023 : v;
-        v = v < -1023 ? -1023 : v;
-        s = jf_category(v, extra);
-        c = ac[zrl ? 0xf0u : (run << 4 | s)];
-        s = zrl ? 0u : s;
-        extra = zrl ? 0u : extra;
-        prev = zrl ? prev + 16u : k;
-        nz = nzn;
-        k = kn;
-        word = wordn;
-        w.put((c >> 8) << s | extra, (c & 0xffu) + s);
-    }
-    if (prev < 63u) {
-        c = ac[0x00];
-        w.put(c >> 8, c & 0xffu);
-    }
-}
+/* adds 1 to the symbol's bin of the workgroup's LDS histogram */
+struct SymCount {
+    uint32_t *dct, *act;
+    __device__ __forceinline__ void dc(uint32_t s, uint32_t) { atomicAdd(dct + s, 1u); }
+    __device__ __forceinline__ void ac(uint32_t sym, uint32_t, uint32_t) { atomicAdd(act + sym, 1u); }
+};
 
 /* workgroup exclusive scan (kT threads); total = the sum.  wtot: LDS [kT / 64] */
 template <class T>
@@ -321,16 +291,17 @@ __global__ __launch_bounds__(kT) void k_jf_len(const JfArgs a, const Tabs tabs)
     const uint32_t iv = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
     jf_tabs_to_lds(tabs, dc, ac);
     const uint32_t n = jf_nblk(a, iv);
-    uint32_t *offs = a.offs + (size_t)f * a.nblkf + (size_t)iv * a.ivblk;
+    uint32_t *offs = a.offs + (size_t)f * a.g.nblkf + (size_t)iv * a.ivblk;
     uint32_t carry = 0;
     for (uint32_t i0 = 0; i0 < n; i0 += kT) {
         const uint32_t i = i0 + t;
-        BitCount w{0};
+        BitCount w{NULL, NULL, 0};
         if (i < n) {
             int diff;
             uint32_t ch;
             const uint64_t nz = jf_load(a, f, iv, i, tile + t * kRow, diff, ch);
-            jf_code(w, tile + t * kRow, nz, diff, dc[ch], ac[ch]);
+            w.dct = dc[ch], w.act = ac[ch];
+            jxe_walk(w, JfRow{tile + t * kRow}, nz, diff);
         }
         uint32_t total;
         const uint32_t ex = jf_scan(w.n, wtot, total);
@@ -376,7 +347,7 @@ __global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const Tabs tabs)
     uint8_t *area = a.ustream + (size_t)f * a.uarea + a.ustart[(size_t)f * a.ni + iv];
     for (uint32_t c = t; c < nchunk; c += kT) ((uint4 *)area)[c] = make_uint4(0, 0, 0, 0);
     __syncthreads();                    /* the interval's place is zero before any lane ORs into it */
-    const uint32_t *offs = a.offs + (size_t)f * a.nblkf + (size_t)iv * a.ivblk;
+    const uint32_t *offs = a.offs + (size_t)f * a.g.nblkf + (size_t)iv * a.ivblk;
     for (uint32_t i0 = 0; i0 < n; i0 += kT) {
         const uint32_t i = i0 + t;
         const bool live = i < n;
@@ -397,8 +368,9 @@ __global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const Tabs tabs)
             const uint64_t nz = jf_load(a, f, iv, i, tile + t * kRow, diff, ch);
             const bool last = i + 1 == n || t + 1 == kT;       /* the next block is the next pass's */
             BitPack w;
+            w.dct = dc[ch], w.act = ac[ch];
             w.open(area, off, slot, rank, last ? ~0u : rk[t + 1]);
-            jf_code(w, tile + t * kRow, nz, diff, dc[ch], ac[ch]);
+            jxe_walk(w, JfRow{tile + t * kRow}, nz, diff);
             if (i + 1 == n) {           /* the interval's end: 1-bits up to the byte boundary */
                 const uint32_t pad = (8u - (bits & 7u)) & 7u;
                 if (pad) w.put((1u << pad) - 1u, pad);
@@ -513,28 +485,6 @@ __global__ __launch_bounds__(kT) void k_jf_zero(const JfOpt o)
 
 constexpr int kBins = 2 * 16 + 2 * 256;  /* DC luma, DC chroma, AC luma, AC chroma */
 
-/* jf_code's walk, counting the symbols it codes: dc[category], ac[run << 4 | category] */
-__device__ __forceinline__ void jf_count(uint32_t *dc, uint32_t *ac, const uint32_t *row, uint64_t nz, int diff)
-{
-    uint32_t extra;
-    atomicAdd(dc + jf_category(diff, extra), 1u);
-    uint32_t prev = 0;
-    while (nz) {                        /* one symbol per turn: a ZRL while the run exceeds 15 */
-        const uint32_t k = (uint32_t)__builtin_ctzll(nz);
-        const uint32_t run = k - prev - 1u;
-        const bool zrl = run > 15u;
-        const uint32_t word = row[k >> 1];
-        int v = (k & 1u) ? (int)word >> 16 : (int)(int16_t)(word & 0xffffu);
-        v = v > 1023 ? 1023 : v;
-        v = v < -1023 ? -1023 : v;
-        const uint32_t s = jf_category(v, extra);
-        atomicAdd(ac + (zrl ? 0xf0u : (run << 4 | s)), 1u);
-        prev = zrl ? prev + 16u : k;
-        nz = zrl ? nz : nz & (nz - 1);
-    }
-    if (prev < 63u) atomicAdd(ac, 1u);
-}
-
 /* one workgroup per restart interval, as k_jf_len: the interval's symbols into LDS bins, the bins
  * into the frame's counts with 64-bit atomic adds (integer sums: the order does not show).  One
  * histogram for the workgroup: a copy per wave measured slower */
@@ -550,7 +500,8 @@ __global__ __launch_bounds__(kT) void k_jf_count(const JfArgs a, const JfOpt o)
         int diff;
         uint32_t ch;
         const uint64_t nz = jf_load(a, f, iv, i, tile + t * kRow, diff, ch);
-        jf_count(h + 16u * ch, h + 32u + 256u * ch, tile + t * kRow, nz, diff);
+        SymCount w{h + 16u * ch, h + 32u + 256u * ch};
+        jxe_walk(w, JfRow{tile + t * kRow}, nz, diff);
     }
     __syncthreads();
     unsigned long long *counts = o.counts + (size_t)f * 1024;
@@ -707,29 +658,17 @@ __global__ __launch_bounds__(kT) void k_jf_tables(const JfOpt o)
 
 size_t r16(size_t x) { return (x + 15) / 16 * 16; }
 
-/* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0 */
+/* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0.  The
+ * device codes with restart intervals only: restart_rows 0 is refused, -1 is one MCU row */
 int jf_geometry(int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
 {
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || width > 65535 || height > 65535 ||
-        sample_ratio < 0 || sample_ratio > 2 || restart_rows == 0 || restart_rows < -1 || nframes == 0 ||
-        nframes > 65535)
-        return JPGX_EARG;
-    const uint32_t hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;
-    if (width % (8 * hs) || height % (8 * vs)) return JPGX_EGEOMETRY;
-    a.hs = hs;
-    a.vs = vs;
-    a.lum = hs * vs;
-    a.bpm = a.lum + 2;
-    a.bpr = (uint32_t)width / 8;
-    a.cpr = a.bpr / hs;
-    a.mrows = (uint32_t)height / 8 / vs;
-    a.nb = a.bpr * ((uint32_t)height / 8);
-    a.nbc = a.cpr * a.mrows;
-    a.nblkf = a.nb + 2 * a.nbc;
+    if (restart_rows == 0 || restart_rows < -1 || nframes == 0 || nframes > 65535) return JPGX_EARG;
+    const int rc = jxe_geometry(width, height, sample_ratio, &a.g);
+    if (rc) return rc;
     a.rpi = restart_rows > 0 ? (uint32_t)restart_rows : 1u;
-    if (a.rpi > 65535u / a.cpr) return JPGX_EARG;             /* Ri is a 16-bit field */
-    a.ni = (a.mrows + a.rpi - 1) / a.rpi;
-    a.ivblk = a.rpi * a.cpr * a.bpm;
+    if (a.rpi > jxe_max_rows(&a.g)) return JPGX_EARG;
+    a.ni = (a.g.mrows + a.rpi - 1) / a.rpi;
+    a.ivblk = a.rpi * a.g.cpr * a.g.bpm;
     return JPGX_OK;
 }
 
@@ -742,7 +681,7 @@ JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap, unsigned jfi
 {
     JfLayout l;
     size_t at = 0;
-    l.offs = at, at += r16(nframes * a.nblkf * sizeof(uint32_t));
+    l.offs = at, at += r16(nframes * a.g.nblkf * sizeof(uint32_t));
     l.ibits = at, at += r16(nframes * a.ni * sizeof(uint32_t));
     l.nff = at, at += r16(nframes * a.ni * sizeof(uint32_t));
     l.ustart = at, at += r16(nframes * a.ni * sizeof(unsigned long long));
@@ -801,12 +740,12 @@ int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nfr
         return JPGX_EARG;
     int rc = jf_geometry(width, height, sample_ratio, restart_rows, nframes, a);
     if (rc) return rc;
-    if (coef_frame_stride % 64 || coef_frame_stride < (size_t)a.nblkf * 64 || out_frame_stride < out_cap)
+    if (coef_frame_stride % 64 || coef_frame_stride < (size_t)a.g.nblkf * 64 || out_frame_stride < out_cap)
         return JPGX_EARG;
     JfHdr hdr;
     memset(&hdr, 0, sizeof hdr);
     size_t dht_at = 0;
-    const size_t hl = jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.cpr, NULL, NULL, hdr.b,
+    const size_t hl = jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.g.cpr, NULL, NULL, hdr.b,
                                           sizeof hdr.b, &dht_at);
     if (!hl) return JPGX_EQUALITY;
     if (hl > sizeof hdr.b) return JPGX_EARG;

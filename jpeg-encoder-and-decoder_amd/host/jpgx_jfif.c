@@ -1,5 +1,8 @@
 /*
- * jpgx_jfif.c -- baseline JFIF writer for the block transform's output (host C99).
+ * jpgx_jfif.c -- the baseline JFIF writer's tables, header bytes and file-level entry points
+ * (host C99).  The scan itself is written by csrc/jpgx_jfif_write.cpp on the host and by
+ * csrc/jpgx_jfif.hip on the device, both from the routines of csrc/jx_jfif_enc.h and both with
+ * the tables and header bytes of this file (csrc/jpgx_internal.h).
  *
  * The reference never writes a file: its huffman_encode() does not terminate and only counts
  * symbols (src/huffman.c:23-235), and its dpcm() is an alternating-sign
@@ -13,18 +16,13 @@
  * table transposed (src/quantise.c:58); when one exceeds 255 (q <= 23) the tables are 16-bit
  * and the frame is extended sequential (SOF1) instead of baseline.  A standard decoder therefore reproduces the
  * reference's pipeline output -- including the effects of its Cb sign error
- * (src/preprocess.c:161) and of the x0 = -8 last-column quirk.  AC magnitudes above 1023
- * (possible only for chroma at q >= 93 with the sign error) are clamped to the baseline range.
+ * (src/preprocess.c:161) and of the x0 = -8 last-column quirk.  AC magnitudes beyond the baseline
+ * range (possible only for chroma at q >= 93 with the sign error) are clamped to it
+ * (JXE_AC_MAX, csrc/jx_jfif_enc.h).
  */
-#define _POSIX_C_SOURCE 200809L
-#include <pthread.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
-#ifdef __SSE2__
-#include <emmintrin.h>
-#endif
 
 #include "../../include/jpgx_compat.h"
 #include "../csrc/jx_consts.h"
@@ -92,112 +90,23 @@ static void put_dht(Out *o, int cls_id, const uint8_t bits[16], const uint8_t *v
     for (int i = 0; i < n; i++) put_byte(o, vals[i]);
 }
 
-/* ---- entropy-coded data: a word-at-a-time bit writer into a growable buffer ---------------
- * Bits accumulate MSB first in a 64-bit register; every 32 bits leave as four bytes at once
- * unless one of them is 0xFF (then byte by byte with the 0x00 stuffing of T.81 F.1.2.3). */
-typedef struct {
-    uint8_t *p;
-    size_t n, cap;
-    uint64_t acc;     /* the low nacc bits are pending */
-    int nacc;
-    int oom;
-} BW;
-
-static int bw_reserve(BW *w, size_t more)
-{
-    if (w->n + more <= w->cap) return 1;
-    size_t nc = w->cap ? w->cap : 1u << 16;
-    while (nc < w->n + more) nc *= 2;
-    uint8_t *q = (uint8_t *)realloc(w->p, nc);
-    if (!q) {
-        w->oom = 1;
-        return 0;
-    }
-    w->p = q;
-    w->cap = nc;
-    return 1;
-}
-
-static inline void bw_byte(BW *w, uint8_t b)
-{
-    w->p[w->n++] = b;
-    if (b == 0xff) w->p[w->n++] = 0x00;
-}
-
-/* v < 2^nb, nb <= 32 (a Huffman code and its additional bits in one call); the caller has
- * reserved room (bw_reserve) */
-static inline void bw_bits(BW *w, uint32_t v, int nb)
-{
-    w->acc = (w->acc << nb) | v;
-    w->nacc += nb;
-    if (w->nacc >= 32) {
-        w->nacc -= 32;
-        const uint32_t x = (uint32_t)(w->acc >> w->nacc);
-        if (((~x - 0x01010101u) & x & 0x80808080u) == 0) {       /* no 0xFF byte in x */
-            uint8_t *d = w->p + w->n;
-            d[0] = (uint8_t)(x >> 24);
-            d[1] = (uint8_t)(x >> 16);
-            d[2] = (uint8_t)(x >> 8);
-            d[3] = (uint8_t)x;
-            w->n += 4;
-        } else {
-            bw_byte(w, (uint8_t)(x >> 24));
-            bw_byte(w, (uint8_t)(x >> 16));
-            bw_byte(w, (uint8_t)(x >> 8));
-            bw_byte(w, (uint8_t)x);
-        }
-    }
-}
-
-/* pad to a byte boundary with 1-bits and emit the pending bytes */
-static void bw_flush(BW *w)
-{
-    const int pad = (8 - (w->nacc & 7)) & 7;
-    if (pad) {
-        w->acc = (w->acc << pad) | ((1u << pad) - 1u);
-        w->nacc += pad;
-    }
-    while (w->nacc >= 8) {
-        w->nacc -= 8;
-        bw_byte(w, (uint8_t)(w->acc >> w->nacc));
-    }
-}
-
-/* magnitude category and the value's additional bits (T.81 F.1.2.1) */
-static inline int category(int v, uint32_t *extra)
-{
-    const unsigned a = (unsigned)(v < 0 ? -v : v);
-    const int s = a ? 32 - __builtin_clz(a) : 0;
-    *extra = (uint32_t)(v < 0 ? v + (1 << s) - 1 : v) & ((1u << s) - 1u);
-    return s;
-}
-
 /* canonical Huffman codes (T.81 Annex C) indexed by symbol, packed: code << 8 | length */
-typedef struct {
-    uint32_t cl[256];
-} HuffCodes;
-
-static void build_codes(const uint8_t bits[16], const uint8_t *vals, HuffCodes *h)
+void jx_jfif_build_codes(const uint8_t bits[16], const uint8_t *vals, uint32_t cl[256])
 {
-    memset(h, 0, sizeof(*h));
+    memset(cl, 0, 256 * sizeof cl[0]);
     unsigned code = 0, k = 0;
     for (int l = 1; l <= 16; l++) {
-        for (int i = 0; i < bits[l - 1]; i++, k++) h->cl[vals[k]] = (code++) << 8 | (unsigned)l;
+        for (int i = 0; i < bits[l - 1]; i++, k++) cl[vals[k]] = (code++) << 8 | (unsigned)l;
         code <<= 1;
     }
 }
 
 void jx_jfif_codes(uint32_t cl[4][256])
 {
-    HuffCodes h;
-    build_codes(kDcLumBits, kDcVals, &h);
-    memcpy(cl[0], h.cl, sizeof h.cl);
-    build_codes(kAcLumBits, kAcLumVals, &h);
-    memcpy(cl[1], h.cl, sizeof h.cl);
-    build_codes(kDcChrBits, kDcVals, &h);
-    memcpy(cl[2], h.cl, sizeof h.cl);
-    build_codes(kAcChrBits, kAcChrVals, &h);
-    memcpy(cl[3], h.cl, sizeof h.cl);
+    jx_jfif_build_codes(kDcLumBits, kDcVals, cl[0]);
+    jx_jfif_build_codes(kAcLumBits, kAcLumVals, cl[1]);
+    jx_jfif_build_codes(kDcChrBits, kDcVals, cl[2]);
+    jx_jfif_build_codes(kAcChrBits, kAcChrVals, cl[3]);
 }
 
 /* ---- per-image tables: ITU-T T.81 Annex K.2 (see csrc/jpgx_internal.h) ---------------------- */
@@ -348,328 +257,40 @@ size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio,
     return o.n;
 }
 
-/* worst-case coded bytes of one block, stuffing included */
-#define JX_BLOCK_MAX (2 * (22 + 63 * 26 + 11 + 8) / 8 + 16)
-
-/* bit k set: z[k] != 0 */
-static inline uint64_t nonzero_mask(const int16_t *z)
-{
-#ifdef __SSE2__
-    const __m128i zero = _mm_setzero_si128();
-    uint64_t m = 0;
-    for (int i = 0; i < 4; i++) {
-        const __m128i a = _mm_loadu_si128((const __m128i *)(z + 16 * i));
-        const __m128i b = _mm_loadu_si128((const __m128i *)(z + 16 * i + 8));
-        const __m128i e = _mm_packs_epi16(_mm_cmpeq_epi16(a, zero), _mm_cmpeq_epi16(b, zero));
-        m |= (uint64_t)(uint16_t)~_mm_movemask_epi8(e) << (16 * i);
-    }
-    return m;
-#else
-    uint64_t m = 0;
-    for (int k = 0; k < 64; k++) m |= (uint64_t)(z[k] != 0) << k;
-    return m;
-#endif
-}
-
-/* one block's Huffman-coded data (T.81 F.1.2): DC difference against *pred, AC run/size */
-static void encode_block(BW *w, const int16_t *z, int *pred, const HuffCodes *dc, const HuffCodes *ac)
-{
-    uint32_t extra;
-    int diff = z[0] - *pred;                       /* true DC prediction */
-    if (diff > 2047) diff = 2047;                  /* (never reached: |DC| <= 1364) */
-    if (diff < -2047) diff = -2047;
-    *pred = z[0];
-    int s = category(diff, &extra);
-    uint32_t c = dc->cl[s];
-    bw_bits(w, (c >> 8) << s | extra, (int)(c & 0xff) + s);
-    uint64_t nz = nonzero_mask(z) & ~1ull;         /* the nonzero AC coefficients */
-    int prev = 0;
-    while (nz) {
-        const int k = __builtin_ctzll(nz);
-        nz &= nz - 1;
-        int run = k - prev - 1;
-        prev = k;
-        int v = z[k];
-        if (v > 1023) v = 1023;
-        if (v < -1023) v = -1023;
-        while (run > 15) {                         /* ZRL */
-            c = ac->cl[0xf0];
-            bw_bits(w, c >> 8, (int)(c & 0xff));
-            run -= 16;
-        }
-        s = category(v, &extra);
-        c = ac->cl[run << 4 | s];
-        bw_bits(w, (c >> 8) << s | extra, (int)(c & 0xff) + s);
-    }
-    if (prev < 63) {                               /* EOB */
-        c = ac->cl[0x00];
-        bw_bits(w, c >> 8, (int)(c & 0xff));
-    }
-}
-
-/* encode_block's walk, counting the symbols it codes instead of writing them: dc[category],
- * ac[run << 4 | category] (ZRL 0xf0, EOB 0x00) */
-static void count_block(const int16_t *z, int *pred, uint64_t *dc, uint64_t *ac)
-{
-    uint32_t extra;
-    int diff = z[0] - *pred;
-    if (diff > 2047) diff = 2047;
-    if (diff < -2047) diff = -2047;
-    *pred = z[0];
-    dc[category(diff, &extra)]++;
-    uint64_t nz = nonzero_mask(z) & ~1ull;
-    int prev = 0;
-    while (nz) {
-        const int k = __builtin_ctzll(nz);
-        nz &= nz - 1;
-        int run = k - prev - 1;
-        prev = k;
-        int v = z[k];
-        if (v > 1023) v = 1023;
-        if (v < -1023) v = -1023;
-        while (run > 15) {
-            ac[0xf0]++;
-            run -= 16;
-        }
-        ac[run << 4 | category(v, &extra)]++;
-    }
-    if (prev < 63) ac[0x00]++;
-}
-
-size_t jpgx_jfif_bound(int width, int height)
-{
-    if (width <= 0 || height <= 0) return 0;
-    /* headers + a per-block maximum with margin -- DC code + magnitude <= 16 + 16 bits, 63 AC
-     * codes + magnitudes <= 63 x (16 + 16) bits, EOB <= 16 bits -- doubled for 0xFF stuffing,
-     * plus per restart interval (at most one per MCU row) the padding byte, its possible stuffing
-     * byte and RSTm: 4 bytes */
-    const size_t blocks = (size_t)(width / 8 + 1) * (height / 8 + 1) * 3;
-    return 1024 + blocks * 2 * (32 + 63 * 32 + 16) / 8 + 4 * (size_t)(height / 8 + 1);
-}
-
-/* The scan's geometry and tables, shared by the coding threads */
+/* ---- the file-level entry points -------------------------------------------------------------
+ * Their common frame: room for `nblocks` blocks of coefficients and for the largest file
+ * (jpgx_jfif_bound), the caller's own step that fills the coefficients, then the scan -- sr 0:
+ * jpgx_write_jfif, else jpgx_write_jfif_sub -- and the file.  A failed malloc is reported as
+ * `nomem`, which is JPGX_ENOMEM for jpgx_encode_rgb_to_jpeg and JPGX_EARG for the two BMP entry
+ * points: an inconsistency of the ABI as released, kept as it is here. */
 typedef struct {
-    const int16_t *coef;
-    int hs, vs;
-    size_t bpr, nb, cpr, nbc, mrows;
-    size_t rows_per_interval, nintervals;
-    HuffCodes dc[2], ac[2];
-} Scan;
+    int16_t *coef;
+    uint8_t *buf;
+    size_t cap;
+} FileJob;
 
-/* restart intervals [i0, i1) into w: DC predictors reset at each, RSTm after each but the
- * scan's last (T.81 F.1.2.1.3, B.2.4.4) */
-static void code_intervals(const Scan *S, size_t i0, size_t i1, BW *w)
+static int file_begin(FileJob *j, size_t nblocks, int width, int height, int nomem)
 {
-    for (size_t iv = i0; iv < i1 && !w->oom; iv++) {
-        int pred[3] = {0, 0, 0};
-        const size_t r0 = iv * S->rows_per_interval;
-        size_t r1 = r0 + S->rows_per_interval;
-        if (r1 > S->mrows) r1 = S->mrows;
-        for (size_t my = r0; my < r1; my++) {
-            if (!bw_reserve(w, S->cpr * (size_t)(S->hs * S->vs + 2) * JX_BLOCK_MAX)) return;
-            for (size_t mx = 0; mx < S->cpr; mx++) {
-                /* MCU: hs x vs luma blocks (raster within the MCU), then Cb, then Cr (T.81 A.2.3) */
-                for (int dy = 0; dy < S->vs; dy++)
-                    for (int dx = 0; dx < S->hs; dx++) {
-                        const size_t yb = (my * S->vs + dy) * S->bpr + mx * S->hs + dx;
-                        encode_block(w, S->coef + yb * 64, &pred[0], &S->dc[0], &S->ac[0]);
-                    }
-                const size_t cb = my * S->cpr + mx;
-                encode_block(w, S->coef + (S->nb + cb) * 64, &pred[1], &S->dc[1], &S->ac[1]);
-                encode_block(w, S->coef + (S->nb + S->nbc + cb) * 64, &pred[2], &S->dc[1], &S->ac[1]);
-            }
-        }
-        if (!bw_reserve(w, 16)) return;
-        bw_flush(w);
-        if (iv + 1 < S->nintervals) {
-            w->p[w->n++] = 0xff;
-            w->p[w->n++] = (uint8_t)(0xd0 + (iv & 7));
-        }
-    }
+    j->coef = (int16_t *)malloc(nblocks * 64 * sizeof(int16_t));
+    j->cap = jpgx_jfif_bound(width, height);
+    j->buf = (uint8_t *)malloc(j->cap);
+    return (j->coef && j->buf) ? JPGX_OK : nomem;
 }
 
-/* the symbols of restart intervals [i0, i1) into cnt: DC luma, AC luma, DC chroma, AC chroma (Cb
- * and Cr together), in code_intervals' order and with its predictor resets */
-static void count_intervals(const Scan *S, size_t i0, size_t i1, uint64_t (*cnt)[256])
+/* rc: what came of filling j->coef */
+static int file_end(FileJob *j, int rc, int width, int height, int quality, int sr, const char *output)
 {
-    for (size_t iv = i0; iv < i1; iv++) {
-        int pred[3] = {0, 0, 0};
-        const size_t r0 = iv * S->rows_per_interval;
-        size_t r1 = r0 + S->rows_per_interval;
-        if (r1 > S->mrows) r1 = S->mrows;
-        for (size_t my = r0; my < r1; my++)
-            for (size_t mx = 0; mx < S->cpr; mx++) {
-                for (int dy = 0; dy < S->vs; dy++)
-                    for (int dx = 0; dx < S->hs; dx++) {
-                        const size_t yb = (my * S->vs + dy) * S->bpr + mx * S->hs + dx;
-                        count_block(S->coef + yb * 64, &pred[0], cnt[0], cnt[1]);
-                    }
-                const size_t cb = my * S->cpr + mx;
-                count_block(S->coef + (S->nb + cb) * 64, &pred[1], cnt[2], cnt[3]);
-                count_block(S->coef + (S->nb + S->nbc + cb) * 64, &pred[2], cnt[2], cnt[3]);
-            }
-    }
-}
-
-typedef struct {
-    const Scan *S;
-    size_t i0, i1;
-    BW w;
-    uint64_t (*cnt)[256];                                  /* non-NULL: count, do not code */
-} Job;
-
-static void *job_main(void *arg)
-{
-    Job *j = (Job *)arg;
-    if (j->cnt) count_intervals(j->S, j->i0, j->i1, j->cnt);
-    else code_intervals(j->S, j->i0, j->i1, &j->w);
-    return NULL;
-}
-
-/* jobs 1 .. T - 1 on threads of their own, job 0 and whatever got no thread on the caller's */
-static void run_jobs(Job *jobs, pthread_t *tid, long T)
-{
-    long nthr = T;
-    for (long t = 1; t < T; t++)
-        if (pthread_create(&tid[t], NULL, job_main, &jobs[t])) {
-            nthr = t;
-            break;
-        }
-    job_main(&jobs[0]);
-    for (long t = nthr; t < T; t++) job_main(&jobs[t]);
-    for (long t = 1; t < nthr; t++) pthread_join(tid[t], NULL);
-}
-
-int jpgx_write_jfif(const int16_t *coef, int width, int height, int quality, uint8_t *out,
-                    size_t cap, size_t *len)
-{
-    return jpgx_write_jfif_ex(coef, width, height, quality, 0, 0, 1, out, cap, len);
-}
-
-int jpgx_write_jfif_sub(const int16_t *coef, int width, int height, int quality,
-                        int sample_ratio, uint8_t *out, size_t cap, size_t *len)
-{
-    return jpgx_write_jfif_ex(coef, width, height, quality, sample_ratio, 0, 1, out, cap, len);
-}
-
-int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, int sample_ratio,
-                       int restart_rows, int nthreads, uint8_t *out, size_t cap, size_t *len)
-{
-    return jpgx_write_jfif_opt(coef, width, height, quality, sample_ratio, restart_rows, nthreads, 0u, out,
-                               cap, len);
-}
-
-int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality, int sample_ratio,
-                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
-                        size_t *len)
-{
-    if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return JPGX_EARG;
-    if (!coef || !out || width <= 0 || height <= 0 || width % 8 || height % 8 ||
-        width > 65535 || height > 65535 || sample_ratio < 0 || sample_ratio > 2 ||
-        restart_rows < -1 || nthreads < 0)
-        return JPGX_EARG;
-    const int hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;   /* Y sampling */
-    if (width % (8 * hs) || height % (8 * vs)) return JPGX_EGEOMETRY;
-    if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
-
-    Scan S;
-    S.coef = coef;
-    S.hs = hs;
-    S.vs = vs;
-    S.bpr = (size_t)(width / 8);
-    S.nb = S.bpr * (size_t)(height / 8);
-    S.cpr = S.bpr / (size_t)hs;
-    S.mrows = (size_t)(height / 8 / vs);
-    S.nbc = S.cpr * S.mrows;                               /* chroma planes' blocks */
-    long T = nthreads;
-    if (T == 0) {
-        T = sysconf(_SC_NPROCESSORS_ONLN);
-        if (T < 1) T = 1;
-        if (T > 64) T = 64;
-    }
-    /* restart interval: rows of MCUs, Ri = rows x MCUs per row (a 16-bit field) */
-    const size_t maxrows = 65535 / S.cpr;
-    size_t rr = 0;
-    if (restart_rows > 0) {
-        rr = (size_t)restart_rows;
-        if (rr > maxrows) return JPGX_EARG;
-    } else if (restart_rows == -1) {                       /* auto: ~4 intervals per thread */
-        rr = (S.mrows + 4 * (size_t)T - 1) / (4 * (size_t)T);
-        if (rr > maxrows) rr = maxrows;
-        if (rr < 1) rr = 1;
-    }
-    S.rows_per_interval = rr ? rr : S.mrows;
-    S.nintervals = (S.mrows + S.rows_per_interval - 1) / S.rows_per_interval;
-    if ((size_t)T > S.nintervals) T = (long)S.nintervals;
-    const int opt = (jfif_flags & JPGX_JFIF_OPTIMIZE) != 0;
-
-    /* thread t takes intervals [t NI / T, (t + 1) NI / T) */
-    Job *jobs = (Job *)calloc((size_t)T, sizeof(Job));
-    pthread_t *tid = (pthread_t *)calloc((size_t)T, sizeof(pthread_t));
-    uint64_t (*cnt)[256] = opt ? (uint64_t (*)[256])calloc((size_t)T * 4, sizeof *cnt) : NULL;
-    int rc = (jobs && tid && (cnt || !opt)) ? JPGX_OK : JPGX_ENOMEM;
-    for (long t = 0; t < T && !rc; t++) {
-        jobs[t].S = &S;
-        jobs[t].i0 = (size_t)t * S.nintervals / (size_t)T;
-        jobs[t].i1 = (size_t)(t + 1) * S.nintervals / (size_t)T;
-    }
-
-    /* the tables: Annex K.3's, or Annex K.2's from the image's own symbols (each thread counts the
-     * intervals it will code; integer sums, so the thread count does not show) */
-    uint8_t (*bits)[16] = NULL, (*vals)[256] = NULL;
-    uint8_t obits[4][16], ovals[4][256];
-    if (opt && !rc) {
-        for (long t = 0; t < T; t++) jobs[t].cnt = cnt + 4 * t;
-        run_jobs(jobs, tid, T);
-        for (long t = 1; t < T; t++)
-            for (int k = 0; k < 4; k++)
-                for (int s = 0; s < 256; s++) cnt[k][s] += cnt[4 * t + k][s];
-        memset(ovals, 0, sizeof ovals);
-        for (int k = 0; k < 4; k++) {
-            HuffCodes *h = k == 0 ? &S.dc[0] : k == 1 ? &S.ac[0] : k == 2 ? &S.dc[1] : &S.ac[1];
-            jx_jfif_optimal(cnt[k], obits[k], ovals[k]);
-            build_codes(obits[k], ovals[k], h);
-        }
-        for (long t = 0; t < T; t++) jobs[t].cnt = NULL;
-        bits = obits;
-        vals = ovals;
-    } else if (!rc) {
-        uint32_t cl[4][256];
-        jx_jfif_codes(cl);
-        memcpy(S.dc[0].cl, cl[0], sizeof cl[0]);
-        memcpy(S.ac[0].cl, cl[1], sizeof cl[1]);
-        memcpy(S.dc[1].cl, cl[2], sizeof cl[2]);
-        memcpy(S.ac[1].cl, cl[3], sizeof cl[3]);
-    }
-
-    /* headers */
-    Out o = {out, 0, cap, 0};
+    size_t len = 0;
+    if (!rc)
+        rc = sr ? jpgx_write_jfif_sub(j->coef, width, height, quality, sr, j->buf, j->cap, &len)
+                : jpgx_write_jfif(j->coef, width, height, quality, j->buf, j->cap, &len);
     if (!rc) {
-        o.n = jx_jfif_header_tabs(width, height, quality, sample_ratio, (unsigned)(rr * S.cpr),
-                                  (const uint8_t (*)[16])bits, (const uint8_t (*)[256])vals, out, cap, NULL);
-        if (!o.n) rc = JPGX_EQUALITY;
-        if (o.n > cap) o.overflow = 1;
+        FILE *f = fopen(output, "wb");
+        if (!f || fwrite(j->buf, 1, len, f) != len) rc = JPGX_EARG;
+        if (f && fclose(f)) rc = JPGX_EARG;
     }
-
-    /* the scan: every thread codes into its own buffer */
-    if (!rc) run_jobs(jobs, tid, T);
-    for (long t = 0; t < T && !rc; t++)
-        if (jobs[t].w.oom) rc = JPGX_ENOMEM;
-    if (!rc) {
-        for (long t = 0; t < T; t++) {
-            if (o.n + jobs[t].w.n <= o.cap) memcpy(o.p + o.n, jobs[t].w.p, jobs[t].w.n);
-            else o.overflow = 1;
-            o.n += jobs[t].w.n;
-        }
-        put_u16(&o, 0xffd9);                               /* EOI */
-        if (len) *len = o.n;
-        if (o.overflow) rc = JPGX_EARG;
-    }
-    if (jobs)
-        for (long t = 0; t < T; t++) free(jobs[t].w.p);
-    free(jobs);
-    free(tid);
-    free(cnt);
+    free(j->coef);
+    free(j->buf);
     return rc;
 }
 
@@ -688,23 +309,10 @@ int jpgx_encode_rgb_to_jpeg(const uint8_t *rgb, int width, int height, size_t pi
     if (rc) return rc;
     const size_t nb = (size_t)(width / 8) * (height / 8);
     const size_t nbc = jpgx_chroma_blocks(width, 0, height / 8, sample_ratio, p.flags);
-    int16_t *coef = (int16_t *)malloc((nb + 2 * nbc) * 64 * sizeof(int16_t));
-    const size_t cap = jpgx_jfif_bound(width, height);
-    uint8_t *buf = (uint8_t *)malloc(cap);
-    size_t len = 0;
-    rc = (coef && buf) ? JPGX_OK : JPGX_ENOMEM;
-    if (!rc) rc = jpgx_blocks(rgb, width, height, pitch, &p, coef, device);
-    if (!rc)
-        rc = sub ? jpgx_write_jfif_sub(coef, width, height, quality, sample_ratio, buf, cap, &len)
-                 : jpgx_write_jfif(coef, width, height, quality, buf, cap, &len);
-    if (!rc) {
-        FILE *f = fopen(output, "wb");
-        if (!f || fwrite(buf, 1, len, f) != len) rc = JPGX_EARG;
-        if (f && fclose(f)) rc = JPGX_EARG;
-    }
-    free(coef);
-    free(buf);
-    return rc;
+    FileJob j;
+    rc = file_begin(&j, nb + 2 * nbc, width, height, JPGX_ENOMEM);
+    if (!rc) rc = jpgx_blocks(rgb, width, height, pitch, &p, j.coef, device);
+    return file_end(&j, rc, width, height, quality, sub ? sample_ratio : 0, output);
 }
 
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,
@@ -723,21 +331,11 @@ int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int qualit
     p.flags = flags;
     const size_t nb = (size_t)(W / 8) * (H / 8);
     const size_t nbc = jpgx_chroma_blocks(W, 0, H / 8, sample_ratio, flags);
-    int16_t *coef = (int16_t *)malloc((nb + 2 * nbc) * 64 * sizeof(int16_t));
-    const size_t cap = jpgx_jfif_bound(W, H);
-    uint8_t *buf = (uint8_t *)malloc(cap);
-    size_t len = 0;
-    rc = (coef && buf) ? JPGX_OK : JPGX_EARG;
-    if (!rc) rc = jpgx_blocks(rgb, W, H, (size_t)W * 3, &p, coef, device);
-    if (!rc) rc = jpgx_write_jfif_sub(coef, W, H, quality, sample_ratio, buf, cap, &len);
-    if (!rc) {
-        FILE *f = fopen(output, "wb");
-        if (!f || fwrite(buf, 1, len, f) != len) rc = JPGX_EARG;
-        if (f && fclose(f)) rc = JPGX_EARG;
-    }
+    FileJob j;
+    rc = file_begin(&j, nb + 2 * nbc, W, H, JPGX_EARG);
+    if (!rc) rc = jpgx_blocks(rgb, W, H, (size_t)W * 3, &p, j.coef, device);
+    rc = file_end(&j, rc, W, H, quality, sample_ratio, output);
     jpgx_free(rgb);
-    free(coef);
-    free(buf);
     return rc;
 }
 
@@ -745,30 +343,20 @@ int jpgx_encode_bmp_to_jpeg(const char *input, const char *output, int quality,
                             int sample_ratio)
 {
     if (!input || !output) return JPGX_EARG;
-    jpgx_jpeg_data j;
-    memset(&j, 0, sizeof j);
-    int rc = jpgx_encode_bmp(input, quality, sample_ratio, 0, 0, &j);
+    jpgx_jpeg_data d;
+    memset(&d, 0, sizeof d);
+    int rc = jpgx_encode_bmp(input, quality, sample_ratio, 0, 0, &d);
     if (rc) return rc;
-    const size_t nb = (size_t)j.num_blocks_Y;
-    int16_t *coef = (int16_t *)malloc(nb * 3 * 64 * sizeof(int16_t));
-    const size_t cap = jpgx_jfif_bound(j.width, j.height);
-    uint8_t *buf = (uint8_t *)malloc(cap);
-    size_t len = 0;
-    rc = (coef && buf) ? JPGX_OK : JPGX_EARG;
+    const size_t nb = (size_t)d.num_blocks_Y;
+    FileJob j;
+    rc = file_begin(&j, nb * 3, d.width, d.height, JPGX_EARG);
     if (!rc) {
-        int **zz[3] = {j.zig_zag_Y, j.zig_zag_Cb, j.zig_zag_Cr};
+        int **zz[3] = {d.zig_zag_Y, d.zig_zag_Cb, d.zig_zag_Cr};
         for (int c = 0; c < 3; c++)
             for (size_t i = 0; i < nb; i++)
-                for (int k = 0; k < 64; k++) coef[((size_t)c * nb + i) * 64 + k] = (int16_t)zz[c][i][k];
-        rc = jpgx_write_jfif(coef, j.width, j.height, quality, buf, cap, &len);
+                for (int k = 0; k < 64; k++) j.coef[((size_t)c * nb + i) * 64 + k] = (int16_t)zz[c][i][k];
     }
-    if (!rc) {
-        FILE *f = fopen(output, "wb");
-        if (!f || fwrite(buf, 1, len, f) != len) rc = JPGX_EARG;
-        if (f && fclose(f)) rc = JPGX_EARG;
-    }
-    jpgx_free_jpgdata(&j);
-    free(coef);
-    free(buf);
+    rc = file_end(&j, rc, d.width, d.height, quality, 0, output);
+    jpgx_free_jpgdata(&d);
     return rc;
 }

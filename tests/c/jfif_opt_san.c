@@ -1,6 +1,6 @@
 /* jfif_opt_san.c -- TEST INFRASTRUCTURE (tests/test_jfif_opt.py): the per-image Huffman tables
- * (jx_jfif_optimal, jpgx_write_jfif_opt of host/jpgx_jfif.c) under -fsanitize=address,undefined, as
- * a program of its own: the builder on one used symbol, two equal counts, 256 equal counts, many
+ * (jx_jfif_optimal of host/jpgx_jfif.c, jpgx_write_jfif_opt of csrc/jpgx_jfif_write.cpp) under
+ * -fsanitize=address,undefined, as a program of its own: the builder on one used symbol, two equal counts, 256 equal counts, many
  * ties, a count above 2^32, random vectors and the Fibonacci vectors on 18 and 19 symbols (trees
  * deeper than 16), each result checked for Kraft's sum, its lengths and its values; the optimised
  * writer into exact-size, short and empty buffers, on 1 and 3 threads.

@@ -6,13 +6,12 @@ seeds and prints each file's length and FNV-1a hash and its first SHOWN corrupti
 decoder's result.  files() / flips() restate the generators, so that a test can hold the very bytes
 the shared decoding routines have seen under AddressSanitizer before it hands them to a GPU."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 
 import jpgx.compat as C
-from conftest import PKG, REPO
+import san_build
+from conftest import PKG
 from jfif_decode import decode
 
 COEF_SEED = 0x6A66696672656164
@@ -21,7 +20,7 @@ FLIPS, SHOWN = 2000, 48
 M64 = (1 << 64) - 1
 # the program's file order: index -> (W, H, sample_ratio, optimize)
 FILES = [(64 if big else 16, 64 if big else 16, sr, opt) for big in (1, 0) for sr in (0, 1, 2) for opt in (0, 1)]
-HAVE_CC = shutil.which("gcc") is not None and shutil.which("g++") is not None
+HAVE_CC = san_build.HAVE_CC
 # The GPU test's corrupt inputs all derive from the program's file 6 (16x16, 4:4:4, Annex K.3 tables):
 # its length and FNV-1a hash as the program prints them, and the corruption undefined_code_flip() finds
 # in its sweep.  tests/test_jfif_read.py holds the program to these values under the sanitizers;
@@ -107,40 +106,10 @@ def undefined_code_flip(idx=6):
     raise AssertionError("the sweep holds no such corruption")
 
 
-_result = None
-
-
 def run_program():
-    """Builds tests/c/jfif_read_san.c with host/*.c, the host plan and the host decoder under
-    -fsanitize=address,undefined (nothing is preloaded) and runs it, once per session; returns
-    (returncode, stdout, stderr)."""
-    global _result
-    if _result is not None:
-        return _result
-    bdir = os.path.join(REPO, "tests", "c", "_build", "jfif_read_san")
-    os.makedirs(bdir, exist_ok=True)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           "-g", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-I" + os.path.join(REPO, "include")]
-    host = sorted(os.path.join(PKG, "host", f) for f in os.listdir(os.path.join(PKG, "host")) if f.endswith(".c"))
-    objs = []
-    for src, cc, std in [(s, "gcc", "-std=c99") for s in host] + [
-            (os.path.join(REPO, "tests", "c", "san_nogpu.c"), "gcc", "-std=c11"),
-            (os.path.join(REPO, "tests", "c", "jfif_read_san.c"), "gcc", "-std=c11"),
-            (os.path.join(PKG, "csrc", "jpgx_plan.cpp"), "g++", "-std=c++17"),
-            (os.path.join(PKG, "csrc", "jpgx_jfif_read.cpp"), "g++", "-std=c++17")]:
-        obj = os.path.join(bdir, os.path.basename(src) + ".o")
-        b = subprocess.run([cc, std] + san + ["-c", src, "-o", obj], capture_output=True, text=True, timeout=600)
-        assert b.returncode == 0, b.stderr[-3000:]
-        objs.append(obj)
-    exe = os.path.join(bdir, "jfif_read_san")
-    b = subprocess.run(["g++"] + san + objs + ["-o", exe, "-lm", "-lpthread"], capture_output=True, text=True,
-                       timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    _result = (r.returncode, r.stdout, r.stderr)
-    return _result
+    """tests/c/jfif_read_san.c with the host layer and the host decoder under the sanitizers, built and
+    run once per session; returns (returncode, stdout, stderr)."""
+    return san_build.run("jfif_read_san", san_build.HOST_LAYER + [os.path.join(PKG, "csrc", "jpgx_jfif_read.cpp")])
 
 
 def assert_clean():

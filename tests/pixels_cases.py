@@ -3,13 +3,13 @@ coefficient frames of the pixel tests, each computed once, and the sanitizer pro
 tests/c/pixels_san.c, built and run once per session."""
 import functools
 import os
-import subprocess
 
 import numpy as np
 
 import jpgx
 import oracle
-from conftest import PKG, REPO
+import san_build
+from conftest import PKG
 
 QUALITIES = (1, 50, 90, 97)
 # (W, H) per sample mode: 8x8 (16x16 for 4:2:x) is one lane group; 136x16 is 17 blocks per row, a run
@@ -92,35 +92,10 @@ def fits_16_bits(coef, qt, nb):
     return max(np.abs(c[:nb] * q[0]).max(), np.abs(c[nb:] * q[1]).max()) < 32768
 
 
-_result = None
-
-
 def run_san():
-    """Builds tests/c/pixels_san.c with csrc/jpgx_pixels_host.cpp under
-    -fsanitize=address,undefined (nothing is preloaded) and runs it, once per session; returns
-    (returncode, stdout, stderr)."""
-    global _result
-    if _result is not None:
-        return _result
-    bdir = os.path.join(REPO, "tests", "c", "_build", "pixels_san")
-    os.makedirs(bdir, exist_ok=True)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           "-g", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-I" + os.path.join(REPO, "include")]
-    objs = []
-    for src, cc, std in [(os.path.join(REPO, "tests", "c", "pixels_san.c"), "gcc", "-std=c11"),
-                         (os.path.join(PKG, "csrc", "jpgx_pixels_host.cpp"), "g++", "-std=c++17")]:
-        obj = os.path.join(bdir, os.path.basename(src) + ".o")
-        b = subprocess.run([cc, std] + san + ["-c", src, "-o", obj], capture_output=True, text=True, timeout=600)
-        assert b.returncode == 0, b.stderr[-3000:]
-        objs.append(obj)
-    exe = os.path.join(bdir, "pixels_san")
-    b = subprocess.run(["g++"] + san + objs + ["-o", exe, "-lpthread"], capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
-    _result = (r.returncode, r.stdout, r.stderr)
-    return _result
+    """tests/c/pixels_san.c with csrc/jpgx_pixels_host.cpp under the sanitizers, built and run once per
+    session; returns (returncode, stdout, stderr)."""
+    return san_build.run("pixels_san", [os.path.join(PKG, "csrc", "jpgx_pixels_host.cpp")], timeout=600)
 
 
 def qt_of(q):

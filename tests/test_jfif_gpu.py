@@ -4,46 +4,25 @@ The oracle everywhere is the host writer on the same coefficients,
 jpgx.compat.write_jfif_ex(coef, W, H, q, sr, restart_rows=rr, nthreads=1), and the comparison is
 == on bytes: no golden data, no tolerance.  (The device's restart_rows = -1 means one MCU row per
 interval; the host writer's -1 depends on its thread count, so its equivalent call passes 1.)"""
-import ctypes
 import io
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import jpgx
 import jpgx.compat as C
-from conftest import GOLDEN, PKG, REPO
+import san_build
+from conftest import GOLDEN
 from jfif_decode import decode
+from jfif_inputs import CASES, hand_made, stuffing_guard, stuffing_heavy
+from jfif_inputs import lap as _lap, nblocks as _nblocks, scan_of as _scan
 
 gpu = pytest.mark.gpu
 
 
-# ---- coefficient generators (restated from tests/test_jfif_restart.py) ---------------------------
-def _nblocks(W, H, sr):
-    nb = (W // 8) * (H // 8)
-    return nb, (nb, nb // 2, nb // 4)[sr]
-
-
-def _lap(W, H, sr, seed, scale=6.0):
-    """laplacian AC, uniform DC in [-300, 300): [nb + 2 nbc][64] (for sr 0 that is [3][nb][64])"""
-    rng = np.random.default_rng(seed)
-    nb, nbc = _nblocks(W, H, sr)
-    coef = rng.laplace(0, scale, size=(nb + 2 * nbc, 64)).astype(np.int16)
-    coef[:, 0] = rng.integers(-300, 300, size=nb + 2 * nbc)
-    return np.ascontiguousarray(coef)
-
-
 def _host(coef, W, H, q, sr, rr):
     return C.write_jfif_ex(coef, W, H, q, sr, restart_rows=1 if rr == -1 else rr, nthreads=1)
-
-
-def _scan(data):
-    """the entropy-coded bytes between the SOS segment and EOI"""
-    at = data.index(b"\xff\xda")
-    return data[at + 14:-2]
 
 
 def _device(cuda, coef, W, H, q, sr, rr, cap=None):
@@ -116,55 +95,16 @@ def test_binding_refuses_host_tensors():
         jpgx.encode_jpeg(torch.zeros((64, 64, 3), dtype=torch.uint8), 50)
 
 
-@pytest.mark.skipif(shutil.which("gcc") is None or shutil.which("g++") is None,
-                    reason="needs gcc/g++ with libasan/libubsan")
+@pytest.mark.skipif(not san_build.HAVE_CC, reason="needs gcc/g++ with libasan/libubsan")
 def test_header_and_tables_under_asan_ubsan():
     """tests/c/jfif_header_san.c, a program of its own, with host/*.c and the host plan under
     AddressSanitizer + UndefinedBehaviorSanitizer (nothing is preloaded)."""
-    bdir = os.path.join(REPO, "tests", "c", "_build", "jfif_san")
-    os.makedirs(bdir, exist_ok=True)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           "-g", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-I" + os.path.join(REPO, "include")]
-    host = sorted(os.path.join(PKG, "host", f) for f in os.listdir(os.path.join(PKG, "host")) if f.endswith(".c"))
-    objs = []
-    for src, cc, std in [(s, "gcc", "-std=c99") for s in host] + [
-            (os.path.join(REPO, "tests", "c", "san_nogpu.c"), "gcc", "-std=c11"),
-            (os.path.join(REPO, "tests", "c", "jfif_header_san.c"), "gcc", "-std=c11"),
-            (os.path.join(PKG, "csrc", "jpgx_plan.cpp"), "g++", "-std=c++17")]:
-        obj = os.path.join(bdir, os.path.basename(src) + ".o")
-        b = subprocess.run([cc, std] + san + ["-c", src, "-o", obj], capture_output=True, text=True, timeout=600)
-        assert b.returncode == 0, b.stderr[-3000:]
-        objs.append(obj)
-    exe = os.path.join(bdir, "jfif_header_san")
-    b = subprocess.run(["g++"] + san + objs + ["-o", exe, "-lm", "-lpthread"], capture_output=True, text=True,
-                       timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0 and "jfif_header_san: clean" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    rc, out, err = san_build.run("jfif_header_san")
+    assert rc == 0 and "jfif_header_san: clean" in out, (out[-2000:], err[-4000:])
+    assert "runtime error" not in err and "AddressSanitizer" not in err, err[-4000:]
 
 
 # ---- GPU: byte equality with the host writer ------------------------------------------------------
-CASES = {
-    # name: (W, H, q, sr, rr, seed)
-    "one_block": (8, 8, 50, 0, 1, 1),
-    "64x48_rr1": (64, 48, 50, 0, 1, 2),
-    "128x64_rr3": (128, 64, 75, 0, 3, 3),             # intervals of 3, 3 and 2 rows
-    "128x64_auto": (128, 64, 75, 0, -1, 3),
-    "single_interval": (64, 48, 50, 0, 100, 4),       # rr >= MCU rows: one interval, DRI still written
-    "q10_16bit_dqt": (64, 48, 10, 0, 2, 5),           # SOF1
-    "q97": (64, 48, 97, 0, 2, 6),
-    "422_64x64": (64, 64, 75, 1, 1, 41),
-    "422_96x64": (96, 64, 75, 1, 3, 61),
-    "420_64x64": (64, 64, 75, 2, 1, 42),
-    "420_96x64": (96, 64, 75, 2, -1, 62),
-    "420_one_mcu": (16, 16, 50, 2, 1, 7),
-    "rst_wraps": (64, 96, 50, 0, 1, 8),               # 12 intervals: RST0..RST7, RST0..RST2
-}
-
-
 @gpu
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_bytes_equal_host_writer(cuda, name):
@@ -192,23 +132,7 @@ def test_all_zero_frame(cuda):
 @gpu
 @pytest.mark.parametrize("sr", [0, 1, 2])
 def test_hand_made_blocks(cuda, sr):
-    W, H = 64, 32
-    nb, nbc = _nblocks(W, H, sr)
-    coef = np.zeros((nb + 2 * nbc, 64), np.int16)
-    coef[1, 63] = 5                                  # three ZRLs, no EOB
-    coef[2, 63] = -1
-    coef[nb + 1, 63] = -700                          # the same in a chroma block
-    coef[3, 20] = -3                                 # one ZRL, a run of 3, EOB
-    coef[nb + nbc + 2, 20] = 1023
-    coef[5, 1:64] = 1                                # 63 codes, no EOB
-    coef[6, 16] = 1                                  # run of exactly 15: no ZRL
-    coef[7, 17] = 1                                  # run of exactly 16: ZRL + run 0
-    coef[8, 33] = 2000                               # AC clamp to 1023
-    coef[9, 33] = -2000
-    # DC steps of +-2047 and beyond between neighbours of a component (the clamp)
-    dcs = np.array([0, 2047, 0, -2047, 2047, -2048, 2047, 4000, -4000, 1, 0, 32767, -32768, 0], np.int16)
-    coef[10:10 + dcs.size, 0] = dcs
-    coef[nb:nb + 4, 0] = [1500, -1500, 1500, -600]
+    W, H, coef = hand_made(sr)
     for rr in (1, 2):
         assert _device(cuda, coef, W, H, 50, sr, rr) == _host(coef, W, H, 50, sr, rr)
 
@@ -216,15 +140,9 @@ def test_hand_made_blocks(cuda, sr):
 @gpu
 @pytest.mark.parametrize("sr", [0, 2])
 def test_stuffing_heavy_frame(cuda, sr):
-    W, H, q = 64, 96, 50
-    nb, nbc = _nblocks(W, H, sr)
-    vals = np.array([0, 0, 0, 1, -1, 1023, -1023, 32767, -32768, 2047, -2047], np.int16)
-    coef = np.ascontiguousarray(np.random.default_rng(0).choice(vals, (nb + 2 * nbc, 64)))
+    W, H, q, coef = stuffing_heavy(sr)
     ref = _host(coef, W, H, q, sr, 1)
-    scan = _scan(ref)
-    pairs = scan.count(b"\xff\x00")
-    endings = sum(scan.count(b"\xff\x00\xff" + bytes([0xd0 + m])) for m in range(8))
-    print(f"stuffed pairs {pairs}, intervals ending FF 00 FF Dn {endings}")
+    pairs, endings = stuffing_guard(ref)
     assert pairs >= 1000 and endings >= 1          # a different numpy must not empty the case
     assert _device(cuda, coef, W, H, q, sr, 1) == ref
 

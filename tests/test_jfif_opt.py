@@ -9,7 +9,6 @@ import ctypes
 import io
 import itertools
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -17,8 +16,11 @@ import pytest
 
 import jpgx
 import jpgx.compat as C
-from conftest import GOLDEN, PKG, REPO
+import san_build
+from conftest import GOLDEN, REPO
 from jfif_decode import decode
+from jfif_inputs import CASES, hand_made, stuffing_heavy          # the geometries of tests/test_jfif_gpu.py
+from jfif_inputs import lap as _lap, nblocks as _nblocks
 
 gpu = pytest.mark.gpu
 OPT = jpgx.JFIF_OPTIMIZE
@@ -150,38 +152,6 @@ def test_builder_all_zero_counts():
 
 
 # ---- coefficients, symbol counts and file parsing ------------------------------------------------
-def _nblocks(W, H, sr):
-    nb = (W // 8) * (H // 8)
-    return nb, (nb, nb // 2, nb // 4)[sr]
-
-
-def _lap(W, H, sr, seed, scale=6.0):
-    """laplacian AC, uniform DC in [-300, 300): [nb + 2 nbc][64] (as tests/test_jfif_gpu.py)"""
-    rng = np.random.default_rng(seed)
-    nb, nbc = _nblocks(W, H, sr)
-    coef = rng.laplace(0, scale, size=(nb + 2 * nbc, 64)).astype(np.int16)
-    coef[:, 0] = rng.integers(-300, 300, size=nb + 2 * nbc)
-    return np.ascontiguousarray(coef)
-
-
-CASES = {
-    # name: (W, H, q, sr, rr, seed) -- the geometries of tests/test_jfif_gpu.py
-    "one_block": (8, 8, 50, 0, 1, 1),
-    "64x48_rr1": (64, 48, 50, 0, 1, 2),
-    "128x64_rr3": (128, 64, 75, 0, 3, 3),
-    "128x64_auto": (128, 64, 75, 0, -1, 3),
-    "single_interval": (64, 48, 50, 0, 100, 4),
-    "q10_16bit_dqt": (64, 48, 10, 0, 2, 5),
-    "q97": (64, 48, 97, 0, 2, 6),
-    "422_64x64": (64, 64, 75, 1, 1, 41),
-    "422_96x64": (96, 64, 75, 1, 3, 61),
-    "420_64x64": (64, 64, 75, 2, 1, 42),
-    "420_96x64": (96, 64, 75, 2, -1, 62),
-    "420_one_mcu": (16, 16, 50, 2, 1, 7),
-    "rst_wraps": (64, 96, 50, 0, 1, 8),
-}
-
-
 def _host(coef, W, H, q, sr, rr, optimize=True, nthreads=1):
     """the oracle: the host writer (the device's restart_rows -1 is one MCU row per interval)"""
     return C.write_jfif_ex(coef, W, H, q, sr, restart_rows=1 if rr == -1 else rr, nthreads=nthreads,
@@ -381,34 +351,13 @@ def test_device_entry_argument_checks():
             assert _call(flags=flags, sr=sr, rr=rr, nf=nf, fstride=(nb + 2 * nbc) * 64, wsb=n - 1) == jpgx.EWORKSPACE
 
 
-@pytest.mark.skipif(shutil.which("gcc") is None or shutil.which("g++") is None,
-                    reason="needs gcc/g++ with libasan/libubsan")
+@pytest.mark.skipif(not san_build.HAVE_CC, reason="needs gcc/g++ with libasan/libubsan")
 def test_builder_and_writer_under_asan_ubsan():
     """tests/c/jfif_opt_san.c, a program of its own, with host/*.c and the host plan under
     AddressSanitizer + UndefinedBehaviorSanitizer (nothing is preloaded)."""
-    bdir = os.path.join(REPO, "tests", "c", "_build", "jfif_opt_san")
-    os.makedirs(bdir, exist_ok=True)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-           "-g", "-O1", "-ffp-contract=off", "-Wall", "-Wextra", "-I" + os.path.join(REPO, "include")]
-    host = sorted(os.path.join(PKG, "host", f) for f in os.listdir(os.path.join(PKG, "host")) if f.endswith(".c"))
-    objs = []
-    for src, cc, std in [(s, "gcc", "-std=c99") for s in host] + [
-            (os.path.join(REPO, "tests", "c", "san_nogpu.c"), "gcc", "-std=c11"),
-            (os.path.join(REPO, "tests", "c", "jfif_opt_san.c"), "gcc", "-std=c11"),
-            (os.path.join(PKG, "csrc", "jpgx_plan.cpp"), "g++", "-std=c++17")]:
-        obj = os.path.join(bdir, os.path.basename(src) + ".o")
-        b = subprocess.run([cc, std] + san + ["-c", src, "-o", obj], capture_output=True, text=True, timeout=600)
-        assert b.returncode == 0, b.stderr[-3000:]
-        objs.append(obj)
-    exe = os.path.join(bdir, "jfif_opt_san")
-    b = subprocess.run(["g++"] + san + objs + ["-o", exe, "-lm", "-lpthread"], capture_output=True, text=True,
-                       timeout=600)
-    assert b.returncode == 0, b.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 0 and "jfif_opt_san: clean" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    rc, out, err = san_build.run("jfif_opt_san")
+    assert rc == 0 and "jfif_opt_san: clean" in out, (out[-2000:], err[-4000:])
+    assert "runtime error" not in err and "AddressSanitizer" not in err, err[-4000:]
 
 
 # ---- GPU: byte equality with the host writer -----------------------------------------------------
@@ -457,30 +406,10 @@ def test_all_zero_frame(cuda, sr):
     assert _device(cuda, coef, W, H, 50, sr, 1) == ref
 
 
-def _hand_made(sr):
-    W, H = 64, 32
-    nb, nbc = _nblocks(W, H, sr)
-    coef = np.zeros((nb + 2 * nbc, 64), np.int16)
-    coef[1, 63] = 5                                  # three ZRLs, no EOB
-    coef[2, 63] = -1
-    coef[nb + 1, 63] = -700                          # the same in a chroma block
-    coef[3, 20] = -3                                 # one ZRL, a run of 3, EOB
-    coef[nb + nbc + 2, 20] = 1023
-    coef[5, 1:64] = 1                                # 63 codes, no EOB
-    coef[6, 16] = 1                                  # run of exactly 15: no ZRL
-    coef[7, 17] = 1                                  # run of exactly 16: ZRL + run 0
-    coef[8, 33] = 2000                               # AC clamp to 1023
-    coef[9, 33] = -2000
-    dcs = np.array([0, 2047, 0, -2047, 2047, -2048, 2047, 4000, -4000, 1, 0, 32767, -32768, 0], np.int16)
-    coef[10:10 + dcs.size, 0] = dcs                  # DC steps of +-2047 and beyond (the clamp)
-    coef[nb:nb + 4, 0] = [1500, -1500, 1500, -600]
-    return W, H, coef
-
-
 @gpu
 @pytest.mark.parametrize("sr", [0, 2])
 def test_hand_made_blocks(cuda, sr):
-    W, H, coef = _hand_made(sr)
+    W, H, coef = hand_made(sr)
     for rr in (1, 2):
         ref = _host(coef, W, H, 50, sr, rr)
         cnt = symbol_counts(coef, W, H, sr, rr)
@@ -492,10 +421,7 @@ def test_hand_made_blocks(cuda, sr):
 @gpu
 @pytest.mark.parametrize("sr", [0, 2])
 def test_stuffing_heavy_frame(cuda, sr):
-    W, H, q = 64, 96, 50
-    nb, nbc = _nblocks(W, H, sr)
-    vals = np.array([0, 0, 0, 1, -1, 1023, -1023, 32767, -32768, 2047, -2047], np.int16)
-    coef = np.ascontiguousarray(np.random.default_rng(0).choice(vals, (nb + 2 * nbc, 64)))
+    W, H, q, coef = stuffing_heavy(sr)
     ref = _host(coef, W, H, q, sr, 1)
     at = ref.index(b"\xff\xda")
     pairs = ref[at + 14:-2].count(b"\xff\x00")

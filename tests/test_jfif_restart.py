@@ -1,5 +1,5 @@
 """The entropy stage's JFIF writer with restart intervals coded on host threads
-(host/jpgx_jfif.c jpgx_write_jfif_ex; SURVEY.md 8f(1), parity unpinned: the reference's
+(csrc/jpgx_jfif_write.cpp jpgx_write_jfif_ex; SURVEY.md 8f(1), parity unpinned: the reference's
 huffman_encode never terminates, src/huffman.c:23-235).  Checked against two independent
 decoders written from T.81 -- tests/jfif_decode.py (Python, small frames) and tests/c/jfif_dec.c
 (C, restart intervals decoded on threads, for big frames) -- and against PIL (libjpeg)."""
