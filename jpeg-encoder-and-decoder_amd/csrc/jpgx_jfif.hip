@@ -58,11 +58,11 @@ constexpr int kHdrSuf = 32;             /* DRI, SOS: 6 + 14 bytes */
 struct JfArgs {
     const int16_t *coef;                /* frame f: Y [nb][64] | Cb [nbc][64] | Cr [nbc][64] at f fstride */
     unsigned long long fstride;         /* int16 elements */
-    jxe_geom g;
+    jx_frame g;
     uint32_t rpi, ni;                   /* MCU rows per interval, intervals per frame */
     uint32_t ivblk;                     /* blocks of a full interval */
     uint32_t hdrlen;
-    uint32_t *offs;                     /* [nframes][nblkf] bit offset within the interval (scan order) */
+    uint32_t *offs;                     /* [nframes][g.nblk] bit offset within the interval (scan order) */
     uint32_t *ibits;                    /* [nframes][ni] coded bits of the interval */
     uint32_t *nff;                      /* [nframes][ni] 0xFF bytes of the interval (padding included) */
     unsigned long long *ustart;         /* [nframes][ni] place in the frame's unstuffed stream */
@@ -109,8 +109,8 @@ struct JfHdrOpt {
 __device__ __forceinline__ uint32_t jf_nblk(const JfArgs &a, uint32_t iv)
 {
     const uint32_t r0 = iv * a.rpi;
-    const uint32_t rows = min(a.rpi, a.g.mrows - r0);
-    return rows * a.g.cpr * a.g.bpm;
+    const uint32_t rows = min(a.rpi, a.g.cbh - r0);
+    return rows * a.g.cbw * a.g.bpm;
 }
 
 typedef uint32_t jf_u4 __attribute__((ext_vector_type(4)));
@@ -120,13 +120,13 @@ typedef uint32_t jf_u4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint64_t jf_load(const JfArgs &a, uint32_t f, uint32_t iv, uint32_t i, uint32_t *row,
                                             int &diff, uint32_t &chroma)
 {
-    const jxe_geom &g = a.g;
+    const jx_frame &g = a.g;
     const uint32_t m = i / g.bpm, j = i - m * g.bpm;
     const int16_t *base = a.coef + (size_t)f * a.fstride;
     /* position jj of the interval's MCU mm in the frame's coefficient array */
     const auto at = [&](uint32_t mm, uint32_t jj) {
-        const uint32_t mr = mm / g.cpr;
-        return jxe_block(g, iv * a.rpi + mr, mm - mr * g.cpr, jj) * 64;
+        const uint32_t mr = mm / g.cbw;
+        return jx_frame_block(&g, iv * a.rpi + mr, mm - mr * g.cbw, jj) * 64;
     };
     const int16_t *z = base + at(m, j);
     /* the previous block of the same component: the luma block before it in the MCU, else the
@@ -291,7 +291,7 @@ __global__ __launch_bounds__(kT) void k_jf_len(const JfArgs a, const Tabs tabs)
     const uint32_t iv = blockIdx.x, f = blockIdx.y, t = threadIdx.x;
     jf_tabs_to_lds(tabs, dc, ac);
     const uint32_t n = jf_nblk(a, iv);
-    uint32_t *offs = a.offs + (size_t)f * a.g.nblkf + (size_t)iv * a.ivblk;
+    uint32_t *offs = a.offs + (size_t)f * a.g.nblk + (size_t)iv * a.ivblk;
     uint32_t carry = 0;
     for (uint32_t i0 = 0; i0 < n; i0 += kT) {
         const uint32_t i = i0 + t;
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(kT) void k_jf_pack(const JfArgs a, const Tabs tabs)
     uint8_t *area = a.ustream + (size_t)f * a.uarea + a.ustart[(size_t)f * a.ni + iv];
     for (uint32_t c = t; c < nchunk; c += kT) ((uint4 *)area)[c] = make_uint4(0, 0, 0, 0);
     __syncthreads();                    /* the interval's place is zero before any lane ORs into it */
-    const uint32_t *offs = a.offs + (size_t)f * a.g.nblkf + (size_t)iv * a.ivblk;
+    const uint32_t *offs = a.offs + (size_t)f * a.g.nblk + (size_t)iv * a.ivblk;
     for (uint32_t i0 = 0; i0 < n; i0 += kT) {
         const uint32_t i = i0 + t;
         const bool live = i < n;
@@ -656,19 +656,17 @@ __global__ __launch_bounds__(kT) void k_jf_tables(const JfOpt o)
     if (t == 0) o.dhtlen[(size_t)f * 4 + tb] = min(2u + seg, (uint32_t)kDhtSlot);
 }
 
-size_t r16(size_t x) { return (x + 15) / 16 * 16; }
-
 /* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0.  The
  * device codes with restart intervals only: restart_rows 0 is refused, -1 is one MCU row */
 int jf_geometry(int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
 {
-    if (restart_rows == 0 || restart_rows < -1 || nframes == 0 || nframes > 65535) return JPGX_EARG;
-    const int rc = jxe_geometry(width, height, sample_ratio, &a.g);
+    if (restart_rows == 0 || restart_rows < -1 || !jx_frames_ok(nframes)) return JPGX_EARG;
+    const int rc = jx_frame_rc_coder(jx_frame_make(width, height, sample_ratio, &a.g));
     if (rc) return rc;
     a.rpi = restart_rows > 0 ? (uint32_t)restart_rows : 1u;
-    if (a.rpi > jxe_max_rows(&a.g)) return JPGX_EARG;
-    a.ni = (a.g.mrows + a.rpi - 1) / a.rpi;
-    a.ivblk = a.rpi * a.g.cpr * a.g.bpm;
+    if (a.rpi > jx_frame_max_rows(&a.g)) return JPGX_EARG;
+    a.ni = (a.g.cbh + a.rpi - 1) / a.rpi;
+    a.ivblk = a.rpi * a.g.cbw * a.g.bpm;
     return JPGX_OK;
 }
 
@@ -680,23 +678,23 @@ struct JfLayout {
 JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap, unsigned jfif_flags)
 {
     JfLayout l;
-    size_t at = 0;
-    l.offs = at, at += r16(nframes * a.g.nblkf * sizeof(uint32_t));
-    l.ibits = at, at += r16(nframes * a.ni * sizeof(uint32_t));
-    l.nff = at, at += r16(nframes * a.ni * sizeof(uint32_t));
-    l.ustart = at, at += r16(nframes * a.ni * sizeof(unsigned long long));
-    l.ostart = at, at += r16(nframes * a.ni * sizeof(unsigned long long));
-    l.ovf = at, at += r16(nframes * sizeof(uint32_t));
-    l.uarea = r16(out_cap) + 16 * (size_t)a.ni;
-    l.ustream = at, at += nframes * l.uarea;
+    jx_carve ws;
+    l.offs = ws.take(nframes * a.g.nblk * sizeof(uint32_t));
+    l.ibits = ws.take(nframes * a.ni * sizeof(uint32_t));
+    l.nff = ws.take(nframes * a.ni * sizeof(uint32_t));
+    l.ustart = ws.take(nframes * a.ni * sizeof(unsigned long long));
+    l.ostart = ws.take(nframes * a.ni * sizeof(unsigned long long));
+    l.ovf = ws.take(nframes * sizeof(uint32_t));
+    l.uarea = jx_r16(out_cap) + 16 * (size_t)a.ni;
+    l.ustream = ws.take(nframes * l.uarea);
     l.counts = l.tabs = l.dht = l.dhtlen = 0;
     if (jfif_flags & JPGX_JFIF_OPTIMIZE) {
-        l.counts = at, at += r16(nframes * 4 * 256 * sizeof(unsigned long long));
-        l.tabs = at, at += r16(nframes * sizeof(JfTabs));
-        l.dht = at, at += r16(nframes * 4 * kDhtSlot);
-        l.dhtlen = at, at += r16(nframes * 4 * sizeof(uint32_t));
+        l.counts = ws.take(nframes * 4 * 256 * sizeof(unsigned long long));
+        l.tabs = ws.take(nframes * sizeof(JfTabs));
+        l.dht = ws.take(nframes * 4 * kDhtSlot);
+        l.dhtlen = ws.take(nframes * 4 * sizeof(uint32_t));
     }
-    l.total = at;
+    l.total = ws.at;
     return l;
 }
 
@@ -740,12 +738,11 @@ int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nfr
         return JPGX_EARG;
     int rc = jf_geometry(width, height, sample_ratio, restart_rows, nframes, a);
     if (rc) return rc;
-    if (coef_frame_stride % 64 || coef_frame_stride < (size_t)a.g.nblkf * 64 || out_frame_stride < out_cap)
-        return JPGX_EARG;
+    if (!jx_coef_batch_ok(coef_frame_stride, a.g.nblk) || out_frame_stride < out_cap) return JPGX_EARG;
     JfHdr hdr;
     memset(&hdr, 0, sizeof hdr);
     size_t dht_at = 0;
-    const size_t hl = jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.g.cpr, NULL, NULL, hdr.b,
+    const size_t hl = jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.g.cbw, NULL, NULL, hdr.b,
                                           sizeof hdr.b, &dht_at);
     if (!hl) return JPGX_EQUALITY;
     if (hl > sizeof hdr.b) return JPGX_EARG;

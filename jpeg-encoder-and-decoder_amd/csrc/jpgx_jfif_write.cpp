@@ -118,7 +118,7 @@ inline uint64_t nonzero_mask(const int16_t *z)
 /* The scan's geometry and tables, shared by the coding threads */
 struct Scan {
     const int16_t *coef;
-    jxe_geom g;
+    jx_frame g;
     size_t rows_per_interval, nintervals;
     uint32_t cl[4][256];                /* jx_jfif_codes' order and packing: code << 8 | length */
 };
@@ -137,7 +137,7 @@ struct CodeSink {
     void put(uint32_t c, uint32_t s, uint32_t extra) { bw_bits(w, (c >> 8) << s | extra, (int)((c & 0xffu) + s)); }
     void dc(uint32_t s, uint32_t extra) { put(dct[s], s, extra); }
     void ac(uint32_t sym, uint32_t s, uint32_t extra) { put(act[sym], s, extra); }
-    bool row() { return bw_reserve(w, (size_t)S->g.cpr * S->g.bpm * JX_BLOCK_MAX) != 0; }
+    bool row() { return bw_reserve(w, (size_t)S->g.cbw * S->g.bpm * JX_BLOCK_MAX) != 0; }
     bool end(size_t iv)
     {
         if (!bw_reserve(w, 16)) return false;
@@ -172,17 +172,17 @@ struct Block {
 template <class Sink>
 void walk_intervals(const Scan *S, size_t i0, size_t i1, Sink sink)
 {
-    const jxe_geom &g = S->g;
+    const jx_frame &g = S->g;
     for (size_t iv = i0; iv < i1; iv++) {
         int pred[3] = {0, 0, 0};
         const size_t r0 = iv * S->rows_per_interval;
         size_t r1 = r0 + S->rows_per_interval;
-        if (r1 > g.mrows) r1 = g.mrows;
+        if (r1 > g.cbh) r1 = g.cbh;
         for (size_t my = r0; my < r1; my++) {
             if (!sink.row()) return;
-            for (uint32_t mx = 0; mx < g.cpr; mx++)
+            for (uint32_t mx = 0; mx < g.cbw; mx++)
                 for (uint32_t j = 0; j < g.bpm; j++) {
-                    const int16_t *z = S->coef + jxe_block(g, (uint32_t)my, mx, j) * 64;
+                    const int16_t *z = S->coef + jx_frame_block(&g, (uint32_t)my, mx, j) * 64;
                     const uint32_t comp = j < g.lum ? 0u : j - g.lum + 1u;
                     const int diff = jxe_dc_diff(z[0], pred[comp]);
                     pred[comp] = z[0];
@@ -264,11 +264,11 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
     if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return JPGX_EARG;
     if (!coef || !out || restart_rows < -1 || nthreads < 0) return JPGX_EARG;
     Scan S;
-    int rc = jxe_geometry(width, height, sample_ratio, &S.g);
+    int rc = jx_frame_rc_coder(jx_frame_make(width, height, sample_ratio, &S.g));
     if (rc) return rc;
     if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
     S.coef = coef;
-    const size_t mrows = S.g.mrows;
+    const size_t mrows = S.g.cbh;
     long T = nthreads;
     if (T == 0) {
         T = sysconf(_SC_NPROCESSORS_ONLN);
@@ -276,7 +276,7 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
         if (T > 64) T = 64;
     }
     /* restart interval: rows of MCUs, Ri = rows x MCUs per row (a 16-bit field) */
-    const size_t maxrows = jxe_max_rows(&S.g);
+    const size_t maxrows = jx_frame_max_rows(&S.g);
     size_t rr = 0;
     if (restart_rows > 0) {
         rr = (size_t)restart_rows;
@@ -328,7 +328,7 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
     size_t n = 0;
     int overflow = 0;
     if (!rc) {
-        n = jx_jfif_header_tabs(width, height, quality, sample_ratio, (unsigned)(rr * S.g.cpr),
+        n = jx_jfif_header_tabs(width, height, quality, sample_ratio, (unsigned)(rr * S.g.cbw),
                                 (const uint8_t (*)[16])bits, (const uint8_t (*)[256])vals, out, cap, NULL);
         if (!n) rc = JPGX_EQUALITY;
         if (n > cap) overflow = 1;

@@ -30,6 +30,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "jx_frame.h"
 #include "jx_hip.h"
 #include "jx_idct.h"
 
@@ -43,6 +44,13 @@ constexpr uint32_t kStageRow = 208;     /* bytes between the staged pixel rows o
 
 __constant__ uint8_t kZZ[64] = JXI_ZZ_INIT;
 
+/* The kernels' view of the frame (jx_frame.h): the eight words they read, in the order their
+ * arguments had when they were measured.  With the whole jx_frame by value two of the 4:2:x figures
+ * lay 0.2 - 0.4 % above the parent's range, so the host fills these from the frame. */
+struct PxGeom {
+    uint32_t bw, bh, cbw, cbh, hs, vs, nb, nbc;
+};
+
 struct PxArgs {
     const int16_t *coef;
     unsigned long long cstride;         /* int16 elements between frames */
@@ -52,7 +60,7 @@ struct PxArgs {
     uint8_t *rgb;
     unsigned long long pitch, ostride;
     uint8_t *planes;                    /* workspace [nframes][2][8 cbh][8 cbw] (4:2:x) */
-    jxi_geom g;
+    PxGeom g;
 };
 
 union V4 {
@@ -291,9 +299,12 @@ __global__ __launch_bounds__(kWave) void k_px_sub(const PxArgs a)
     }
 }
 
-size_t px_workspace(const jxi_geom &g, int sample_ratio, size_t nframes)
+/* the chroma sample planes (4:2:x): the workspace's one part */
+size_t px_workspace(const jx_frame &g, size_t nframes)
 {
-    return sample_ratio ? nframes * 2 * (size_t)g.nbc * 64 : 0;
+    jx_carve ws;
+    if (g.hs > 1) ws.take(nframes * 2 * (size_t)g.nbc * 64);
+    return ws.at;
 }
 
 unsigned px_grid_x(uint32_t blocks_per_row)
@@ -308,9 +319,9 @@ extern "C" {
 
 size_t jpgx_pixels_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes)
 {
-    jxi_geom g;
-    if (nframes == 0 || nframes > 65535 || jxi_geometry(width, height, sample_ratio, &g)) return 0;
-    return px_workspace(g, sample_ratio, nframes);
+    jx_frame g;
+    if (!jx_frames_ok(nframes) || jx_frame_make(width, height, sample_ratio, &g)) return 0;
+    return px_workspace(g, nframes);
 }
 
 int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
@@ -321,16 +332,17 @@ int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nfra
     PxArgs a;
     memset(&a, 0, sizeof a);
     if (!d_coef || !d_qt || !d_rgb || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_status & 3) ||
-        ((uintptr_t)d_rgb & 7) || nframes == 0 || nframes > 65535)
+        ((uintptr_t)d_rgb & 7) || !jx_frames_ok(nframes))
         return JPGX_EARG;
-    const int rc = jxi_geometry(width, height, sample_ratio, &a.g);
+    jx_frame f;
+    const int rc = jx_frame_rc_pixels(jx_frame_make(width, height, sample_ratio, &f));
     if (rc) return rc;
-    const size_t per = ((size_t)a.g.nb + 2 * (size_t)a.g.nbc) * 64;
-    if (coef_frame_stride % 64 || coef_frame_stride < per) return JPGX_EARG;
+    a.g = PxGeom{f.bw, f.bh, f.cbw, f.cbh, f.hs, f.vs, f.nb, f.nbc};
+    if (!jx_coef_batch_ok(coef_frame_stride, f.nblk)) return JPGX_EARG;
     if (qt_frame_stride != 0 && qt_frame_stride < 128) return JPGX_EARG;
     if (out_pitch < (size_t)width * 3 || out_pitch % 8) return JPGX_EARG;
     if (out_frame_stride < out_pitch * (size_t)height || out_frame_stride % 8) return JPGX_EARG;
-    const size_t need = px_workspace(a.g, sample_ratio, nframes);
+    const size_t need = px_workspace(f, nframes);
     if (workspace_bytes < need) return JPGX_EWORKSPACE;
     if (need && (!d_workspace || ((uintptr_t)d_workspace & 15))) return JPGX_EARG;
     a.coef = d_coef;

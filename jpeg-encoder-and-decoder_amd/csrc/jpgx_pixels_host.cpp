@@ -15,6 +15,7 @@
 #include <unistd.h>
 
 #include "../../include/jpgx_compat.h"
+#include "jx_frame.h"
 #include "jx_idct.h"
 
 namespace {
@@ -24,7 +25,7 @@ const uint8_t kZZ[64] = JXI_ZZ_INIT;
 struct Ctx {
     const int16_t *coef;
     const uint16_t (*qt)[64];
-    jxi_geom g;
+    jx_frame g;
     uint8_t *plane[3];              /* Y: 8 bh x 8 bw, Cb / Cr: 8 cbh x 8 cbw */
     uint8_t *rgb;
     size_t pitch;
@@ -54,7 +55,7 @@ void block_samples(const int16_t *coef, const uint16_t *qt, uint8_t *dst, size_t
 
 void samples_rows(const Ctx &c, uint32_t m0, uint32_t m1)
 {
-    const jxi_geom &g = c.g;
+    const jx_frame &g = c.g;
     for (int ch = 0; ch < 3; ch++) {
         const uint32_t bw = ch ? g.cbw : g.bw, per = ch ? 1u : g.vs;
         const int16_t *src = c.coef + (ch == 0 ? 0 : ((size_t)g.nb + (size_t)(ch - 1) * g.nbc) * 64);
@@ -68,7 +69,7 @@ void samples_rows(const Ctx &c, uint32_t m0, uint32_t m1)
 
 void pixel_rows(const Ctx &c, uint32_t m0, uint32_t m1)
 {
-    const jxi_geom &g = c.g;
+    const jx_frame &g = c.g;
     const uint32_t W = g.bw * 8, Wc = g.cbw * 8, Hc = g.cbh * 8;
     const int v2 = g.vs == 2;
     for (uint32_t y = m0 * 8 * g.vs; y < m1 * 8 * g.vs; y++) {
@@ -140,7 +141,7 @@ extern "C" int jpgx_pixels_host(const int16_t *coef, int width, int height, int 
     if (!coef || !qt || !rgb || nthreads < 0) return JPGX_EARG;
     Ctx c;
     memset(&c, 0, sizeof c);
-    const int rc = jxi_geometry(width, height, sample_ratio, &c.g);
+    const int rc = jx_frame_rc_pixels(jx_frame_make(width, height, sample_ratio, &c.g));
     if (rc) return rc;
     if (pitch < (size_t)width * 3) return JPGX_EARG;
     const size_t ny = (size_t)c.g.nb * 64, nc = (size_t)c.g.nbc * 64;

@@ -1,0 +1,100 @@
+/*
+ * jx_frame.h -- a coded frame, stated once: what width, height and sample ratio make
+ * of the sampling factors, the block and MCU counts and the place of an MCU's blocks in the
+ * coefficient array Y [nb][64] | Cb [nbc][64] | Cr [nbc][64].  One source for the JFIF coder (host and
+ * device), the pixel path and the device decoder's entry point; the decoder's routines keep their own
+ * copy in jxd_frame (jx_jfif_dec.h; DESIGN.md 4.7 says why).  Plain C99 that is also C++ and HIP.
+ */
+#ifndef JX_FRAME_H
+#define JX_FRAME_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/jpgx.h"
+
+#if defined(__HIPCC__)
+#define JXF_FN __host__ __device__ static inline
+#else
+#define JXF_FN static inline
+#endif
+
+/* Y sampled hs x vs, Cb and Cr 1 x 1, one interleaved scan */
+typedef struct jx_frame {
+    uint32_t hs, vs;        /* Y blocks per MCU, across and down: 1x1, 2x1, 2x2                  */
+    uint32_t lum, bpm;      /* Y blocks per MCU (hs x vs); blocks per MCU (lum + 2)              */
+    uint32_t bw, bh;        /* Y blocks per block row, block rows                                */
+    uint32_t cbw, cbh;      /* the same of a chroma plane: MCUs per MCU row, MCU rows            */
+    uint32_t nb, nbc, nblk; /* blocks: Y, per chroma plane (= MCUs), per frame                   */
+} jx_frame;
+
+/* why a frame is refused; the first that applies */
+enum {
+    JXF_SAMPLE = 1,         /* sample_ratio is not 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0)             */
+    JXF_RANGE,              /* a side <= 0 or > 65535 (SOF's 16-bit fields)                      */
+    JXF_MULT8,              /* a side is not a multiple of 8                                     */
+    JXF_MCU                 /* a side is not a multiple of the MCU (8 hs x 8 vs)                 */
+};
+
+/* the luma sampling factors of sample_ratio 0 (4:4:4), 1 (4:2:2), 2 (4:2:0) */
+JXF_FN void jx_frame_sampling(int sample_ratio, uint32_t *hs, uint32_t *vs)
+{
+    *hs = sample_ratio ? 2u : 1u;
+    *vs = sample_ratio == 2 ? 2u : 1u;
+}
+
+JXF_FN int jx_frame_make(int width, int height, int sample_ratio, jx_frame *f)
+{
+    if (sample_ratio < 0 || sample_ratio > 2) return JXF_SAMPLE;
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return JXF_RANGE;
+    if (width % 8 || height % 8) return JXF_MULT8;
+    jx_frame_sampling(sample_ratio, &f->hs, &f->vs);
+    f->bw = (uint32_t)width / 8u;
+    f->bh = (uint32_t)height / 8u;
+    if (f->bw % f->hs || f->bh % f->vs) return JXF_MCU;
+    f->lum = f->hs * f->vs;
+    f->bpm = f->lum + 2u;
+    f->cbw = f->bw / f->hs;
+    f->cbh = f->bh / f->vs;
+    f->nb = f->bw * f->bh;
+    f->nbc = f->cbw * f->cbh;
+    f->nblk = f->nb + 2u * f->nbc;
+    return 0;
+}
+
+/* The codes the entry points refuse with are part of the ABI and differ; each is one mapping of
+ * the reason:            SAMPLE         RANGE           MULT8           MCU
+ *   the JFIF coder       EARG           EARG            EARG            EGEOMETRY
+ *   the device decoder   EARG           EARG            EGEOMETRY       EGEOMETRY
+ *   the pixel path       ESAMPLE        EGEOMETRY       EGEOMETRY       EGEOMETRY           */
+JXF_FN int jx_frame_rc_coder(int why) { return !why ? JPGX_OK : why == JXF_MCU ? JPGX_EGEOMETRY : JPGX_EARG; }
+JXF_FN int jx_frame_rc_decoder(int why) { return !why ? JPGX_OK : why >= JXF_MULT8 ? JPGX_EGEOMETRY : JPGX_EARG; }
+JXF_FN int jx_frame_rc_pixels(int why) { return !why ? JPGX_OK : why == JXF_SAMPLE ? JPGX_ESAMPLE : JPGX_EGEOMETRY; }
+
+/* the most MCU rows a restart interval may have: Ri = rows x MCUs per row is DRI's 16-bit field */
+JXF_FN uint32_t jx_frame_max_rows(const jx_frame *f) { return 65535u / f->cbw; }
+
+/* block indices in the frame's coefficient array: luma block (dy, dx) of MCU (my, mx), and the
+ * MCU's block of chroma plane c (0: Cb, 1: Cr) */
+JXF_FN size_t jx_frame_luma(const jx_frame *f, uint32_t my, uint32_t mx, uint32_t dy, uint32_t dx)
+{
+    return (size_t)(my * f->vs + dy) * f->bw + mx * f->hs + dx;
+}
+
+JXF_FN size_t jx_frame_chroma(const jx_frame *f, uint32_t c, uint32_t my, uint32_t mx)
+{
+    return (size_t)f->nb + (size_t)c * f->nbc + (size_t)my * f->cbw + mx;
+}
+
+/* position j of MCU (my, mx) in scan order: the hs x vs luma blocks in raster order within the
+ * MCU, then Cb, then Cr (T.81 A.2.3) */
+JXF_FN size_t jx_frame_block(const jx_frame *f, uint32_t my, uint32_t mx, uint32_t j)
+{
+    if (j < f->lum) {
+        const uint32_t dy = j / f->hs;
+        return jx_frame_luma(f, my, mx, dy, j - dy * f->hs);
+    }
+    return jx_frame_chroma(f, j - f->lum, my, mx);
+}
+
+#endif

@@ -7,4 +7,27 @@
 #include "../../include/jpgx.h"
 #define JX_MAX_DEV 64       /* devices with state of their own (tables uploaded once per device) */
 static inline int jx_hip_rc(hipError_t e) { return e == hipSuccess ? JPGX_OK : JPGX_EHIP; }
+
+/* what the batch entry points (JFIF coder, decoder, pixels) check and carve alike */
+static inline size_t jx_r16(size_t x) { return (x + 15) / 16 * 16; }
+
+/* a workspace carved front to back: every part begins on a multiple of 16 bytes */
+struct jx_carve {
+    size_t at = 0;
+    size_t take(size_t bytes)
+    {
+        const size_t off = at;
+        at += jx_r16(bytes);
+        return off;
+    }
+};
+
+/* a grid dimension holds the frame index */
+static inline bool jx_frames_ok(size_t nframes) { return nframes != 0 && nframes <= 65535; }
+
+/* frames of whole blocks, coef_frame_stride int16 elements apart, each with room for nblk blocks */
+static inline bool jx_coef_batch_ok(size_t coef_frame_stride, uint32_t nblk)
+{
+    return coef_frame_stride % 64 == 0 && coef_frame_stride >= (size_t)nblk * 64;
+}
 #endif

@@ -122,30 +122,4 @@ JXI_FN void jxi_rgb(uint32_t y, uint32_t cb, uint32_t cr, uint32_t *r, uint32_t 
     *b = jxi_clamp255(y + jxi_sar(116130u * cb + (32768u - 128u * 116130u), 16));
 }
 
-/* the geometry of a frame of the stated size and sampling; nonzero: JPGX_ESAMPLE / JPGX_EGEOMETRY
- * (-3 / -1, include/jpgx.h) */
-struct jxi_geom {
-    uint32_t bw, bh;        /* Y blocks per block row, block rows                  */
-    uint32_t cbw, cbh;      /* the same of a chroma plane                          */
-    uint32_t hs, vs;        /* luma sampling 1x1, 2x1, 2x2                         */
-    uint32_t nb, nbc;       /* blocks of Y, of a chroma plane                      */
-};
-
-JXI_FN int jxi_geometry(int width, int height, int sample_ratio, jxi_geom *g)
-{
-    if (sample_ratio < 0 || sample_ratio > 2) return -3;
-    g->hs = sample_ratio ? 2u : 1u;
-    g->vs = sample_ratio == 2 ? 2u : 1u;
-    if (width <= 0 || height <= 0 || width > 65535 || height > 65535 || (uint32_t)width % (8u * g->hs) ||
-        (uint32_t)height % (8u * g->vs))
-        return -1;
-    g->bw = (uint32_t)width / 8u;
-    g->bh = (uint32_t)height / 8u;
-    g->cbw = g->bw / g->hs;
-    g->cbh = g->bh / g->vs;
-    g->nb = g->bw * g->bh;
-    g->nbc = g->cbw * g->cbh;
-    return 0;
-}
-
 #endif

@@ -2,8 +2,8 @@
  * jx_jfif_enc.h -- the baseline JFIF entropy coder's routines, one source for the
  * host writer (csrc/jpgx_jfif_write.cpp, g++) and the device coder (csrc/jpgx_jfif.hip): the
  * magnitude categories of T.81 F.1.2.1, the clamps, one block's walk (DC symbol, run/size symbols,
- * ZRL, EOB), the scan's geometry and the place of an MCU's blocks in the coefficient array.  Plain
- * functions and templates, no allocation, no I/O, no global state.
+ * ZRL, EOB).  The scan's geometry and the place of an MCU's blocks in the coefficient array are
+ * jx_frame.h's.  Plain functions and templates, no allocation, no I/O, no global state.
  *
  * Not here, because the two sides differ by nature: the bit writers (a growable buffer with
  * stuffing on the host; bit offsets, LDS slots and a later stuffing pass on the device), the table
@@ -16,7 +16,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/jpgx.h"
+#include "jx_frame.h"
 
 #if defined(__HIPCC__)
 #define JXE_FN __host__ __device__ static inline
@@ -90,52 +90,6 @@ JXE_FN void jxe_walk(Sink &sink, Coef coef, uint64_t nz, int diff)
         sink.ac(sym, s, extra);
     }
     if (prev < 63u) sink.ac(0x00u, 0u, 0u);
-}
-
-/* the scan's geometry: Y sampled hs x vs, Cb and Cr 1 x 1, one interleaved scan */
-struct jxe_geom {
-    uint32_t hs, vs;        /* Y blocks per MCU, across and down                                 */
-    uint32_t lum, bpm;      /* Y blocks per MCU (hs x vs); blocks per MCU (lum + 2)              */
-    uint32_t bpr, cpr;      /* Y blocks per block row, MCUs per MCU row                          */
-    uint32_t mrows;         /* MCU rows                                                          */
-    uint32_t nb, nbc, nblkf;/* blocks: Y, per chroma plane, per frame                            */
-};
-
-/* JPGX_EARG unless width and height are positive multiples of 8 up to 65535 and sample_ratio is
- * 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0); JPGX_EGEOMETRY unless they are multiples of the MCU */
-JXE_FN int jxe_geometry(int width, int height, int sample_ratio, jxe_geom *g)
-{
-    if (width <= 0 || height <= 0 || width % 8 || height % 8 || width > 65535 || height > 65535 ||
-        sample_ratio < 0 || sample_ratio > 2)
-        return JPGX_EARG;
-    const uint32_t hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;
-    if (width % (8 * hs) || height % (8 * vs)) return JPGX_EGEOMETRY;
-    g->hs = hs;
-    g->vs = vs;
-    g->lum = hs * vs;
-    g->bpm = g->lum + 2;
-    g->bpr = (uint32_t)width / 8;
-    g->cpr = g->bpr / hs;
-    g->mrows = (uint32_t)height / 8 / vs;
-    g->nb = g->bpr * ((uint32_t)height / 8);
-    g->nbc = g->cpr * g->mrows;
-    g->nblkf = g->nb + 2 * g->nbc;
-    return JPGX_OK;
-}
-
-/* the most MCU rows a restart interval may have: Ri = rows x MCUs per row is DRI's 16-bit field */
-JXE_FN uint32_t jxe_max_rows(const jxe_geom *g) { return 65535u / g->cpr; }
-
-/* where position j of MCU (my, mx) is in the frame's coefficient array Y [nb][64] | Cb [nbc][64] |
- * Cr [nbc][64], in blocks: the hs x vs luma blocks in raster order within the MCU, then Cb, then
- * Cr (T.81 A.2.3) */
-JXE_FN size_t jxe_block(const jxe_geom &g, uint32_t my, uint32_t mx, uint32_t j)
-{
-    if (j < g.lum) {
-        const uint32_t dy = j / g.hs, dx = j - dy * g.hs;
-        return (size_t)(my * g.vs + dy) * g.bpr + mx * g.hs + dx;
-    }
-    return (size_t)g.nb + (size_t)(j - g.lum) * g.nbc + (size_t)my * g.cpr + mx;
 }
 
 #endif

@@ -27,6 +27,7 @@
 #include "../../include/jpgx_compat.h"
 #include "../csrc/jx_consts.h"
 #include "../csrc/jpgx_internal.h"
+#include "../csrc/jx_frame.h"
 
 /* ITU-T T.81 Annex K.3, Tables K.3-K.6: code-length counts and symbol values */
 static const uint8_t kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
@@ -189,7 +190,8 @@ size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio,
 {
     uint16_t zz[2][64];
     if (jpgx_jfif_qt(quality, zz)) return 0;
-    const int hs = sample_ratio ? 2 : 1, vs = sample_ratio == 2 ? 2 : 1;   /* Y sampling */
+    uint32_t hs, vs;                                       /* Y sampling */
+    jx_frame_sampling(sample_ratio, &hs, &vs);
     Out o = {out, 0, cap, 0};
     put_u16(&o, 0xffd8);                                   /* SOI */
     put_u16(&o, 0xffe0);                                   /* APP0 JFIF 1.01 */
@@ -269,6 +271,16 @@ typedef struct {
     size_t cap;
 } FileJob;
 
+/* the blocks of the frame that sample ratio sr codes, for a size the forward path takes */
+static int frame_blocks(int width, int height, const jpgx_params *p, int sr, size_t *nblocks)
+{
+    jx_frame f;
+    int rc = jpgx_validate(width, height, p);
+    if (!rc) rc = jx_frame_rc_coder(jx_frame_make(width, height, sr, &f));
+    if (!rc) *nblocks = f.nblk;
+    return rc;
+}
+
 static int file_begin(FileJob *j, size_t nblocks, int width, int height, int nomem)
 {
     j->coef = (int16_t *)malloc(nblocks * 64 * sizeof(int16_t));
@@ -305,12 +317,11 @@ int jpgx_encode_rgb_to_jpeg(const uint8_t *rgb, int width, int height, size_t pi
      * jpgx_encode_bmp_to_jpeg_ex) */
     const int sub = (flags & JPGX_FLAG_SUBSAMPLE) && sample_ratio != 0;
     p.flags = sub ? JPGX_FLAG_SUBSAMPLE : 0u;
-    int rc = jpgx_validate(width, height, &p);
+    size_t nblocks;
+    int rc = frame_blocks(width, height, &p, sub ? sample_ratio : 0, &nblocks);
     if (rc) return rc;
-    const size_t nb = (size_t)(width / 8) * (height / 8);
-    const size_t nbc = jpgx_chroma_blocks(width, 0, height / 8, sample_ratio, p.flags);
     FileJob j;
-    rc = file_begin(&j, nb + 2 * nbc, width, height, JPGX_ENOMEM);
+    rc = file_begin(&j, nblocks, width, height, JPGX_ENOMEM);
     if (!rc) rc = jpgx_blocks(rgb, width, height, pitch, &p, j.coef, device);
     return file_end(&j, rc, width, height, quality, sub ? sample_ratio : 0, output);
 }
@@ -329,12 +340,14 @@ int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int qualit
     jpgx_params p;
     jpgx_default_params(&p, W, H, quality, sample_ratio);
     p.flags = flags;
-    const size_t nb = (size_t)(W / 8) * (H / 8);
-    const size_t nbc = jpgx_chroma_blocks(W, 0, H / 8, sample_ratio, flags);
-    FileJob j;
-    rc = file_begin(&j, nb + 2 * nbc, W, H, JPGX_EARG);
-    if (!rc) rc = jpgx_blocks(rgb, W, H, (size_t)W * 3, &p, j.coef, device);
-    rc = file_end(&j, rc, W, H, quality, sample_ratio, output);
+    size_t nblocks;
+    rc = frame_blocks(W, H, &p, sample_ratio, &nblocks);
+    if (!rc) {
+        FileJob j;
+        rc = file_begin(&j, nblocks, W, H, JPGX_EARG);
+        if (!rc) rc = jpgx_blocks(rgb, W, H, (size_t)W * 3, &p, j.coef, device);
+        rc = file_end(&j, rc, W, H, quality, sample_ratio, output);
+    }
     jpgx_free(rgb);
     return rc;
 }

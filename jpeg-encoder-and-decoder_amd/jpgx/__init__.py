@@ -291,6 +291,30 @@ def chroma_blocks(width: int, row_begin: int, row_end: int, sample_ratio: int = 
     return int(lib.jpgx_chroma_blocks(width, row_begin, row_end, sample_ratio, flags))
 
 
+def _frame(fn: str, width: int, height: int, sample_ratio: int, flags: int | None = None, d_coef=None,
+           whole_blocks: bool = False):
+    """(nb, nbc, int16 elements per frame, elements between frames) of a frame's coefficients,
+    Y [nb][64] | Cb [nbc][64] | Cr [nbc][64].  flags None: a coded frame (csrc/jx_frame.h), its
+    geometry checked and its chroma subsampled as sample_ratio says; else the forward path's output
+    under `flags`.  d_coef ([nframes][...]): every frame must be contiguous and hold that much
+    (whole_blocks: and be laid out as the JFIF coder needs it); without it the fourth value is None."""
+    if flags is None:
+        if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
+            raise ValueError(f"{fn}: bad geometry or sample_ratio")
+        flags = FLAG_SUBSAMPLE if sample_ratio else 0
+    nb = (width // 8) * (height // 8)
+    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, flags)
+    per_frame = (nb + 2 * nbc) * 64
+    if d_coef is None:
+        return nb, nbc, per_frame, None
+    if not d_coef[0].is_contiguous() or d_coef[0].numel() < per_frame:
+        raise ValueError(f"{fn}: each frame must be contiguous and hold nb + 2 nbc blocks")
+    stride = int(d_coef.stride(0)) if d_coef.shape[0] > 1 else int(d_coef[0].numel())
+    if whole_blocks and (d_coef.data_ptr() % 16 or stride % 64):
+        raise ValueError(f"{fn}: 16-byte aligned frames, a stride of whole blocks")
+    return nb, nbc, per_frame, stride
+
+
 def entropy_stats_gpu(d_coef, nb_y: int, nb_c: int, carry=None, stream=None):
     """(dc int32 [nb_y + 2 nb_c], hist uint32 [4][257]) device tensors: the reference's dpcm and
     huffman_encode frequency pass over d_coef (torch int16 tensor, Y|Cb|Cr blocks)."""
@@ -351,17 +375,8 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
         raise ValueError("jfif_gpu: d_coef must be a device tensor")
     if d_coef.dtype != torch.int16 or d_coef.dim() < 2:
         raise ValueError("jfif_gpu: d_coef must be an int16 [nframes][...] tensor")
-    if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
-        raise ValueError("jfif_gpu: bad geometry or sample_ratio")
-    nb = (width // 8) * (height // 8)
-    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, FLAG_SUBSAMPLE if sample_ratio else 0)
-    per_frame = (nb + 2 * nbc) * 64
-    if not d_coef[0].is_contiguous() or d_coef[0].numel() < per_frame:
-        raise ValueError("jfif_gpu: each frame must be contiguous and hold nb + 2 nbc blocks")
+    _, _, per_frame, fstride = _frame("jfif_gpu", width, height, sample_ratio, d_coef=d_coef, whole_blocks=True)
     nf = d_coef.shape[0]
-    fstride = d_coef.stride(0) if nf > 1 else d_coef[0].numel()
-    if d_coef.data_ptr() % 16 or fstride % 64:
-        raise ValueError("jfif_gpu: 16-byte aligned frames, a stride of whole blocks")
     dev = d_coef.device
     cap = int(cap) if cap else max(1 << 20, per_frame // 2)
     jflags = JFIF_OPTIMIZE if optimize else 0
@@ -419,14 +434,11 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
         raise ValueError("jfif_decode_gpu: d_files [nframes][cap] and lens [nframes]")
     if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
         raise ValueError("jfif_decode_gpu: each file must be contiguous")
-    if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
-        raise ValueError("jfif_decode_gpu: bad geometry or sample_ratio")
+    nb, nbc, _, _ = _frame("jfif_decode_gpu", width, height, sample_ratio)
     nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
     fstride = int(d_files.stride(0)) if nf > 1 else cap
     if fstride < cap:
         raise ValueError("jfif_decode_gpu: overlapping files")
-    nb = (width // 8) * (height // 8)
-    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, FLAG_SUBSAMPLE if sample_ratio else 0)
     dev = d_files.device
     coef = torch.empty((nf, nb + 2 * nbc, 64), dtype=torch.int16, device=dev)
     qt = torch.empty((nf, 2, 64), dtype=torch.uint16, device=dev)
@@ -486,15 +498,8 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
         raise ValueError("pixels_gpu: d_coef must be an int16 [nframes][...] device tensor")
     if not isinstance(d_qt, torch.Tensor) or not d_qt.is_cuda or d_qt.dtype != torch.uint16 or not d_qt.is_contiguous():
         raise ValueError("pixels_gpu: d_qt must be a contiguous uint16 device tensor")
-    if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
-        raise ValueError("pixels_gpu: bad geometry or sample_ratio")
     nf = int(d_coef.shape[0])
-    nb = (width // 8) * (height // 8)
-    nbc = chroma_blocks(width, 0, height // 8, sample_ratio, FLAG_SUBSAMPLE if sample_ratio else 0)
-    per = (nb + 2 * nbc) * 64
-    if not d_coef[0].is_contiguous() or d_coef[0].numel() < per:
-        raise ValueError("pixels_gpu: each frame must be contiguous and hold nb + 2 nbc blocks")
-    cstride = int(d_coef.stride(0)) if nf > 1 else int(d_coef[0].numel())
+    _, _, _, cstride = _frame("pixels_gpu", width, height, sample_ratio, d_coef=d_coef)
     if d_qt.numel() == 128:
         qstride = 0
     elif d_qt.numel() == 128 * nf:
@@ -566,8 +571,7 @@ def encode_blocks(rgb, quality: int, sample_ratio: int = 0, underflow: bytes | N
     int16 [3][nb][64] (with FLAG_SUBSAMPLE: [nb + 2 nbc][64], see split_sub).  Device tensors
     stay on the device; numpy goes through jpgx_blocks."""
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
-    nb = (H // 8) * (W // 8)
-    nbc = chroma_blocks(W, 0, H // 8, sample_ratio, flags)
+    nb, nbc, per_frame, _ = _frame("encode_blocks", W, H, sample_ratio, flags)
     shape = (nb + 2 * nbc, 64) if flags & FLAG_SUBSAMPLE else (3, nb, 64)
     if isinstance(rgb, np.ndarray):
         rgb = np.ascontiguousarray(rgb, np.uint8)
@@ -582,7 +586,7 @@ def encode_blocks(rgb, quality: int, sample_ratio: int = 0, underflow: bytes | N
     p = default_params(W, H, quality, sample_ratio, underflow, flags)
     _check(validate(W, H, p), "jpgx_validate")
     fr = frames(W, H)
-    fr.out_frame_stride = shape[0] * 64 if flags & FLAG_SUBSAMPLE else 3 * nb * 64
+    fr.out_frame_stride = per_frame
     out = torch.empty(shape, dtype=torch.int16, device=rgb.device)
     ws = torch.empty(workspace_size(fr), dtype=torch.uint8, device=rgb.device)
     blocks_gpu(fr, p, rgb.contiguous(), out, ws)
@@ -595,8 +599,7 @@ def encode_blocks_multi(rgb: np.ndarray, quality: int, ngpus: int, sample_ratio:
     rgb = np.ascontiguousarray(rgb, np.uint8)
     H, W = rgb.shape[:2]
     p = default_params(W, H, quality, sample_ratio, underflow, flags)
-    nb = (H // 8) * (W // 8)
-    nbc = chroma_blocks(W, 0, H // 8, sample_ratio, flags)
+    nb, nbc, _, _ = _frame("encode_blocks_multi", W, H, sample_ratio, flags)
     out = np.empty((nb + 2 * nbc, 64) if flags & FLAG_SUBSAMPLE else (3, nb, 64), np.int16)
     _check(lib.jpgx_blocks_multi(rgb.ctypes.data, W, H, W * 3, ctypes.byref(p), out.ctypes.data,
                                  ngpus), "jpgx_blocks_multi")
@@ -631,8 +634,7 @@ class HostContext:
         if rgb.strides[0] < 3 * W:                # flipped or overlapping rows: not a pitch
             raise ValueError("rgb rows must be laid out top-down with a pitch >= 3 * width")
         p = default_params(W, H, quality, sample_ratio, underflow, flags)
-        nb = (H // 8) * (W // 8)
-        nbc = chroma_blocks(W, 0, H // 8, sample_ratio, flags)
+        nb, nbc, _, _ = _frame("HostContext.blocks", W, H, sample_ratio, flags)
         shape = (nb + 2 * nbc, 64) if flags & FLAG_SUBSAMPLE else (3, nb, 64)
         if out is None:
             out = np.empty(shape, np.int16)

@@ -1,5 +1,6 @@
-"""Test helper: the coefficient frames that tests/test_jfif_gpu.py, tests/test_jfif_opt.py and
-tests/test_jfif_pinned.py share, so that the three hold the writers to the very same inputs."""
+"""Test helper: the coefficient frames that tests/test_jfif_gpu.py, tests/test_jfif_opt.py,
+tests/test_jfif_pinned.py, tests/test_jfif_read.py and tests/test_jfif_decode_gpu.py share, so that
+they hold the writers and the decoders to the very same inputs."""
 import numpy as np
 
 CASES = {
@@ -40,9 +41,8 @@ def scan_of(data):
     return data[at + 14:-2]
 
 
-def hand_made(sr):
+def hand_made(sr, W=64, H=32):
     """(W, H, coef): every rule of the block walk in a 64 x 32 frame"""
-    W, H = 64, 32
     nb, nbc = nblocks(W, H, sr)
     coef = np.zeros((nb + 2 * nbc, 64), np.int16)
     coef[1, 63] = 5                                  # three ZRLs, no EOB
@@ -62,9 +62,9 @@ def hand_made(sr):
     return W, H, coef
 
 
-def stuffing_heavy(sr):
+def stuffing_heavy(sr, W=64, H=96):
     """(W, H, q, coef): a 64 x 96 frame of extreme values, whose scan is full of 0xFF bytes"""
-    W, H, q = 64, 96, 50
+    q = 50
     nb, nbc = nblocks(W, H, sr)
     vals = np.array([0, 0, 0, 1, -1, 1023, -1023, 32767, -32768, 2047, -2047], np.int16)
     coef = np.ascontiguousarray(np.random.default_rng(0).choice(vals, (nb + 2 * nbc, 64)))

@@ -10,6 +10,7 @@ import jpgx
 import oracle
 import san_build
 from conftest import PKG
+from jfif_inputs import nblocks  # noqa: F401  (the pixel tests use it as P.nblocks)
 
 QUALITIES = (1, 50, 90, 97)
 # (W, H) per sample mode: 8x8 (16x16 for 4:2:x) is one lane group; 136x16 is 17 blocks per row, a run
@@ -20,11 +21,6 @@ SIZES = {0: ((8, 8), (16, 16), (136, 16), (48, 32), (96, 64)),
          2: ((16, 16), (272, 16), (48, 32), (96, 64))}
 EXTREME = (32767, -32767, -32768)
 ENTRY = (1, 255, 65535)
-
-
-def nblocks(W, H, sr):
-    nb = (W // 8) * (H // 8)
-    return nb, (nb, nb // 2, nb // 4)[sr]
 
 
 @functools.lru_cache(maxsize=None)

@@ -15,48 +15,9 @@ import jpgx
 import jpgx.compat as C
 from conftest import GOLDEN, coef_sha
 from jfif_decode import decode
+from jfif_inputs import hand_made, lap as _lap, nblocks as _nblocks, stuffing_heavy
 
 HEADER, SCAN = jpgx.EJFIF_HEADER, jpgx.EJFIF_SCAN
-
-
-# ---- coefficient generators (restated from tests/test_jfif_gpu.py) -------------------------------
-def _nblocks(W, H, sr):
-    nb = (W // 8) * (H // 8)
-    return nb, (nb, nb // 2, nb // 4)[sr]
-
-
-def _lap(W, H, sr, seed, scale=6.0):
-    """laplacian AC, uniform DC in [-300, 300): [nb + 2 nbc][64] (for sr 0 that is [3][nb][64])"""
-    rng = np.random.default_rng(seed)
-    nb, nbc = _nblocks(W, H, sr)
-    coef = rng.laplace(0, scale, size=(nb + 2 * nbc, 64)).astype(np.int16)
-    coef[:, 0] = rng.integers(-300, 300, size=nb + 2 * nbc)
-    return np.ascontiguousarray(coef)
-
-
-def _hand_made(sr, W=64, H=32):
-    nb, nbc = _nblocks(W, H, sr)
-    coef = np.zeros((nb + 2 * nbc, 64), np.int16)
-    coef[1, 63] = 5                                  # three ZRLs, no EOB
-    coef[2, 63] = -1
-    coef[nb + 1, 63] = -700                          # the same in a chroma block
-    coef[3, 20] = -3                                 # one ZRL, a run of 3, EOB
-    coef[nb + nbc + 2, 20] = 1023
-    coef[5, 1:64] = 1                                # 63 codes, no EOB
-    coef[6, 16] = 1                                  # run of exactly 15: no ZRL
-    coef[7, 17] = 1                                  # run of exactly 16: ZRL + run 0
-    coef[8, 33] = 2000                               # AC clamp to 1023
-    coef[9, 33] = -2000
-    dcs = np.array([0, 2047, 0, -2047, 2047, -2048, 2047, 4000, -4000, 1, 0, 32767, -32768, 0], np.int16)
-    coef[10:10 + dcs.size, 0] = dcs                  # DC steps of +-2047 and beyond (the clamp)
-    coef[nb:nb + 4, 0] = [1500, -1500, 1500, -600]
-    return coef
-
-
-def _stuffing_heavy(sr, W=64, H=96):
-    nb, nbc = _nblocks(W, H, sr)
-    vals = np.array([0, 0, 0, 1, -1, 1023, -1023, 32767, -32768, 2047, -2047], np.int16)
-    return np.ascontiguousarray(np.random.default_rng(0).choice(vals, (nb + 2 * nbc, 64)))
 
 
 def _write(coef, W, H, q, sr, rr, optimize=False):
@@ -133,14 +94,14 @@ def test_one_block_and_one_mcu(W, H, sr):
 
 @pytest.mark.parametrize("sr", [0, 1, 2])
 def test_hand_made_blocks_and_clamped_input(sr):
-    coef = _hand_made(sr)
+    coef = hand_made(sr, 64, 32)[2]
     for rr, opt in ((0, False), (1, False), (2, True)):
         _check_against_independent(_write(coef, 64, 32, 50, sr, rr, opt))
 
 
 @pytest.mark.parametrize("sr", [0, 2])
 def test_stuffing_heavy_frame(sr):
-    data = _write(_stuffing_heavy(sr), 64, 96, 50, sr, 1)
+    data = _write(stuffing_heavy(sr, 64, 96)[3], 64, 96, 50, sr, 1)
     assert data.count(b"\xff\x00") >= 1000
     _check_against_independent(data, nthreads=3)
 

@@ -14,6 +14,7 @@ import jfif_san_cases as S
 import jpgx
 import jpgx.compat as C
 import pixels_cases as P
+from jfif_decode import decode
 
 gpu = pytest.mark.gpu
 FILL = 0x7A
@@ -200,6 +201,30 @@ def test_decode_jpeg(cuda, sr):
     with pytest.raises(jpgx.JpgxError) as e:
         jpgx.decode_jpeg(files[0][:-2], cuda)
     assert e.value.rc == jpgx.EJFIF_SCAN
+
+
+@gpu
+def test_frames_wider_than_high_and_higher_than_wide(cuda):
+    """48x16 and 16x48, 4:2:2 and 4:2:0, through encode_jpeg and decode_jpeg: the smallest frames whose
+    blocks per row and block rows differ for Y and for chroma alike, so that a frame field taken
+    for its neighbour (csrc/jx_frame.h: bw / bh, cbw / cbh) shows in the bytes or in the pixels"""
+    import torch
+    import oracle
+    for W, H in ((48, 16), (16, 48)):
+        rgb = torch.from_numpy(oracle.gen_splitmix(7 * W + H, W, H)).to(cuda)
+        for sr in (1, 2):
+            data = jpgx.encode_jpeg(rgb, 90, sample_ratio=sr, flags=jpgx.FLAG_SUBSAMPLE, restart_rows=1)
+            coef = jpgx.encode_blocks(rgb, 90, sr, flags=jpgx.FLAG_SUBSAMPLE).cpu().numpy()
+            assert data == C.write_jfif_ex(coef, W, H, 90, sr, restart_rows=1, nthreads=1), (W, H, sr)
+            r = C.read_jfif(data, 1)
+            assert (r["width"], r["height"], r["sample_ratio"]) == (W, H, sr)
+            # tests/jfif_decode.py places the blocks by its own reading of T.81, not by jx_frame.h
+            ind = decode(data)
+            assert (ind["width"], ind["height"], ind["sampling"]) == (W, H, (2, sr))
+            assert np.array_equal(np.concatenate([np.asarray(c).reshape(-1, 64) for c in ind["coef"]]), r["coef"])
+            got = jpgx.decode_jpeg(data, cuda)
+            assert got.shape == (H, W, 3)
+            assert np.array_equal(got.cpu().numpy(), C.pixels_host(r["coef"], W, H, sr, r["qt"], 2)), (W, H, sr)
 
 
 # ---- a captured graph ----------------------------------------------------------------------------------------
