@@ -115,6 +115,7 @@ int jx_plan_tables_mx(int quality, float w[24][8], float lim[24][8], int16_t q[2
 int jx_plan_tables_mx422(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
 int jx_plan_tables_mx420(int quality, float w[24][8], float lim[24][8], int16_t q[2][64]);
 int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8]);
+int jx_mxs_device_operands(uint16_t out[3][64][8]);   /* k_mxs's three device tiles (g_mxs_B) */
 int jx_mx422_operands(uint16_t ops[JX_MX_PARTS][4][64][8]);
 int jx_mx420_operands(uint16_t ops[JX_MX_PARTS][5][64][8]);
 long long jx_selftest_mx(long long nblocks, unsigned long long seed, int quality,

@@ -23,10 +23,12 @@
  *           row m = 4 jb + y, k = byte k of the pixel row (zero-extended: the f16 b 2^-24,
  *           exact, one v_perm per two bytes; k = 24 the bias 1.0).  One product with B = colour x
  *           cosine gives, in C row m, column j, the row transform of channel j/8 (Y, Cb),
- *           frequency u = j%8.  Cr: the two sets' K halves as independent products summed by
- *           one VALU add (B zero outside its set's columns), so column j of the Cr tile is set
- *           j/8's Cr at u = j%8.  B = Bh + Bl (two f16 parts); acc_h = A Bh is EXACT in any
- *           summation order (jpgx_plan.cpp); R = acc_h + acc_l (Bl encoded at Bh's scale).
+ *           frequency u = j%8.  Cr (k_mxs): one tile [Bh_cr | Bl_cr] per set and half gives acc_h
+ *           in columns 0..7 and acc_l in columns 8..15; a DPP add inside the 16-lane row merges
+ *           them so that column j is set j/8's Cr at u = j%8 (mxs_cr_rows; the 4:2:x kernels'
+ *           Y: the two sets' K halves chained, B zero outside its set's columns).  B = Bh + Bl
+ *           (two f16 parts); acc_h = A Bh is EXACT in any summation order (jpgx_plan.cpp);
+ *           R = acc_h + acc_l (Bl encoded at Bh's scale).
  *   Columns every lane then holds three whole columns (8 rows, registers 0..3 of the two
  *           halves): (set 0, c = j/8, u), (set 1, same), (Cr, set j/8, u).  Each runs jx_fdct8
  *           in scalar fp32 (the FOps code the band is derived for; no packed-fp32 instruction in
@@ -633,6 +635,31 @@ __device__ __forceinline__ void mx_combine(mx_f4 hl, mx_f4 ll, mx_f4 hh, mx_f4 l
     R[4] = lh.x + hh.x, R[5] = lh.y + hh.y, R[6] = lh.z + hh.z, R[7] = lh.w + hh.w;
 }
 
+/* k_mxs's Cr rows from the products with Bc = [Bh_cr | Bl_cr] (g_mxs_B[2]): x / y are one C
+ * register of the set-0 / set-1 tile, acc_h of u = j in lanes j = l % 16 < 8 and acc_l of u = j - 8
+ * in the others.  A lane's Cr column is (set j / 8, u = j % 8), so
+ *   j <  8: R = x[j] + x[j + 8]      j >= 8: R = y[j - 8] + y[j]
+ * -- in both halves fl(acc_h + acc_l), the single commutative fp32 add of mx_combine -- the other
+ * term through DPP row_ror:8, a rotation inside the 16-lane row (one C row group).  Two
+ * v_add_f32_dpp: the set-1 sum in every lane, then the set-0 sum over banks 0..1 (lanes j < 8) of
+ * the same register.  The second is inline asm (the compiler has no form for a masked DPP add); its
+ * source x is the OLDER product of the pair, so the compiler's wait states for the first add's read
+ * of y (the matrix pipe is in order) cover it, and `r` orders it behind that add. */
+__device__ __forceinline__ float mxs_cr_row(float x, float y)
+{
+    float r = y + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), 0x128, 0xf, 0xf, true));
+    asm("v_add_f32_dpp %0, %1, %1 row_ror:8 row_mask:0xf bank_mask:0x3" : "+v"(r) : "v"(x));
+    return r;
+}
+/* R rows 0..7 of a lane's Cr column from cx[set][half] (rows 0..3, 4..7) */
+__device__ __forceinline__ void mxs_cr_rows(const mx_f4 (&cx)[2][2], float (&R)[8])
+{
+    R[0] = mxs_cr_row(cx[0][0].x, cx[1][0].x), R[1] = mxs_cr_row(cx[0][0].y, cx[1][0].y);
+    R[2] = mxs_cr_row(cx[0][0].z, cx[1][0].z), R[3] = mxs_cr_row(cx[0][0].w, cx[1][0].w);
+    R[4] = mxs_cr_row(cx[0][1].x, cx[1][1].x), R[5] = mxs_cr_row(cx[0][1].y, cx[1][1].y);
+    R[6] = mxs_cr_row(cx[0][1].z, cx[1][1].z), R[7] = mxs_cr_row(cx[0][1].w, cx[1][1].w);
+}
+
 /* a column's scales from the workgroup table; t0 = 0 (4:4:4: Y|Cb, 4:2:x: Y) or 2 (4:4:4: Cr,
  * 4:2:x: chroma); its squared band limits are table t0 + 1 */
 struct MxW {
@@ -793,8 +820,9 @@ __device__ __forceinline__ void mx_column_t(const mx_f4 (&acc)[4], const MxW &t,
  * grid-stride layout drifts: instruction arbitration favours older waves,
  * profiles/r03_skeleton_wgrank.txt; the memory skeleton reads 0.72-0.76 non-persistent vs
  * 0.67-0.70 persistent, profiles/r04_*).  What a short wave needs is a cheap start:
- *   - its B operands (6 KiB, quality-independent, g_mxs_B) come from global memory (L2) into
- *     registers, then its pixel DMA for all three steps is issued (step k lives in slot k);
+ *   - its B operands (three tiles, 3 KiB, quality-independent, g_mxs_B) come from global memory
+ *     (L2) into 12 registers, then its pixel DMA for all three steps is issued (step k lives in
+ *     slot k);
  *   - this quality's scale / limit table with the hot-path band limits, the zig-zag positions and
  *     the exact pass's tables are one pre-laid-out image (g_mxs_img) that the workgroup's four
  *     waves copy into LDS with LDS-DMA (16-byte pieces), one s_barrier;
@@ -810,14 +838,16 @@ struct alignas(16) MxsLds {
     uint16_t task[8];                   /* inline exact batch                           */
 };
 static_assert(sizeof(MxsLds) % 16 == 0, "16-byte aligned LDS regions");
-/* the B operands (round 6): read by each wave from global memory (L2) into registers at its start,
- * [part * 3 + which] = Y|Cb, Cr set 0, Cr set 1 (zero in columns 8..15 / 0..7) -- no zeroing VALU
- * per step, no reload after an exact pass, and a 4-KiB smaller workgroup image (rounds 4b-5 kept
- * them in the image: 105.1 vs 106.0 us per launch on one box, profiles/r06_b_operands.txt; round 4b's
- * wrong C rows 12..15 with B from global memory were the packed-fp32 fault of DESIGN.md 4.3f) */
+/* the B operands (round 6): read by each wave from global memory (L2) into registers at its start
+ * -- no reload after an exact pass, and a smaller workgroup image (rounds 4b-5 kept them in the
+ * image: 105.1 vs 106.0 us per launch on one box, profiles/r06_b_operands.txt; round 4b's wrong C
+ * rows 12..15 with B from global memory were the packed-fp32 fault of DESIGN.md 4.3f).  Three
+ * tiles, 3 KiB and 12 VGPRs per wave (jx_mxs_device_operands derives them from the plan's six):
+ * [0] Y|Cb hi, [1] Y|Cb lo, [2] Bc = Cr hi in C columns 0..7 | Cr lo in columns 8..15 -- no tile
+ * holds a zero half, and the Cr matrix is there once (profiles/mxs_cr_tile.txt) */
+__device__ mx_u4 g_mxs_B[3][64];
 /* the workgroup image: scale / limit table, hot-path limits (mx_limc) per lane profile and column
  * kind, zig-zag positions, the exact pass's tables */
-__device__ mx_u4 g_mxs_B[3 * JX_MX_PARTS][64];
 struct alignas(16) MxsImg {
     MxsTab tab;
     float limc[2][16];
@@ -934,11 +964,9 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     MxsLds &L = s_lds[wave];
-    mx_u4 B[kParts][3];                          /* older than every DMA of the wave */
+    mx_u4 B[3];                                  /* older than every DMA of the wave */
 #pragma unroll
-    for (int p = 0; p < kParts; p++)
-#pragma unroll
-        for (int w = 0; w < 3; w++) B[p][w] = g_mxs_B[3 * p + w][lane];
+    for (int w = 0; w < 3; w++) B[w] = g_mxs_B[w][lane];
     /* the image into LDS (LDS-DMA: piece p of thread t lands at 16 p) */
     {
         const uint8_t *img = (const uint8_t *)&g_mxs_img[g.force ? 1 : 0][g.quality];
@@ -1020,12 +1048,12 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
         __builtin_amdgcn_sched_barrier(0);
         const mx_f4 z = {};
         uint32_t fl = 0;
-        mx_f4 acc[3][4];
+        mx_f4 acc[2][4];
         const auto mma_set = [&](mx_f4(&o)[4], const mx_h8 &Alo, const mx_h8 &Ahi) __attribute__((always_inline)) {
-            o[0] = mx_mma(Alo, B[0][0], z);
-            o[2] = mx_mma(Ahi, B[0][0], z);
-            o[1] = mx_mma(Alo, B[1][0], z);
-            o[3] = mx_mma(Ahi, B[1][0], z);
+            o[0] = mx_mma(Alo, B[0], z);
+            o[2] = mx_mma(Ahi, B[0], z);
+            o[1] = mx_mma(Alo, B[1], z);
+            o[3] = mx_mma(Ahi, B[1], z);
         };
         mma_set(acc[0], A00, A01);
         __builtin_amdgcn_sched_barrier(0);
@@ -1033,29 +1061,21 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
         __builtin_amdgcn_sched_barrier(0);
         mx_column_t<0>(acc[0], w0, limc0, tb, 0, j, za, fl, 0);
         __builtin_amdgcn_sched_barrier(0);
-        /* the Cr tile: the two sets' K halves as eight independent products and one VALU add per
-         * element, cr[0] + cr[1] -- bit-identical to a chained form, since in every column one of
-         * the two halves is an exact zero (B1 is zero in columns 8..15, B2 in 0..7) -- so no
-         * product of k_mxs waits in the matrix pipe for another; the products
-         * are issued in source order (cr[1][3] last: the fence) */
-        mx_f4 cr[2][4];
-        cr[0][0] = mx_mma(A00, B[0][1], z);
+        /* the Cr tile: four independent full-width products with Bc = [Bh_cr | Bl_cr] -- cx[s][h]
+         * holds, for set s and row half h, acc_h of u = j in columns j < 8 and acc_l of u = j - 8 in
+         * columns j >= 8 (mxs_cr_rows merges them) -- so no product of k_mxs multiplies stored
+         * zeros or waits in the matrix pipe for another; the products are issued
+         * in source order (cx[1][1] last: the fence) */
+        mx_f4 cx[2][2];
+        cx[0][0] = mx_mma(A00, B[2], z);
         __builtin_amdgcn_sched_barrier(0);
-        cr[0][2] = mx_mma(A01, B[0][1], z);
+        cx[0][1] = mx_mma(A01, B[2], z);
         __builtin_amdgcn_sched_barrier(0);
-        cr[0][1] = mx_mma(A00, B[1][1], z);
+        cx[1][0] = mx_mma(A10, B[2], z);
         __builtin_amdgcn_sched_barrier(0);
-        cr[0][3] = mx_mma(A01, B[1][1], z);
+        cx[1][1] = mx_mma(A11, B[2], z);
         __builtin_amdgcn_sched_barrier(0);
-        cr[1][0] = mx_mma(A10, B[0][2], z);
-        __builtin_amdgcn_sched_barrier(0);
-        cr[1][2] = mx_mma(A11, B[0][2], z);
-        __builtin_amdgcn_sched_barrier(0);
-        cr[1][1] = mx_mma(A10, B[1][2], z);
-        __builtin_amdgcn_sched_barrier(0);
-        cr[1][3] = mx_mma(A11, B[1][2], z);
-        __builtin_amdgcn_sched_barrier(0);
-        mx_column_t<4 * kBSs>(acc[1], w0, limc0, tb, 0, j, za, fl, 1, &cr[1][3]);
+        mx_column_t<4 * kBSs>(acc[1], w0, limc0, tb, 0, j, za, fl, 1, &cx[1][1]);
         __builtin_amdgcn_sched_barrier(0);
         const uint8_t *const ob = (const uint8_t *)S.dst;
         /* the launch's last step: flags of its clamped copies are dropped (never stored) */
@@ -1078,7 +1098,7 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
         };
         const bool early = S.simple && __ballot((fl & 0xffffu) != 0) == 0;
         if (early) {
-            mx_fence(cr[1][3]);                        /* the Cr products are done (operand rule) */
+            mx_fence(cx[1][1]);                        /* the Cr products are done (operand rule) */
             mx_wave_sync();
             const mx_u4 v0 = *(const mx_u4 *)(L.stage + ro);
             const mx_u4 v1 = *(const mx_u4 *)(L.stage + rcb);
@@ -1086,11 +1106,12 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
             __builtin_nontemporal_store(v1, (mx_u4 *)(ob + so1));
         }
         __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; i++)                    /* scalar adds (no packed fp32, mx_unpack8) */
-            acc[2][i] = mx_f4{cr[0][i].x + cr[1][i].x, cr[0][i].y + cr[1][i].y, cr[0][i].z + cr[1][i].z,
-                              cr[0][i].w + cr[1][i].w};
-        mx_column_t<8 * kBSs, true>(acc[2], w0, limc2, tb, 2, j, za, fl, 2);
+        {
+            float R[8];
+            mxs_cr_rows(cx, R);
+            __builtin_amdgcn_sched_barrier(0);         /* the scales are read after the tiles (lazy) */
+            mx_column_r<8 * kBSs>(R, mx_w(tb, 2, j), limc2, tb, 2, j, za, fl, 2);
+        }
         mx_wave_sync();
         if (__builtin_expect(__ballot(fl != 0) != 0, 0)) {
             clamp(fl);
@@ -2155,7 +2176,8 @@ void mx_ex_tab(MxExTab &x, const jx_mxtab &t)
 typedef uint16_t mx_tile[64][8];
 
 /* k_mxs: 4:4:4 / reference-parity output.  The table is Y|Cb at 16 lane profiles with Cr compacted
- * to 8 (MxsTab); the operands stay outside the image (g_mxs_B: Y|Cb, Cr set 0, Cr set 1). */
+ * to 8 (MxsTab); the operands stay outside the image (g_mxs_B: Y|Cb hi, Y|Cb lo and the Cr tile
+ * [hi | lo], derived from the plan's six tiles where they land on the device). */
 struct MxsK {
     typedef MxsImg Img;
     static constexpr const char *name = "k_mxs";
@@ -2174,9 +2196,12 @@ struct MxsK {
                     if (jp < 8) I.tab.cr[tt][h][jp] = full.wl[2 + tt][h][jp];
                 }
     }
-    static hipError_t upload_operands(const mx_tile *ops)
+    static hipError_t upload_operands(const mx_tile *)
     {
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_mxs_B), ops, sizeof(mx_tile) * tiles * JX_MX_PARTS);
+        std::vector<uint16_t> dev(sizeof(mx_tile) / sizeof(uint16_t) * 3);      /* heap: reentrant */
+        static_assert(sizeof(g_mxs_B) == 3 * sizeof(mx_tile), "the three device tiles");
+        if (jx_mxs_device_operands((mx_tile *)dev.data())) return hipErrorInvalidValue;
+        return hipMemcpyToSymbol(HIP_SYMBOL(g_mxs_B), dev.data(), sizeof(g_mxs_B));
     }
 };
 

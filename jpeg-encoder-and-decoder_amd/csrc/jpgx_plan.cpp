@@ -528,8 +528,9 @@ extern "C" int jx_mx_loexp(void) { return JX_MX_LOEXP; }
 
 /* k_mxs's operands, 3 * part + which; lane l holds B[k = 8 (l >> 4) + e][plan column of l & 15].
  * which 0 = columns j = 8c + u for c = Y, Cb; 1 = Cr at u = j for j < 8, zero columns j >= 8;
- * 2 = zero columns j < 8, Cr at u = j - 8 for j >= 8 (the kernel sums A_set0 B1 + A_set1 B2: the
- * two sets concatenated along K) */
+ * 2 = zero columns j < 8, Cr at u = j - 8 for j >= 8 (the six-tile form sums A_set0 B1 + A_set1 B2:
+ * the two sets concatenated along K; tests/test_mx_pins.py pins it, k_mxs itself runs the three
+ * tiles jx_mxs_device_operands derives from it) */
 extern "C" int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8])
 {
     MxSplitPtr S(new MxSplit);
@@ -546,6 +547,26 @@ extern "C" int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8])
                     else if (which == 2 && j >= 8) n = 16 + j - 8;
                     ops[3 * part + which][l][e] = n >= 0 ? S->bits(part, k, n) : 0;
                 }
+    return JPGX_OK;
+}
+
+/* What k_mxs keeps on the device (g_mxs_B), derived from the six tiles above: 0 = Y|Cb hi
+ * (ops[0]), 1 = Y|Cb lo (ops[3]), 2 = Bc = [Bh_cr | Bl_cr], the Cr matrix's hi part in C columns
+ * 0..7 and its lo part in columns 8..15 -- lane for lane ops[3 * 0 + 1] where l % 16 < 8 and
+ * ops[3 * 1 + 2] elsewhere (the set-1 tile is the same matrix shifted by eight columns).  One
+ * product A Bc gives acc_h in columns 0..7 and acc_l in columns 8..15 of the same set's Cr. */
+static_assert(JX_MX_PARTS == 2, "k_mxs's Cr tile holds one hi and one lo part");
+extern "C" int jx_mxs_device_operands(uint16_t out[3][64][8])
+{
+    std::unique_ptr<uint16_t[][64][8]> ops(new uint16_t[3 * JX_MX_PARTS][64][8]);
+    const int rc = jx_mx_operands(ops.get());
+    if (rc) return rc;
+    for (int l = 0; l < 64; l++)
+        for (int e = 0; e < 8; e++) {
+            out[0][l][e] = ops[0][l][e];
+            out[1][l][e] = ops[3][l][e];
+            out[2][l][e] = (l & 15) < 8 ? ops[3 * 0 + 1][l][e] : ops[3 * 1 + 2][l][e];
+        }
     return JPGX_OK;
 }
 
