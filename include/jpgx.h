@@ -255,6 +255,29 @@ int jpgx_jfif_decode_gpu(const uint8_t *d_files, size_t file_stride, const uint6
                          size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status,
                          void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* A flag of jpgx_jfif_decode_gpu_ex: decode inside the restart intervals.  A
+ * workgroup of 256 lanes takes an interval; its lanes start at guessed places sub_bytes apart, hand
+ * their exit states on until these are the sequential decoder's, and then write.  A file without
+ * DRI is decoded by one workgroup instead of one lane. */
+#define JPGX_JFIF_DECODE_SUBINTERVAL 1u
+
+/* jpgx_jfif_decode_gpu with decode_flags.  0: exactly jpgx_jfif_decode_gpu_workspace_size /
+ * jpgx_jfif_decode_gpu (the same size, outputs and launches).  JPGX_JFIF_DECODE_SUBINTERVAL: the
+ * contract above holds as it stands -- the checks and their order, all before the first device
+ * call; d_status[f] jpgx_read_jfif's return for the same bytes; a status-0 frame's coefficients
+ * and tables the host's; no write outside a frame's elements, no read outside a file's bytes;
+ * asynchronous, capturable, stateless, no memset -- with another kernel in the place of the scan.
+ * Unknown flag bits: JPGX_EARG (size 0 from the size query).
+ * jpgx_jfif_decode_sub_shape: the kernel's bytes per subsequence and subsequences per tile. */
+size_t jpgx_jfif_decode_gpu_workspace_size_ex(int width, int height, int sample_ratio,
+                                              size_t nframes, size_t file_cap, unsigned decode_flags);
+int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len,
+                            size_t nframes, int width, int height, int sample_ratio,
+                            unsigned decode_flags, int16_t *d_coef, size_t coef_frame_stride,
+                            uint16_t *d_qt, int32_t *d_status, void *d_workspace,
+                            size_t workspace_bytes, void *stream);
+void jpgx_jfif_decode_sub_shape(uint32_t *sub_bytes, uint32_t *tile_subs);
+
 /* The pixel half of the way back: coefficients to interleaved RGB, entirely on the
  * device.  The pixels are those of libjpeg's default decoder for the same coefficients and tables:
  * the 13-bit fixed-point ("islow") inverse DCT, the triangle-filter ("fancy") chroma upsampling for

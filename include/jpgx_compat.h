@@ -219,6 +219,26 @@ int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info);
 int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap,
                    uint16_t qt[2][64], jpgx_jfif_info *info);
 
+/* The host twin of the device decoder that works inside a restart interval (include/jpgx.h:
+ * JPGX_JFIF_DECODE_SUBINTERVAL).  It runs the routines the kernel runs
+ * (csrc/jx_jfif_sub.h), lane after lane, round after round and tile after tile, on one thread: an
+ * interval's bytes cut into subsequences of sub_bytes bytes and tiles of tile_subs subsequences
+ * (sub_bytes >= 16, tile_subs >= 2, their product at most 2^24, else JPGX_EARG; 0, 0: the kernel's
+ * shape, jpgx_jfif_decode_sub_shape).  Arguments, outputs and returns are jpgx_read_jfif's, for
+ * every input and every shape.  stats (may be NULL) counts what the mechanism did. */
+typedef struct jpgx_jfif_sub_stats {
+    uint64_t subsequences, tiles, /* decoded; loaded                                              */
+        rounds_max,               /* the most rounds a tile took before no lane changed its entry */
+        redecodes,                /* subsequences decoded again in a round                        */
+        wrong_first_guesses,      /* lanes whose guess did not lead to the exit state they ended with */
+        starts_on_stuffing,       /* guesses moved off a stuffed 00                               */
+        units_across_sub,         /* units whose last bit lies past their subsequence ...         */
+        units_across_tile;        /* ... and past their tile                                      */
+} jpgx_jfif_sub_stats;
+int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs,
+                       int16_t *coef, size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info,
+                       jpgx_jfif_sub_stats *stats);
+
 /* The host twin of jpgx_pixels_gpu (include/jpgx.h): one frame's coefficients, in
  * the layout jpgx_read_jfif returns, and its two zig-zag tables -> interleaved top-down RGB rows
  * `pitch` bytes apart (only bytes [0, 3 width) of a row are written).  The same arithmetic from the

@@ -30,6 +30,7 @@ HORIZONTAL_VERTICAL_SUBSAMPLING = 2
 FLAG_FORCE_EXACT = 1
 FLAG_SUBSAMPLE = 2      # true 4:2:2 / 4:2:0 chroma (extension; see include/jpgx.h)
 JFIF_OPTIMIZE = 1       # a flag of the JFIF writers: per-image Huffman tables (JPGX_JFIF_OPTIMIZE)
+JFIF_DECODE_SUBINTERVAL = 1     # a flag of the device decoder: decode inside the restart intervals
 
 OK, EGEOMETRY, EQUALITY, ESAMPLE, EARG, EHIP, EWORKSPACE, ENODEV, ENOMEM = 0, -1, -2, -3, -4, -5, -6, -7, -8
 EJFIF_HEADER, EJFIF_SCAN = -9, -10      # the JFIF decoder's two refusals (include/jpgx.h)
@@ -51,6 +52,7 @@ EXPORTS = [
     "jpgx_jfif_gpu_workspace_size", "jpgx_jfif_gpu",
     "jpgx_jfif_gpu_workspace_size_ex", "jpgx_jfif_gpu_ex",
     "jpgx_jfif_decode_gpu_workspace_size", "jpgx_jfif_decode_gpu",
+    "jpgx_jfif_decode_gpu_workspace_size_ex", "jpgx_jfif_decode_gpu_ex", "jpgx_jfif_decode_sub_shape",
     "jpgx_pixels_gpu_workspace_size", "jpgx_pixels_gpu", "jpgx_jfif_qt",
 ]
 COMPAT_EXPORTS = [
@@ -61,7 +63,7 @@ COMPAT_EXPORTS = [
     "jpgx_free", "jpgx_encode_bmp", "jpgx_jfif_bound", "jpgx_write_jfif",
     "jpgx_encode_bmp_to_jpeg", "jpgx_write_jfif_sub", "jpgx_encode_bmp_to_jpeg_ex",
     "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex", "jpgx_write_jfif_opt",
-    "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_pixels_host",
+    "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host",
 ]
 
 
@@ -134,6 +136,11 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_decode_gpu_workspace_size.argtypes = [i, i, i, sz, sz]
     L.jpgx_jfif_decode_gpu_workspace_size.restype = sz
     L.jpgx_jfif_decode_gpu.argtypes = [vp, sz, vp, sz, i, i, i, vp, sz, vp, vp, vp, sz, vp]
+    L.jpgx_jfif_decode_gpu_workspace_size_ex.argtypes = [i, i, i, sz, sz, ctypes.c_uint]
+    L.jpgx_jfif_decode_gpu_workspace_size_ex.restype = sz
+    L.jpgx_jfif_decode_gpu_ex.argtypes = [vp, sz, vp, sz, i, i, i, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp]
+    L.jpgx_jfif_decode_sub_shape.argtypes = [vp, vp]
+    L.jpgx_jfif_decode_sub_shape.restype = None
     L.jpgx_pixels_gpu_workspace_size.argtypes = [i, i, i, sz]
     L.jpgx_pixels_gpu_workspace_size.restype = sz
     L.jpgx_pixels_gpu.argtypes = [vp, sz, sz, i, i, i, vp, sz, vp, vp, sz, sz, vp, sz, vp]
@@ -415,7 +422,16 @@ def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restar
     return out[0, :n].cpu().numpy().tobytes()
 
 
-def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 0, stream=None):
+def jfif_decode_sub_shape() -> tuple[int, int]:
+    """(bytes per subsequence, subsequences per tile) of the decoder that works inside a restart
+    interval (jpgx_jfif_decode_sub_shape)."""
+    s, t = ctypes.c_uint32(), ctypes.c_uint32()
+    lib.jpgx_jfif_decode_sub_shape(ctypes.addressof(s), ctypes.addressof(t))
+    return s.value, t.value
+
+
+def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 0, stream=None,
+                    subinterval: bool = False):
     """The coefficients of a batch of baseline JFIF files in device memory (jpgx_jfif_decode_gpu;
     entropy decoding only): d_files uint8 [nframes][cap] and lens int64 [nframes] as jfif_gpu returns
     them, every file of the stated width, height and sample_ratio ->
@@ -423,7 +439,9 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
     on the device.  Frame f's layout is encode_blocks' ([3][nb][64] viewed as [3 nb][64] for
     sample_ratio 0, Y | Cb | Cr for 1, 2); status[f] is 0, EJFIF_HEADER or EJFIF_SCAN, what
     compat.read_jfif reports for the same bytes; a frame with a nonzero status has unspecified
-    coefficients.  Nothing is copied to the host and nothing waits."""
+    coefficients.  Nothing is copied to the host and nothing waits.  subinterval:
+    JFIF_DECODE_SUBINTERVAL, a workgroup per restart interval instead of a lane (jpgx_jfif_decode_gpu_ex;
+    DESIGN.md 4.8a): the same outputs, faster where intervals are long or few."""
     import torch
     for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -443,22 +461,24 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
     coef = torch.empty((nf, nb + 2 * nbc, 64), dtype=torch.int16, device=dev)
     qt = torch.empty((nf, 2, 64), dtype=torch.uint16, device=dev)
     status = torch.empty(nf, dtype=torch.int32, device=dev)
-    need = int(lib.jpgx_jfif_decode_gpu_workspace_size(width, height, sample_ratio, nf, fstride))
+    dflags = JFIF_DECODE_SUBINTERVAL if subinterval else 0
+    need = int(lib.jpgx_jfif_decode_gpu_workspace_size_ex(width, height, sample_ratio, nf, fstride, dflags))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    _check(lib.jpgx_jfif_decode_gpu(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, sample_ratio,
-                                    coef.data_ptr(), (nb + 2 * nbc) * 64, qt.data_ptr(), status.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu")
+    _check(lib.jpgx_jfif_decode_gpu_ex(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, sample_ratio,
+                                       dflags, coef.data_ptr(), (nb + 2 * nbc) * 64, qt.data_ptr(), status.data_ptr(),
+                                       ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu")
     if stream is not None:
         ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
     return coef, qt, status
 
 
-def decode_jpeg_coefficients(data: bytes, device):
+def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False):
     """One baseline JFIF file in host memory -> its coefficients on `device`: the header walk on the
     host for the geometry (compat.jfif_info), one host-to-device copy of the bytes, jfif_decode_gpu.
     Returns compat.read_jfif's dict with device tensors: coef int16 ([3][nb][64] for 4:4:4,
     [nb + 2 nbc][64] otherwise), qt uint16 [2][64], width, height, sample_ratio, restart_interval.
-    Raises JpgxError on a nonzero status (that reads the status back, a synchronisation)."""
+    Raises JpgxError on a nonzero status (that reads the status back, a synchronisation).
+    subinterval: as jfif_decode_gpu's."""
     import torch
     from . import compat
     info = compat.jfif_info(data)
@@ -468,7 +488,8 @@ def decode_jpeg_coefficients(data: bytes, device):
     host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
     d_files = host.to(dev).reshape(1, -1)
     lens = torch.tensor([len(data)], dtype=torch.int64, device=dev)
-    coef, qt, status = jfif_decode_gpu(d_files, lens, info["width"], info["height"], info["sample_ratio"])
+    coef, qt, status = jfif_decode_gpu(d_files, lens, info["width"], info["height"], info["sample_ratio"],
+                                       subinterval=subinterval)
     _check(int(status[0]), "jpgx_jfif_decode_gpu")
     out = coef[0].reshape(3, -1, 64) if info["sample_ratio"] == 0 else coef[0]
     return dict(coef=out, qt=qt[0], width=info["width"], height=info["height"],
@@ -529,13 +550,14 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     return out.view(nf, height, pitch)[:, :, :3 * width].unflatten(2, (width, 3))
 
 
-def decode_jpeg(data, device):
+def decode_jpeg(data, device, subinterval: bool = False):
     """Baseline JFIF file(s) in host memory -> RGB on `device`: decode_jpeg_coefficients' header step
     on the host for the geometry, one host-to-device copy of the bytes, then jfif_decode_gpu and
     pixels_gpu on one stream; the coefficients never leave the device.  data: bytes -> uint8 [H][W][3];
     a list of files of one geometry -> [n][H][W][3].  The pixels are libjpeg's default decoder's.
     Raises JpgxError for a frame whose status is nonzero (that reads the statuses back, a
-    synchronisation)."""
+    synchronisation).  subinterval: as jfif_decode_gpu's; the choice for files without restart
+    intervals, which one lane decodes otherwise."""
     import torch
     from . import compat
     single = isinstance(data, (bytes, bytearray, memoryview))
@@ -553,7 +575,7 @@ def decode_jpeg(data, device):
         host[k, :len(f)] = np.frombuffer(f, np.uint8)
     d_files = torch.from_numpy(host).to(dev)
     lens = torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
-    coef, qt, status = jfif_decode_gpu(d_files, lens, W, H, sr)
+    coef, qt, status = jfif_decode_gpu(d_files, lens, W, H, sr, subinterval=subinterval)
     rgb = pixels_gpu(coef, W, H, sr, d_qt=qt, status=status)
     for rc in status.cpu().tolist():
         _check(int(rc), "jpgx_jfif_decode_gpu")

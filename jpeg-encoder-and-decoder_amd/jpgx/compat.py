@@ -103,6 +103,8 @@ def _setup(L):
 
     L.jpgx_jfif_info_of.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(JfifInfo)]
     L.jpgx_read_jfif.argtypes = [vp, ctypes.c_size_t, i, vp, ctypes.c_size_t, vp, ctypes.POINTER(JfifInfo)]
+    L.jpgx_read_jfif_sub.argtypes = [vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_size_t, vp,
+                                     ctypes.POINTER(JfifInfo), vp]
     L.jpgx_pixels_host.argtypes = [vp, i, i, i, vp, vp, ctypes.c_size_t, i]
 
 
@@ -320,6 +322,31 @@ def read_jfif(data, nthreads: int = 1) -> dict:
         coef = coef.reshape(3, info["nb_y"], 64)
     return dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
                 sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
+
+
+class JfifSubStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in (
+        "subsequences", "tiles", "rounds_max", "redecodes", "wrong_first_guesses", "starts_on_stuffing",
+        "units_across_sub", "units_across_tile")]
+
+
+def read_jfif_sub(data, sub_bytes: int = 0, tile_subs: int = 0) -> dict:
+    """jpgx_read_jfif_sub: read_jfif by the routines of the device decoder that works inside a restart
+    interval, subsequences of sub_bytes bytes and tiles of tile_subs subsequences
+    (0, 0: the kernel's shape).  read_jfif's dict and `stats`, a dict of the twin's counters."""
+    info = jfif_info(data)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    nblk = info["nb_y"] + 2 * info["nb_c"]
+    coef = np.empty((nblk, 64), np.int16)
+    qt = np.zeros((2, 64), np.uint16)
+    got, stats = JfifInfo(), JfifSubStats()
+    _check(lib.jpgx_read_jfif_sub(buf.ctypes.data, len(buf), sub_bytes, tile_subs, coef.ctypes.data, coef.size,
+                                  qt.ctypes.data, ctypes.byref(got), ctypes.byref(stats)), "jpgx_read_jfif_sub")
+    if info["sample_ratio"] == 0:
+        coef = coef.reshape(3, info["nb_y"], 64)
+    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
+                sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"],
+                stats={n: int(getattr(stats, n)) for n, _ in JfifSubStats._fields_})
 
 
 def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt: np.ndarray,

@@ -30,6 +30,16 @@ coder writes from the same coefficients and writes profiles/jfif_gpu_dec.json; p
   device_over_host   decode time (median) / host_route_s: above 1, the host route is the faster one
   intervals       restart intervals of the batch = the lanes that work
   coefficients_equal   every frame's status 0 and its coefficients == the ones that were coded
+With --decode --subinterval the run times the decoder that works inside a restart interval
+(JPGX_JFIF_DECODE_SUBINTERVAL, jpgx_jfif_decode_gpu_ex) against flags 0 in the same
+process on the same files and writes profiles/jfif_gpu_dec_sub.json; per input:
+  decode_us, decode_sub_us    flags 0 and the flag per batch (events, as above; all rounds, sorted)
+  sub_slowest_over_plain_fastest   below 1: the flag's slowest round beats the fastest of flags 0
+  coder_us, sub_over_coder    the coder's time for the same files and the flag's median over it
+  host_route_s, plain_over_host, sub_over_host   the host route as above
+  coefficients_equal          statuses 0 and coefficients == the coded ones, both ways, before and after
+and once, for the photo-like input: "no_dri", its first frame recoded without restart intervals by
+the host writer, decoded both ways (1 call per round, 3 rounds: flags 0 is one lane's work).
 With --pixels the run times the pixel half of the way back (jpgx_pixels_gpu) on the
 transform's own coefficients with jpgx_jfif_qt's tables and writes profiles/jfif_gpu_px.json; per
 input and sample mode (4:4:4, and true 4:2:2 / 4:2:0 from JPGX_FLAG_SUBSAMPLE):
@@ -41,7 +51,7 @@ input and sample mode (4:4:4, and true 4:2:2 / 4:2:0 from JPGX_FLAG_SUBSAMPLE):
   host_route_s    the route without it: the coefficients copied to pinned host memory +
                   jpgx_pixels_host on 16 threads, frame after frame; best of 2 (host_route_d2h_s: the copy)
   pixels_equal    every frame == jpgx_pixels_host, before and after the timed calls
-Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode | --pixels] [OUT.json]"""
+Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels] [OUT.json]"""
 import json
 import os
 import sys
@@ -285,6 +295,110 @@ def measure_dec(name, d_rgb, dev):
     }
 
 
+def measure_dec_sub(name, d_rgb, dev):
+    nb = (W // 8) * (H // 8)
+    per = 3 * nb * 64
+    SUB = jpgx.JFIF_DECODE_SUBINTERVAL
+    coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+    p = jpgx.default_params(W, H, Q, 0)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+    jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+    torch.cuda.synchronize()
+    _, lens = jpgx.jfif_gpu(coef, W, H, Q, 0, 1, cap=1 << 20)
+    cap = (int(lens.max()) + 4095) // 4096 * 4096
+    files = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+    lens = torch.empty(F, dtype=torch.int64, device=dev)
+    cwsb = int(jpgx.lib.jpgx_jfif_gpu_workspace_size(W, H, 0, 1, F, cap))
+    cws = torch.empty(cwsb, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def coder():
+        rc = jpgx.lib.jpgx_jfif_gpu(coef.data_ptr(), per, F, W, H, Q, 0, 1, files.data_ptr(), cap, cap,
+                                    lens.data_ptr(), cws.data_ptr(), cwsb, stream)
+        assert rc == 0, rc
+
+    coder()
+    torch.cuda.synchronize()
+    n = lens.cpu().numpy()
+    assert (n > 0).all(), n
+    t_coder = timed(coder)
+
+    def decoder(d_files, stride, d_lens, nf, flags):
+        back = torch.empty((nf, per), dtype=torch.int16, device=dev)
+        qt = torch.empty((nf, 2, 64), dtype=torch.uint16, device=dev)
+        status = torch.empty(nf, dtype=torch.int32, device=dev)
+        wsb = int(jpgx.lib.jpgx_jfif_decode_gpu_workspace_size_ex(W, H, 0, nf, stride, flags))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+        def dec():
+            rc = jpgx.lib.jpgx_jfif_decode_gpu_ex(d_files.data_ptr(), stride, d_lens.data_ptr(), nf, W, H, 0, flags,
+                                                  back.data_ptr(), per, qt.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                                                  wsb, stream)
+            assert rc == 0, rc
+
+        def equal():
+            return bool((status == 0).all()) and bool(torch.equal(back, coef[:nf]))
+        return dec, equal, back
+
+    res = {"input": name, "file_bytes_per_frame": [int(x) for x in n], "intervals": F * (H // 8),
+           "sub_shape": list(jpgx.jfif_decode_sub_shape()), "coder_us": t_coder}
+    ok = True
+    for key, flags in (("decode_us", 0), ("decode_sub_us", SUB)):
+        dec, equal, back = decoder(files, cap, lens, F, flags)
+        back.fill_(0x5A5A)
+        dec()
+        torch.cuda.synchronize()
+        ok = ok and equal()
+        res[key] = timed(dec)
+        ok = ok and equal()
+        del back
+    res["sub_slowest_over_plain_fastest"] = res["decode_sub_us"][-1] / res["decode_us"][0]
+    res["sub_over_plain"] = res["decode_sub_us"][2] / res["decode_us"][2]
+    res["sub_over_coder"] = res["decode_sub_us"][2] / t_coder[2]
+    res["gpx_per_s_sub"] = F * W * H / res["decode_sub_us"][0] / 1e3
+
+    pinned = torch.empty((F, cap), dtype=torch.uint8).pin_memory()
+    host_s, host_equal = [], True
+    hc = coef.cpu().numpy()
+    got = [np.empty(per, np.int16) for _ in range(F)]
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pinned.copy_(files)
+        torch.cuda.synchronize()
+        for f in range(F):
+            rc = jpgx.lib.jpgx_read_jfif(pinned.data_ptr() + f * cap, int(n[f]), HOST_THREADS, got[f].ctypes.data,
+                                         per, None, None)
+            assert rc == 0, rc
+        host_s.append(time.perf_counter() - t0)
+        host_equal = host_equal and all(np.array_equal(got[f], hc[f]) for f in range(F))
+    res.update(host_route_s=min(host_s), host_threads=HOST_THREADS,
+               plain_over_host=res["decode_us"][2] * 1e-6 / min(host_s),
+               sub_over_host=res["decode_sub_us"][2] * 1e-6 / min(host_s))
+
+    if name.startswith("flat"):
+        one = C.write_jfif(hc[0].reshape(3, nb, 64), W, H, Q)
+        assert C.jfif_info(one)["restart_interval"] == 0
+        d_one = torch.from_numpy(np.frombuffer(one, np.uint8).copy()).to(dev).reshape(1, -1)
+        d_len = torch.tensor([len(one)], dtype=torch.int64, device=dev)
+        no_dri = {"file_bytes": len(one)}
+        for key, flags in (("decode_us", 0), ("decode_sub_us", SUB)):
+            dec, equal, back = decoder(d_one, len(one), d_len, 1, flags)
+            back.fill_(0x5A5A)
+            dec()
+            torch.cuda.synchronize()
+            ok = ok and equal()
+            no_dri[key] = timed(dec, calls=1, rounds=3, settle=0.0)
+            ok = ok and equal()
+            del back
+        no_dri["sub_over_plain"] = no_dri["decode_sub_us"][1] / no_dri["decode_us"][1]
+        res["no_dri"] = no_dri
+    res.update(coefficients_equal=bool(ok), host_coefficients_equal=bool(host_equal),
+               bytes_equal=bool(ok and host_equal), repeat_equal=bool(ok))
+    return res
+
+
 def measure_px(name, d_rgb, dev):
     nb = (W // 8) * (H // 8)
     qt_host = jpgx.jfif_qt(Q)
@@ -357,16 +471,18 @@ def measure_px(name, d_rgb, dev):
 
 
 def main():
-    modes = ("--optimize", "--decode", "--pixels")
+    modes = ("--optimize", "--decode", "--pixels", "--subinterval")
     args = [a for a in sys.argv[1:] if a not in modes]
-    optimize, decoding, pixels = (m in sys.argv[1:] for m in modes)
-    run = measure_px if pixels else measure_dec if decoding else measure_opt if optimize else measure
+    optimize, decoding, pixels, sub = (m in sys.argv[1:] for m in modes)
+    assert decoding or not sub, "--subinterval goes with --decode"
+    run = measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
+        measure_opt if optimize else measure
     dst = args[0] if args else os.path.join(
-        REPO, "profiles", "jfif_gpu_px.json" if pixels else "jfif_gpu_dec.json" if decoding else
-        "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
+        REPO, "profiles", "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
+        "jfif_gpu_dec.json" if decoding else "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py" + (" --pixels" if pixels else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
