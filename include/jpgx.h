@@ -310,6 +310,54 @@ int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nfra
                     uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
                     void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- files of any width and height --------------------------------------
+ * The entry points above take only sizes that are multiples of the MCU (8 x 8 for sample_ratio 0,
+ * 16 x 8 for 1, 16 x 16 for 2).  The _any family takes any width and height in 1 .. 65535.  Such a
+ * file codes every block of its coded frame: the size rounded up to the MCU (jpgx_coded_size).  The
+ * coefficients are the coded frame's, in the layout above with nb and nbc counted over the coded
+ * size; the pixels are the visible width x height.  For a size that is a multiple of the MCU every
+ * output, return and workspace size of an _any call equals its sibling's.
+ *
+ * jpgx_coded_size: width and height rounded up to the MCU of sample_ratio, for sizing coefficient
+ * buffers: nb = (coded_width / 8) * (coded_height / 8), nbc = nb / (1, 2, 4 for sample_ratio 0, 1,
+ * 2).  JPGX_EARG for null pointers, a sample_ratio outside 0..2 or a side outside 1 .. 65535. */
+int jpgx_coded_size(int width, int height, int sample_ratio, int *coded_width, int *coded_height);
+
+/* jpgx_jfif_decode_gpu_workspace_size_ex / jpgx_jfif_decode_gpu_ex (decode_flags 0 or
+ * JPGX_JFIF_DECODE_SUBINTERVAL) for files of any size.  width and height are the file's, as SOF
+ * states them; a file that states others has status JPGX_EJFIF_HEADER.  coef_frame_stride is at least
+ * the coded frame's (nb + 2 nbc) * 64; every block of the coded frame is decoded and written, the
+ * blocks no pixel of which is visible included.  d_status[f], the coefficients and the tables equal
+ * jpgx_read_jfif_any's for the same bytes.  The contract of jpgx_jfif_decode_gpu_ex holds otherwise,
+ * word for word: the checks and their order, no read outside a file's d_len[f] bytes, no write
+ * outside a frame's (nb + 2 nbc) * 64 elements.  A side outside 1 .. 65535 is JPGX_EARG;
+ * JPGX_EGEOMETRY does not occur. */
+size_t jpgx_jfif_decode_gpu_any_workspace_size(int width, int height, int sample_ratio,
+                                               size_t nframes, size_t file_cap, unsigned decode_flags);
+int jpgx_jfif_decode_gpu_any(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len,
+                             size_t nframes, int width, int height, int sample_ratio,
+                             unsigned decode_flags, int16_t *d_coef, size_t coef_frame_stride,
+                             uint16_t *d_qt, int32_t *d_status, void *d_workspace,
+                             size_t workspace_bytes, void *stream);
+
+/* jpgx_pixels_gpu_workspace_size / jpgx_pixels_gpu for a frame of any size: d_coef holds the coded
+ * frame's coefficients (jpgx_jfif_decode_gpu_any's output), width and height are the visible
+ * frame's.  The pixels are libjpeg's default decoder's for a file of that size, equal byte for byte
+ * to jpgx_pixels_host_any: whole blocks are transformed, and the chroma upsampling clamps at the
+ * component's real extent, ceil(width / 2) samples per row and (4:2:0) ceil(height / 2) rows; with
+ * two samples or fewer per row the chroma is replicated, not filtered.  This is not
+ * a crop of the coded frame's pixels.  out_pitch is at least 3 width and a multiple of 8,
+ * out_frame_stride at least out_pitch * height and a multiple of 8; only bytes [0, 3 width) of rows
+ * [0, height) are written.  The workspace is the coded frame's chroma planes.  Everything else,
+ * the checks, their order and their codes included, is jpgx_pixels_gpu's: a side outside
+ * 1 .. 65535 is JPGX_EGEOMETRY, the only case of that code. */
+size_t jpgx_pixels_gpu_any_workspace_size(int width, int height, int sample_ratio, size_t nframes);
+int jpgx_pixels_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes,
+                        int width, int height, int sample_ratio,
+                        const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                        uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
+                        void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* The two tables exactly as the JFIF writers put them into DQT for `quality` (the divisors the
  * forward path applied, zig-zag order): jpgx_blocks_gpu's output can be turned into pixels without
  * writing a file.  JPGX_EQUALITY outside 1..97, JPGX_EARG for a null qt. */

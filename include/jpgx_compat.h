@@ -249,6 +249,26 @@ int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint
 int jpgx_pixels_host(const int16_t *coef, int width, int height, int sample_ratio,
                      const uint16_t qt[2][64], uint8_t *rgb, size_t pitch, int nthreads);
 
+/* Files of any width and height (include/jpgx.h: the _any family): each of the four
+ * takes its sibling's arguments and keeps its sibling's contract without "width and height multiples
+ * of the MCU" -- any width and height in 1 .. 65535.  info.width / height are the SOF's; nb_y / nb_c
+ * and the coefficients are the coded frame's, the size rounded up to the MCU (jpgx_coded_size),
+ * every block of which the file codes.  jpgx_read_jfif_sub_any is the host twin of the device
+ * decoder's kernel as jpgx_read_jfif_sub is.  jpgx_pixels_host_any takes the coded frame's
+ * coefficients and the visible width and height and writes bytes [0, 3 width) of rows [0, height):
+ * libjpeg's default decoder's pixels for a file of that size -- the chroma upsampling clamps at the
+ * component's real extent and replicates a row of two samples or fewer, so they are
+ * not a crop of the coded frame's pixels; a side outside 1 .. 65535 is JPGX_EGEOMETRY.  For a size
+ * that is a multiple of the MCU every output and return equals the sibling's. */
+int jpgx_jfif_info_of_any(const uint8_t *file, size_t len, jpgx_jfif_info *info);
+int jpgx_read_jfif_any(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap,
+                       uint16_t qt[2][64], jpgx_jfif_info *info);
+int jpgx_read_jfif_sub_any(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs,
+                           int16_t *coef, size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info,
+                           jpgx_jfif_sub_stats *stats);
+int jpgx_pixels_host_any(const int16_t *coef, int width, int height, int sample_ratio,
+                         const uint16_t qt[2][64], uint8_t *rgb, size_t pitch, int nthreads);
+
 /* encode_bmp_to_jpeg with flags: JPGX_FLAG_SUBSAMPLE and sample_ratio 1/2 write a truly
  * subsampled JFIF (extension); otherwise exactly jpgx_encode_bmp_to_jpeg.  GPU `device`. */
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

@@ -20,6 +20,8 @@
  *                bytes starting at a guessed place, the exit states handed on in rounds until they
  *                are the sequential decoder's, then placed and written: jx_jfif_sub.h's routines,
  *                which the host twin jpgx_read_jfif_sub runs too
+ * jpgx_jfif_decode_gpu_any (files of any width and height) differs in the header kernel's mode alone:
+ * the other kernels see the coded frame's counts.
  * The interval's blocks are zeroed and filled by the lanes that decode them; no memset.
  * The call keeps no state and is capturable.
  */
@@ -81,6 +83,9 @@ __device__ __forceinline__ uint32_t jd_scan(uint32_t x, uint32_t *wtot, uint32_t
     return base + incl - x;
 }
 
+/* ANY: the header walk's mode (jx_jfif_dec.h) -- the file's width and height are compared as they
+ * stand in SOF, its counts are the coded frame's */
+template <int ANY>
 __global__ __launch_bounds__(kWave) void k_jd_header(const JdArgs a)
 {
     __shared__ int32_t rc_s;
@@ -89,7 +94,7 @@ __global__ __launch_bounds__(kWave) void k_jd_header(const JdArgs a)
     if (t == 0) {
         const unsigned long long len = a.len[f];
         int rc = JPGX_EJFIF_HEADER;     /* bit 63 (an overflow report) is above every stride */
-        if (len <= a.fstride) rc = jxd_parse_header(a.files + (size_t)f * a.fstride, (size_t)len, fr, a.tabs + 4 * (size_t)f);
+        if (len <= a.fstride) rc = jxd_parse_header<ANY>(a.files + (size_t)f * a.fstride, (size_t)len, fr, a.tabs + 4 * (size_t)f);
         if (!rc && (fr->width != a.width || fr->height != a.height || fr->hs != a.hs || fr->vs != a.vs))
             rc = JPGX_EJFIF_HEADER;
         a.st[f] = rc;
@@ -380,10 +385,13 @@ struct JdLayout {
  * JPGX_EGEOMETRY.  The kernels keep the six words of geometry their arguments always had (with the
  * whole jx_frame as argument and in jxd_frame the decoder was 0.9 - 3.1 % slower):
  * the host fills them from the frame */
-int jd_geometry(int width, int height, int sample_ratio, size_t nframes, size_t file_cap, JdArgs &a, JdLayout &l)
+int jd_geometry(bool any, int width, int height, int sample_ratio, size_t nframes, size_t file_cap, JdArgs &a, JdLayout &l)
 {
     jx_frame f;
-    const int rc = jx_frame_rc_decoder(jx_frame_make(width, height, sample_ratio, &f));
+    jx_frame_any fa;
+    const int why = any ? jx_frame_make_any(width, height, sample_ratio, &fa) : jx_frame_make(width, height, sample_ratio, &f);
+    const int rc = jx_frame_rc_decoder(why);
+    if (any && !why) f = fa.c;          /* the coded frame: what the coefficients and the MCU counts are of */
     if (rc == JPGX_EARG || !jx_frames_ok(nframes) || file_cap == 0 || file_cap > 0xffffffffull - kChunk)
         return JPGX_EARG;
     if (rc) return rc;
@@ -404,29 +412,11 @@ int jd_geometry(int width, int height, int sample_ratio, size_t nframes, size_t 
     return JPGX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t jpgx_jfif_decode_gpu_workspace_size_ex(int width, int height, int sample_ratio, size_t nframes, size_t file_cap,
-                                              unsigned decode_flags)
-{
-    JdArgs a;
-    JdLayout l;
-    if (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL) return 0;
-    if (jd_geometry(width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
-    return l.total;
-}
-
-size_t jpgx_jfif_decode_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes, size_t file_cap)
-{
-    return jpgx_jfif_decode_gpu_workspace_size_ex(width, height, sample_ratio, nframes, file_cap, 0u);
-}
-
-int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
-                            int height, int sample_ratio, unsigned decode_flags, int16_t *d_coef,
-                            size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status, void *d_workspace,
-                            size_t workspace_bytes, void *stream)
+/* jpgx_jfif_decode_gpu_ex (any = false) and jpgx_jfif_decode_gpu_any: the checks, their order and the
+ * launches are the same but for the geometry's rule and the header kernel's mode */
+int jd_decode(bool any, const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
+              int height, int sample_ratio, unsigned decode_flags, int16_t *d_coef, size_t coef_frame_stride,
+              uint16_t *d_qt, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     JdArgs a;
     JdLayout l;
@@ -435,7 +425,7 @@ int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const ui
         ((uintptr_t)d_coef & 15) || ((uintptr_t)d_status & 3) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_workspace & 15) ||
         (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL))
         return JPGX_EARG;
-    const int rc = jd_geometry(width, height, sample_ratio, nframes, file_stride, a, l);
+    const int rc = jd_geometry(any, width, height, sample_ratio, nframes, file_stride, a, l);
     if (rc) return rc;
     if (!jx_coef_batch_ok(coef_frame_stride, a.nblk)) return JPGX_EARG;
     if (workspace_bytes < l.total) return JPGX_EWORKSPACE;
@@ -454,7 +444,8 @@ int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const ui
     a.mpos = (uint32_t *)(ws + l.mpos);
     hipStream_t s = (hipStream_t)stream;
     const dim3 per_frame((unsigned)nframes), per_chunk(a.nchunk, (unsigned)nframes);
-    hipLaunchKernelGGL(k_jd_header, per_frame, dim3(kWave), 0, s, a);
+    if (any) hipLaunchKernelGGL(k_jd_header<1>, per_frame, dim3(kWave), 0, s, a);
+    else hipLaunchKernelGGL(k_jd_header<0>, per_frame, dim3(kWave), 0, s, a);
     hipLaunchKernelGGL(k_jd_count, per_chunk, dim3(kT), 0, s, a);
     hipLaunchKernelGGL(k_jd_frame, per_frame, dim3(kT), 0, s, a);
     hipLaunchKernelGGL(k_jd_place, per_chunk, dim3(kT), 0, s, a);
@@ -463,6 +454,53 @@ int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const ui
     else
         hipLaunchKernelGGL(k_jd_scan, dim3((a.nmcu + kWave - 1) / kWave, (unsigned)nframes), dim3(kWave), 0, s, a);
     return jx_hip_rc(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jpgx_jfif_decode_gpu_workspace_size_ex(int width, int height, int sample_ratio, size_t nframes, size_t file_cap,
+                                              unsigned decode_flags)
+{
+    JdArgs a;
+    JdLayout l;
+    if (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL) return 0;
+    if (jd_geometry(false, width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
+    return l.total;
+}
+
+size_t jpgx_jfif_decode_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes, size_t file_cap)
+{
+    return jpgx_jfif_decode_gpu_workspace_size_ex(width, height, sample_ratio, nframes, file_cap, 0u);
+}
+
+int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
+                            int height, int sample_ratio, unsigned decode_flags, int16_t *d_coef,
+                            size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status, void *d_workspace,
+                            size_t workspace_bytes, void *stream)
+{
+    return jd_decode(false, d_files, file_stride, d_len, nframes, width, height, sample_ratio, decode_flags, d_coef,
+                     coef_frame_stride, d_qt, d_status, d_workspace, workspace_bytes, stream);
+}
+
+size_t jpgx_jfif_decode_gpu_any_workspace_size(int width, int height, int sample_ratio, size_t nframes, size_t file_cap,
+                                               unsigned decode_flags)
+{
+    JdArgs a;
+    JdLayout l;
+    if (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL) return 0;
+    if (jd_geometry(true, width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
+    return l.total;
+}
+
+int jpgx_jfif_decode_gpu_any(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
+                             int height, int sample_ratio, unsigned decode_flags, int16_t *d_coef,
+                             size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status, void *d_workspace,
+                             size_t workspace_bytes, void *stream)
+{
+    return jd_decode(true, d_files, file_stride, d_len, nframes, width, height, sample_ratio, decode_flags, d_coef,
+                     coef_frame_stride, d_qt, d_status, d_workspace, workspace_bytes, stream);
 }
 
 int jpgx_jfif_decode_gpu(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,

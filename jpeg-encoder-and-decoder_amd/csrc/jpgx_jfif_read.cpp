@@ -1,6 +1,7 @@
 /*
  * jpgx_jfif_read.cpp -- the host decoder of baseline JFIF files back to the coefficient layout
- * (DESIGN.md 4.8): jpgx_jfif_info_of, jpgx_read_jfif (include/jpgx_compat.h).  The routines are
+ * (DESIGN.md 4.8): jpgx_jfif_info_of, jpgx_read_jfif and their _any siblings for files of any width and
+ * height, and jpgx_coded_size (include/jpgx_compat.h, include/jpgx.h).  The routines are
  * those of jx_jfif_dec.h, the ones the device decoder (jpgx_jfif_dec.hip) runs; this file adds the
  * search for the restart markers and the threads.  No HIP: built with g++, as jpgx_plan.cpp.
  */
@@ -52,6 +53,12 @@ void fill_info(const jxd_frame &fr, jpgx_jfif_info *info)
     info->nb_c = fr.nbc;
 }
 
+/* the header walk in one of its two modes (jx_jfif_dec.h): any = the _any entry points' */
+int parse(bool any, const uint8_t *file, size_t len, jxd_frame *fr, jxd_tab *tabs)
+{
+    return any ? jxd_parse_header<1>(file, len, fr, tabs) : jxd_parse_header<0>(file, len, fr, tabs);
+}
+
 /* the restart markers: FF D0 .. D7 cannot occur inside entropy-coded data.  Their count must be the
  * intervals' less one, their numbers run k mod 8, and EOI ends the file.  marks: [ni - 1] */
 int find_marks(const uint8_t *file, size_t len, const jxd_frame *fr, size_t *marks)
@@ -67,33 +74,29 @@ int find_marks(const uint8_t *file, size_t len, const jxd_frame *fr, size_t *mar
     return found != fr->ni - 1 ? JPGX_EJFIF_SCAN : 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info)
+int info_of(bool any, const uint8_t *file, size_t len, jpgx_jfif_info *info)
 {
     if (!file || !info) return JPGX_EARG;
     jxd_frame fr;
     jxd_tab *tabs = (jxd_tab *)malloc(4 * sizeof(jxd_tab));
     if (!tabs) return JPGX_ENOMEM;
     memset(&fr, 0, sizeof fr);
-    const int rc = jxd_parse_header(file, len, &fr, tabs);
+    const int rc = parse(any, file, len, &fr, tabs);
     free(tabs);
     if (rc) return rc;
     fill_info(fr, info);
     return JPGX_OK;
 }
 
-int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
-                   jpgx_jfif_info *info)
+int read_jfif(bool any, const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
+              jpgx_jfif_info *info)
 {
     if (!file || !coef || nthreads < 0) return JPGX_EARG;
     jxd_frame fr;
     memset(&fr, 0, sizeof fr);
     jxd_tab *tabs = (jxd_tab *)malloc(4 * sizeof(jxd_tab));
     if (!tabs) return JPGX_ENOMEM;
-    int rc = jxd_parse_header(file, len, &fr, tabs);
+    int rc = parse(any, file, len, &fr, tabs);
     if (rc) {
         free(tabs);
         return rc;
@@ -141,6 +144,36 @@ int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef,
     free(marks);
     free(tabs);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(false, file, len, info); }
+
+int jpgx_jfif_info_of_any(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(true, file, len, info); }
+
+int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
+                   jpgx_jfif_info *info)
+{
+    return read_jfif(false, file, len, nthreads, coef, coef_cap, qt, info);
+}
+
+int jpgx_read_jfif_any(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
+                       jpgx_jfif_info *info)
+{
+    return read_jfif(true, file, len, nthreads, coef, coef_cap, qt, info);
+}
+
+int jpgx_coded_size(int width, int height, int sample_ratio, int *coded_width, int *coded_height)
+{
+    if (!coded_width || !coded_height || sample_ratio < 0 || sample_ratio > 2) return JPGX_EARG;
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return JPGX_EARG;
+    const int mw = sample_ratio ? 16 : 8, mh = sample_ratio == 2 ? 16 : 8;
+    *coded_width = (width + mw - 1) / mw * mw;
+    *coded_height = (height + mh - 1) / mh * mh;
+    return JPGX_OK;
 }
 
 }  /* extern "C" */
@@ -272,18 +305,8 @@ int sub_interval(const uint8_t *file, size_t len, size_t begin, size_t end, cons
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-void jpgx_jfif_decode_sub_shape(uint32_t *sub_bytes, uint32_t *tile_subs)
-{
-    if (sub_bytes) *sub_bytes = JXS_SUB;
-    if (tile_subs) *tile_subs = JXS_TILE;
-}
-
-int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
-                       size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
+int read_sub(bool any, const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
+             size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
 {
     if (!file || !coef) return JPGX_EARG;
     if (!sub_bytes && !tile_subs) sub_bytes = JXS_SUB, tile_subs = JXS_TILE;
@@ -293,7 +316,7 @@ int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint
     memset(&fr, 0, sizeof fr);
     jxd_tab *tabs = (jxd_tab *)malloc(4 * sizeof(jxd_tab));
     if (!tabs) return JPGX_ENOMEM;
-    int rc = jxd_parse_header(file, len, &fr, tabs);
+    int rc = parse(any, file, len, &fr, tabs);
     if (rc) {
         free(tabs);
         return rc;
@@ -324,6 +347,28 @@ int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint
     free(marks);
     free(tabs);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+void jpgx_jfif_decode_sub_shape(uint32_t *sub_bytes, uint32_t *tile_subs)
+{
+    if (sub_bytes) *sub_bytes = JXS_SUB;
+    if (tile_subs) *tile_subs = JXS_TILE;
+}
+
+int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
+                       size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
+{
+    return read_sub(false, file, len, sub_bytes, tile_subs, coef, coef_cap, qt, info, stats);
+}
+
+int jpgx_read_jfif_sub_any(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
+                           size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
+{
+    return read_sub(true, file, len, sub_bytes, tile_subs, coef, coef_cap, qt, info, stats);
 }
 
 }  /* extern "C" */

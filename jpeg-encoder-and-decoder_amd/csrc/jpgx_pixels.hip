@@ -26,6 +26,9 @@
  *     differs in b & 2 and so reads opposite halves of the 8-dword row: no conflict.
  * Every global index comes from the checked geometry, blockIdx and the lane: the data only ever
  * become values.  No global state, no memset; capturable.
+ *
+ * jpgx_pixels_gpu_any (a frame of any width and height) launches the instantiations ANY = 1 of
+ * k_px444 and k_px_sub, the plain call ANY = 0; k_px_chroma serves both.
  */
 #include <stdint.h>
 #include <string.h>
@@ -61,6 +64,22 @@ struct PxArgs {
     unsigned long long pitch, ostride;
     uint8_t *planes;                    /* workspace [nframes][2][8 cbh][8 cbw] (4:2:x) */
     PxGeom g;
+};
+
+/* the _any entry points' arguments (jpgx_pixels_gpu_any): g is the coded frame's, and with it come the
+ * visible frame and a chroma plane's real extent (jx_frame_any).  A type of its own, so that the plain
+ * kernels' arguments stay what they were */
+struct PxArgsAny : PxArgs {
+    uint32_t w, h, wc, hc;
+};
+
+template <int ANY>
+struct PxA {
+    typedef PxArgs type;
+};
+template <>
+struct PxA<1> {
+    typedef PxArgsAny type;
 };
 
 union V4 {
@@ -161,9 +180,14 @@ __device__ __forceinline__ void px_transform(const int16_t *const (&src)[NCH], c
 }
 
 /* lane (b, row j) has the 8 pixels of its row: 24 bytes to the staging buffer, then pixel row r of
- * the run, 24 n bytes at out + r * pitch, leaves in 8-byte pieces; lanes beyond the run store nothing */
+ * the run, 24 n bytes at out + r * pitch, leaves in 8-byte pieces; lanes beyond the run store nothing.
+ * ANY: only rows r < rows and bytes [0, nbytes) of a row are the frame's (both the same for the whole
+ * wave; 8 and 24 n everywhere but in a row's last run and the last block row): no row beyond, and
+ * where the bytes end inside a piece, lane r writes that piece of row r as 4 + 2 + 1 bytes */
+template <int ANY>
 __device__ __forceinline__ void px_store(const uint32_t (&y)[8], const uint32_t (&cb)[8], const uint32_t (&cr)[8],
-                                         uint32_t n, const Lane &L, uint8_t *stage, uint8_t *out, size_t pitch)
+                                         uint32_t n, const Lane &L, uint8_t *stage, uint8_t *out, size_t pitch,
+                                         uint32_t rows = 8u, uint32_t nbytes = 192u)
 {
     uint32_t px[24];
 #pragma unroll
@@ -180,7 +204,27 @@ __device__ __forceinline__ void px_store(const uint32_t (&y)[8], const uint32_t 
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const uint32_t piece = threadIdx.x + 64u * k, r = piece / 24u, c = piece % 24u;
-        if (c < 3u * n) *(uint2 *)(out + (size_t)r * pitch + c * 8u) = *(const uint2 *)(stage + r * kStageRow + c * 8u);
+        const bool whole = ANY ? r < rows && c * 8u + 8u <= nbytes : c < 3u * n;     /* nbytes <= 24 n */
+        if (whole) *(uint2 *)(out + (size_t)r * pitch + c * 8u) = *(const uint2 *)(stage + r * kStageRow + c * 8u);
+    }
+    if (ANY && (nbytes & 7u)) {         /* the same for the whole wave: lane r finishes row r */
+        const uint32_t r = threadIdx.x, at = nbytes & ~7u;
+        if (r < rows) {
+            const uint2 w = *(const uint2 *)(stage + r * kStageRow + at);
+            uint8_t *tail = out + (size_t)r * pitch + at;           /* 8-byte aligned */
+            uint32_t v = w.x;
+            if (nbytes & 4u) {
+                *(uint32_t *)tail = v;
+                tail += 4;
+                v = w.y;
+            }
+            if (nbytes & 2u) {
+                *(uint16_t *)tail = (uint16_t)v;
+                tail += 2;
+                v >>= 16;
+            }
+            if (nbytes & 1u) *tail = (uint8_t)v;
+        }
     }
     __syncthreads();                    /* the staging buffer is free for the next run's image */
 }
@@ -188,7 +232,8 @@ __device__ __forceinline__ void px_store(const uint32_t (&y)[8], const uint32_t 
 __device__ __forceinline__ bool px_skip(const PxArgs &a, uint32_t f) { return a.status && a.status[f] != 0; }
 
 /* five waves per SIMD: 82 VGPRs without a spill, where the allocator left to itself takes 99 (four waves) */
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void k_px444(const PxArgs a)
+template <int ANY>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void k_px444(const typename PxA<ANY>::type a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t img[3 * 512];
     const uint32_t f = blockIdx.z, by = blockIdx.y;
@@ -206,7 +251,12 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(5))) void
                                        frame + (2 * (size_t)a.g.nb + blk) * 64};
         uint32_t s[3][8];
         px_transform<3>(src, tab, n, L, img, s);
-        px_store(s[0], s[1], s[2], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch);
+        if constexpr (ANY) {            /* the grid has the visible block rows only: by * 8 < h, run * 64 < w */
+            px_store<1>(s[0], s[1], s[2], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch,
+                        min(8u, a.h - by * 8u), min(24u * n, 3u * a.w - run * 192u));
+        } else {
+            px_store<0>(s[0], s[1], s[2], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch);
+        }
     }
 }
 
@@ -252,8 +302,20 @@ __device__ __forceinline__ void px_row6(const uint8_t *row, uint32_t i0, uint32_
     p[5] = row[i0 + 4u < wc ? i0 + 4u : wc - 1u];
 }
 
-template <int V2>
-__global__ __launch_bounds__(kWave) void k_px_sub(const PxArgs a)
+/* px_row6 where the row really ends at wc, before the plane's pitch (the last run of a row): every
+ * index clamps to wc - 1, those inside the dword included.  p[5] is clamped already */
+__device__ __forceinline__ void px_row6_edge(const uint8_t *row, uint32_t i0, uint32_t wc, uint32_t (&p)[6])
+{
+    const uint32_t last = row[wc - 1u];
+#pragma unroll
+    for (uint32_t k = 0; k < 5u; k++)
+        if (i0 + k > wc) p[k] = last;   /* sample i0 + k - 1 is beyond wc - 1 */
+}
+
+/* ANY: the planes keep the coded frame's pitch and rows; the clamps are at the chroma's real extent
+ * a.wc x a.hc, and a row of two samples or fewer is replicated, not filtered */
+template <int V2, int ANY>
+__global__ __launch_bounds__(kWave) void k_px_sub(const typename PxA<ANY>::type a)
 {
     __shared__ __attribute__((aligned(16))) uint32_t img[512];
     const uint32_t f = blockIdx.z, by = blockIdx.y;     /* a Y block row */
@@ -261,8 +323,10 @@ __global__ __launch_bounds__(kWave) void k_px_sub(const PxArgs a)
     Lane L;
     px_lane(a, f, L);
     const uint32_t nruns = (a.g.bw + 7u) / 8u;
-    const uint32_t wc = a.g.cbw * 8u, hc = a.g.cbh * 8u;
-    const size_t plane = (size_t)wc * hc;
+    const uint32_t pc = a.g.cbw * 8u;   /* bytes between a plane's rows */
+    uint32_t wc = pc, hc = a.g.cbh * 8u;
+    const size_t plane = (size_t)pc * hc;
+    if constexpr (ANY) wc = a.wc, hc = a.hc;
     const int16_t *frame = a.coef + (size_t)f * a.cstride;
     const uint8_t *planes = a.planes + (size_t)f * 2u * plane;
     uint8_t *out = a.rgb + (size_t)f * a.ostride + (size_t)by * 8u * a.pitch;
@@ -276,26 +340,43 @@ __global__ __launch_bounds__(kWave) void k_px_sub(const PxArgs a)
         const int16_t *const src[1] = {frame + ((size_t)by * a.g.bw + (size_t)run * 8u) * 64};
         uint32_t s[1][8], up[2][8];
         px_transform<1>(src, tab, n, L, img, s);
-        const uint32_t i0 = run * 32u + L.b * 4u;       /* the lane's 4 chroma samples; below wc while L.b < n */
+        const uint32_t i0 = run * 32u + L.b * 4u;       /* the lane's 4 chroma samples; below pc while L.b < n */
+        /* the same for the whole wave: this run's samples or their right neighbour lie beyond wc - 1 */
+        const bool edge = ANY && run * 32u + 32u >= wc;
 #pragma unroll
         for (int ch = 0; ch < 2; ch++) {
             uint32_t p[6] = {0, 0, 0, 0, 0, 0};
             if (L.b < n) {
-                px_row6(planes + ch * plane + (size_t)cy * wc, i0, wc, p);
-                if (V2) {
-                    uint32_t q[6];
-                    px_row6(planes + ch * plane + (size_t)far * wc, i0, wc, q);
+                /* both rows' loads first, as in the plain kernel; the edge's corrections after them */
+                uint32_t q[6];
+                px_row6(planes + ch * plane + (size_t)cy * pc, i0, wc, p);
+                if (V2) px_row6(planes + ch * plane + (size_t)far * pc, i0, wc, q);
+                if (edge) {
+                    px_row6_edge(planes + ch * plane + (size_t)cy * pc, i0, wc, p);
+                    if (V2) px_row6_edge(planes + ch * plane + (size_t)far * pc, i0, wc, q);
+                }
+                if (V2 && !(ANY && wc <= 2u)) {
 #pragma unroll
                     for (int i = 0; i < 6; i++) p[i] = jxi_vsum(p[i], q[i]);
                 }
             }
+            if (ANY && wc <= 2u) {      /* replication: the near row's sample for both pixels */
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                up[ch][2 * i] = jxi_up_even(p[i + 1], p[i], V2);
-                up[ch][2 * i + 1] = jxi_up_odd(p[i + 1], p[i + 2], V2);
+                for (int i = 0; i < 4; i++) up[ch][2 * i] = up[ch][2 * i + 1] = p[i + 1];
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    up[ch][2 * i] = jxi_up_even(p[i + 1], p[i], V2);
+                    up[ch][2 * i + 1] = jxi_up_odd(p[i + 1], p[i + 2], V2);
+                }
             }
         }
-        px_store(s[0], up[0], up[1], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch);
+        if constexpr (ANY) {            /* the grid has the visible block rows only: by * 8 < h, run * 64 < w */
+            px_store<1>(s[0], up[0], up[1], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch,
+                        min(8u, a.h - by * 8u), min(24u * n, 3u * a.w - run * 192u));
+        } else {
+            px_store<0>(s[0], up[0], up[1], n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch);
+        }
     }
 }
 
@@ -313,30 +394,33 @@ unsigned px_grid_x(uint32_t blocks_per_row)
     return (nruns + kRunsPerWave - 1) / kRunsPerWave;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t jpgx_pixels_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes)
+/* jpgx_pixels_gpu (ANY = 0) and jpgx_pixels_gpu_any: the checks and their order are the same but for
+ * the geometry's rule.  ANY: the Y grid has the block rows that hold a visible pixel row; the chroma
+ * kernel fills the coded planes whole, as it does for the plain call */
+template <int ANY>
+int px_run(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height, int sample_ratio,
+           const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status, uint8_t *d_rgb, size_t out_pitch,
+           size_t out_frame_stride, void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    jx_frame g;
-    if (!jx_frames_ok(nframes) || jx_frame_make(width, height, sample_ratio, &g)) return 0;
-    return px_workspace(g, nframes);
-}
-
-int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
-                    int sample_ratio, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
-                    uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride, void *d_workspace,
-                    size_t workspace_bytes, void *stream)
-{
-    PxArgs a;
+    typename PxA<ANY>::type a;
     memset(&a, 0, sizeof a);
     if (!d_coef || !d_qt || !d_rgb || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_status & 3) ||
         ((uintptr_t)d_rgb & 7) || !jx_frames_ok(nframes))
         return JPGX_EARG;
     jx_frame f;
-    const int rc = jx_frame_rc_pixels(jx_frame_make(width, height, sample_ratio, &f));
-    if (rc) return rc;
+    unsigned yrows;
+    if constexpr (ANY) {
+        jx_frame_any fa;
+        const int rc = jx_frame_rc_pixels(jx_frame_make_any(width, height, sample_ratio, &fa));
+        if (rc) return rc;
+        f = fa.c;
+        a.w = fa.w, a.h = fa.h, a.wc = fa.wc, a.hc = fa.hc;
+        yrows = (fa.h + 7u) / 8u;
+    } else {
+        const int rc = jx_frame_rc_pixels(jx_frame_make(width, height, sample_ratio, &f));
+        if (rc) return rc;
+        yrows = f.bh;
+    }
     a.g = PxGeom{f.bw, f.bh, f.cbw, f.cbh, f.hs, f.vs, f.nb, f.nbc};
     if (!jx_coef_batch_ok(coef_frame_stride, f.nblk)) return JPGX_EARG;
     if (qt_frame_stride != 0 && qt_frame_stride < 128) return JPGX_EARG;
@@ -355,15 +439,52 @@ int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nfra
     a.ostride = out_frame_stride;
     a.planes = (uint8_t *)d_workspace;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 ygrid(px_grid_x(a.g.bw), a.g.bh, (unsigned)nframes);
+    const dim3 ygrid(px_grid_x(a.g.bw), yrows, (unsigned)nframes);
     if (sample_ratio == 0) {
-        hipLaunchKernelGGL(k_px444, ygrid, dim3(kWave), 0, s, a);
+        hipLaunchKernelGGL(k_px444<ANY>, ygrid, dim3(kWave), 0, s, a);
     } else {
-        hipLaunchKernelGGL(k_px_chroma, dim3(px_grid_x(a.g.cbw), a.g.cbh, (unsigned)nframes), dim3(kWave), 0, s, a);
-        if (sample_ratio == 2) hipLaunchKernelGGL(k_px_sub<1>, ygrid, dim3(kWave), 0, s, a);
-        else hipLaunchKernelGGL(k_px_sub<0>, ygrid, dim3(kWave), 0, s, a);
+        const PxArgs &plain = a;
+        hipLaunchKernelGGL(k_px_chroma, dim3(px_grid_x(a.g.cbw), a.g.cbh, (unsigned)nframes), dim3(kWave), 0, s, plain);
+        if (sample_ratio == 2) hipLaunchKernelGGL((k_px_sub<1, ANY>), ygrid, dim3(kWave), 0, s, a);
+        else hipLaunchKernelGGL((k_px_sub<0, ANY>), ygrid, dim3(kWave), 0, s, a);
     }
     return jx_hip_rc(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jpgx_pixels_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes)
+{
+    jx_frame g;
+    if (!jx_frames_ok(nframes) || jx_frame_make(width, height, sample_ratio, &g)) return 0;
+    return px_workspace(g, nframes);
+}
+
+int jpgx_pixels_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                    int sample_ratio, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                    uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride, void *d_workspace,
+                    size_t workspace_bytes, void *stream)
+{
+    return px_run<0>(d_coef, coef_frame_stride, nframes, width, height, sample_ratio, d_qt, qt_frame_stride, d_status,
+                     d_rgb, out_pitch, out_frame_stride, d_workspace, workspace_bytes, stream);
+}
+
+size_t jpgx_pixels_gpu_any_workspace_size(int width, int height, int sample_ratio, size_t nframes)
+{
+    jx_frame_any g;
+    if (!jx_frames_ok(nframes) || jx_frame_make_any(width, height, sample_ratio, &g)) return 0;
+    return px_workspace(g.c, nframes);
+}
+
+int jpgx_pixels_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                        int sample_ratio, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                        uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride, void *d_workspace,
+                        size_t workspace_bytes, void *stream)
+{
+    return px_run<1>(d_coef, coef_frame_stride, nframes, width, height, sample_ratio, d_qt, qt_frame_stride, d_status,
+                     d_rgb, out_pitch, out_frame_stride, d_workspace, workspace_bytes, stream);
 }
 
 }  /* extern "C" */

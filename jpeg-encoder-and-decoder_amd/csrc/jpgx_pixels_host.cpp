@@ -1,6 +1,6 @@
 /*
- * jpgx_pixels_host.cpp -- the host twin of the pixel kernels: jpgx_pixels_host
- * (include/jpgx_compat.h).  The arithmetic is jx_idct.h's, the source the kernels
+ * jpgx_pixels_host.cpp -- the host twin of the pixel kernels: jpgx_pixels_host and
+ * jpgx_pixels_host_any, a frame of any width and height (include/jpgx_compat.h).  The arithmetic is jx_idct.h's, the source the kernels
  * (jpgx_pixels.hip) compile; this file adds the planes and the threads.  No HIP: built with g++,
  * as jpgx_jfif_read.cpp.
  *
@@ -25,7 +25,8 @@ const uint8_t kZZ[64] = JXI_ZZ_INIT;
 struct Ctx {
     const int16_t *coef;
     const uint16_t (*qt)[64];
-    jx_frame g;
+    jx_frame g;                     /* the coded frame */
+    uint32_t w, h, wc, hc;          /* the visible frame and a chroma plane's real extent (jx_frame_any) */
     uint8_t *plane[3];              /* Y: 8 bh x 8 bw, Cb / Cr: 8 cbh x 8 cbw */
     uint8_t *rgb;
     size_t pitch;
@@ -70,20 +71,25 @@ void samples_rows(const Ctx &c, uint32_t m0, uint32_t m1)
 void pixel_rows(const Ctx &c, uint32_t m0, uint32_t m1)
 {
     const jx_frame &g = c.g;
-    const uint32_t W = g.bw * 8, Wc = g.cbw * 8, Hc = g.cbh * 8;
-    const int v2 = g.vs == 2;
-    for (uint32_t y = m0 * 8 * g.vs; y < m1 * 8 * g.vs; y++) {
-        const uint8_t *yrow = c.plane[0] + (size_t)y * W;
+    /* the planes are the coded frame's; the clamps are at the chroma's real extent, and with two
+     * samples or fewer per row the chroma is replicated, not filtered */
+    const uint32_t P = g.bw * 8, Pc = g.cbw * 8, W = c.w, Wc = c.wc, Hc = c.hc;
+    const int v2 = g.vs == 2, rep = Wc <= 2;
+    for (uint32_t y = m0 * 8 * g.vs; y < m1 * 8 * g.vs && y < c.h; y++) {
+        const uint8_t *yrow = c.plane[0] + (size_t)y * P;
         uint8_t *out = c.rgb + (size_t)y * c.pitch;
         const uint32_t cy = y / g.vs;
         const uint32_t far = !v2 ? cy : (y & 1u) ? (cy + 1 < Hc ? cy + 1 : cy) : (cy ? cy - 1 : 0);
-        const uint8_t *n1 = c.plane[1] + (size_t)cy * Wc, *f1 = c.plane[1] + (size_t)far * Wc;
-        const uint8_t *n2 = c.plane[2] + (size_t)cy * Wc, *f2 = c.plane[2] + (size_t)far * Wc;
+        const uint8_t *n1 = c.plane[1] + (size_t)cy * Pc, *f1 = c.plane[1] + (size_t)far * Pc;
+        const uint8_t *n2 = c.plane[2] + (size_t)cy * Pc, *f2 = c.plane[2] + (size_t)far * Pc;
         for (uint32_t x = 0; x < W; x++) {
             uint32_t cb, cr, r, gg, b;
             if (g.hs == 1) {
                 cb = n1[x];
                 cr = n2[x];
+            } else if (rep) {
+                cb = n1[x >> 1];
+                cr = n2[x >> 1];
             } else {
                 const uint32_t i = x >> 1;
                 const uint32_t j = (x & 1u) ? (i + 1 < Wc ? i + 1 : i) : (i ? i - 1 : 0);   /* clamped to the plane */
@@ -133,16 +139,21 @@ void run_phase(const Ctx &c, int phase, uint32_t nt)
         if (started[t]) pthread_join(th[t], NULL);
 }
 
-}  // namespace
-
-extern "C" int jpgx_pixels_host(const int16_t *coef, int width, int height, int sample_ratio, const uint16_t qt[2][64],
-                                uint8_t *rgb, size_t pitch, int nthreads)
+int pixels_host(bool any, const int16_t *coef, int width, int height, int sample_ratio, const uint16_t qt[2][64],
+                uint8_t *rgb, size_t pitch, int nthreads)
 {
     if (!coef || !qt || !rgb || nthreads < 0) return JPGX_EARG;
     Ctx c;
     memset(&c, 0, sizeof c);
-    const int rc = jx_frame_rc_pixels(jx_frame_make(width, height, sample_ratio, &c.g));
+    jx_frame_any a;
+    const int rc = jx_frame_rc_pixels(any ? jx_frame_make_any(width, height, sample_ratio, &a)
+                                          : jx_frame_make(width, height, sample_ratio, &c.g));
     if (rc) return rc;
+    if (any) c.g = a.c;
+    c.w = (uint32_t)width;
+    c.h = (uint32_t)height;
+    c.wc = any ? a.wc : c.g.cbw * 8;
+    c.hc = any ? a.hc : c.g.cbh * 8;
     if (pitch < (size_t)width * 3) return JPGX_EARG;
     const size_t ny = (size_t)c.g.nb * 64, nc = (size_t)c.g.nbc * 64;
     uint8_t *planes = (uint8_t *)malloc(ny + 2 * nc);
@@ -163,3 +174,21 @@ extern "C" int jpgx_pixels_host(const int16_t *coef, int width, int height, int 
     free(planes);
     return JPGX_OK;
 }
+
+}  // namespace
+
+extern "C" {
+
+int jpgx_pixels_host(const int16_t *coef, int width, int height, int sample_ratio, const uint16_t qt[2][64], uint8_t *rgb,
+                     size_t pitch, int nthreads)
+{
+    return pixels_host(false, coef, width, height, sample_ratio, qt, rgb, pitch, nthreads);
+}
+
+int jpgx_pixels_host_any(const int16_t *coef, int width, int height, int sample_ratio, const uint16_t qt[2][64],
+                         uint8_t *rgb, size_t pitch, int nthreads)
+{
+    return pixels_host(true, coef, width, height, sample_ratio, qt, rgb, pitch, nthreads);
+}
+
+}  /* extern "C" */

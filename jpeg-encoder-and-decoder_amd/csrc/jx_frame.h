@@ -62,6 +62,49 @@ JXF_FN int jx_frame_make(int width, int height, int sample_ratio, jx_frame *f)
     return 0;
 }
 
+/* A file of any width and height (the decode side's _any entry points): the coded
+ * frame is the file's size rounded up to the MCU, and everything above holds for it; the visible
+ * frame is the SOF's w x h, of which a chroma plane really has wc = ceil(w / hs) samples per row and
+ * hc = ceil(h / vs) rows -- the extent the upsampling clamps at. */
+typedef struct jx_frame_any {
+    jx_frame c;             /* the coded frame                                                   */
+    uint32_t w, h;          /* the visible frame, 1 .. 65535 each                                */
+    uint32_t wc, hc;        /* a chroma plane's real extent                                      */
+} jx_frame_any;
+
+/* the coded size of width x height: both rounded up to the MCU */
+JXF_FN void jx_frame_coded(uint32_t width, uint32_t height, uint32_t hs, uint32_t vs, uint32_t *cw, uint32_t *ch)
+{
+    *cw = (width + 8u * hs - 1u) / (8u * hs) * (8u * hs);
+    *ch = (height + 8u * vs - 1u) / (8u * vs) * (8u * vs);
+}
+
+/* jx_frame_make without the multiple-of-the-MCU tests: JXF_SAMPLE or JXF_RANGE are all it refuses.
+ * For a size that is a multiple of the MCU, a->c is what jx_frame_make fills. */
+JXF_FN int jx_frame_make_any(int width, int height, int sample_ratio, jx_frame_any *a)
+{
+    if (sample_ratio < 0 || sample_ratio > 2) return JXF_SAMPLE;
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return JXF_RANGE;
+    jx_frame *f = &a->c;
+    uint32_t cw, ch;
+    jx_frame_sampling(sample_ratio, &f->hs, &f->vs);
+    jx_frame_coded((uint32_t)width, (uint32_t)height, f->hs, f->vs, &cw, &ch);
+    f->bw = cw / 8u;
+    f->bh = ch / 8u;
+    f->lum = f->hs * f->vs;
+    f->bpm = f->lum + 2u;
+    f->cbw = f->bw / f->hs;
+    f->cbh = f->bh / f->vs;
+    f->nb = f->bw * f->bh;
+    f->nbc = f->cbw * f->cbh;
+    f->nblk = f->nb + 2u * f->nbc;
+    a->w = (uint32_t)width;
+    a->h = (uint32_t)height;
+    a->wc = (a->w + f->hs - 1u) / f->hs;
+    a->hc = (a->h + f->vs - 1u) / f->vs;
+    return 0;
+}
+
 /* The codes the entry points refuse with are part of the ABI and differ; each is one mapping of
  * the reason:            SAMPLE         RANGE           MULT8           MCU
  *   the JFIF coder       EARG           EARG            EARG            EGEOMETRY

@@ -88,7 +88,10 @@ JXD_FN int jxd_build_table(const uint8_t *bits, const uint8_t *vals, jxd_tab *t)
 /* SOI .. the end of SOS.  Accepts baseline SOF0 and SOF1 with 8-bit samples, 3 components in one
  * interleaved scan, luma sampled 1x1, 2x1 or 2x2 and chroma 1x1, width and height multiples of the
  * MCU, DQT with 8- or 16-bit entries, DHT (classes 0 / 1, ids 0 / 1), DRI; skips APPn and COM.
+ * ANY = 1 (the _any entry points): any width and height 1 .. 65535; fr->width and fr->height are the
+ * SOF's, the counts bpr .. nblk those of the coded frame, the size rounded up to the MCU.
  * Returns 0 or JPGX_EJFIF_HEADER. */
+template <int ANY = 0>
 JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_tab *tabs /*[4]*/)
 {
     const int bad = JPGX_EJFIF_HEADER;
@@ -142,7 +145,8 @@ JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_
             if (seg[10] != 0x11 || seg[13] != 0x11 || fr->tq[1] != fr->tq[2]) return bad;
             fr->hs = s >> 4;
             fr->vs = s & 15u;
-            if (!fr->width || !fr->height || fr->width % (8 * fr->hs) || fr->height % (8 * fr->vs)) return bad;
+            if (!fr->width || !fr->height) return bad;
+            if (!ANY && (fr->width % (8 * fr->hs) || fr->height % (8 * fr->vs))) return bad;
             have_sof = 1;
         } else if (m == 0xdd) {
             if (n != 2) return bad;
@@ -171,11 +175,18 @@ JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_
         }
         i += 2 + ln;
     }
-    fr->bpr = fr->width / 8;
-    fr->cpr = fr->bpr / fr->hs;
-    fr->mrows = fr->height / 8 / fr->vs;
+    if (ANY) {
+        fr->cpr = (fr->width + 8 * fr->hs - 1) / (8 * fr->hs);
+        fr->mrows = (fr->height + 8 * fr->vs - 1) / (8 * fr->vs);
+        fr->bpr = fr->cpr * fr->hs;
+        fr->nb = fr->bpr * (fr->mrows * fr->vs);
+    } else {
+        fr->bpr = fr->width / 8;
+        fr->cpr = fr->bpr / fr->hs;
+        fr->mrows = fr->height / 8 / fr->vs;
+        fr->nb = fr->bpr * (fr->height / 8);
+    }
     fr->nmcu = fr->cpr * fr->mrows;
-    fr->nb = fr->bpr * (fr->height / 8);
     fr->nbc = fr->nmcu;
     fr->nblk = fr->nb + 2 * fr->nbc;
     fr->mpi = fr->ri && fr->ri < fr->nmcu ? fr->ri : fr->nmcu;

@@ -12,6 +12,8 @@ Reference mapping (matthewT53/JPEG-Encoder-and-Decoder):
 No counterpart in the reference (its decoder is an empty header): jfif_decode_gpu,
 decode_jpeg_coefficients -- baseline JFIF files back to the coefficients (DESIGN.md 4.8);
 pixels_gpu, decode_jpeg -- the coefficients to RGB, libjpeg's default decoder's pixels (4.9).
+These four take any_size=True for files whose width and height are no multiple of the MCU (the
+library's _any entry points); coded_size is the size such a file's coefficients are of.
 """
 from __future__ import annotations
 
@@ -54,6 +56,8 @@ EXPORTS = [
     "jpgx_jfif_decode_gpu_workspace_size", "jpgx_jfif_decode_gpu",
     "jpgx_jfif_decode_gpu_workspace_size_ex", "jpgx_jfif_decode_gpu_ex", "jpgx_jfif_decode_sub_shape",
     "jpgx_pixels_gpu_workspace_size", "jpgx_pixels_gpu", "jpgx_jfif_qt",
+    "jpgx_coded_size", "jpgx_jfif_decode_gpu_any_workspace_size", "jpgx_jfif_decode_gpu_any",
+    "jpgx_pixels_gpu_any_workspace_size", "jpgx_pixels_gpu_any",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -64,6 +68,7 @@ COMPAT_EXPORTS = [
     "jpgx_encode_bmp_to_jpeg", "jpgx_write_jfif_sub", "jpgx_encode_bmp_to_jpeg_ex",
     "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex", "jpgx_write_jfif_opt",
     "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host",
+    "jpgx_jfif_info_of_any", "jpgx_read_jfif_any", "jpgx_read_jfif_sub_any", "jpgx_pixels_host_any",
 ]
 
 
@@ -145,6 +150,13 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_pixels_gpu_workspace_size.restype = sz
     L.jpgx_pixels_gpu.argtypes = [vp, sz, sz, i, i, i, vp, sz, vp, vp, sz, sz, vp, sz, vp]
     L.jpgx_jfif_qt.argtypes = [i, vp]
+    L.jpgx_coded_size.argtypes = [i, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
+    L.jpgx_jfif_decode_gpu_any_workspace_size.argtypes = L.jpgx_jfif_decode_gpu_workspace_size_ex.argtypes
+    L.jpgx_jfif_decode_gpu_any_workspace_size.restype = sz
+    L.jpgx_jfif_decode_gpu_any.argtypes = L.jpgx_jfif_decode_gpu_ex.argtypes
+    L.jpgx_pixels_gpu_any_workspace_size.argtypes = L.jpgx_pixels_gpu_workspace_size.argtypes
+    L.jpgx_pixels_gpu_any_workspace_size.restype = sz
+    L.jpgx_pixels_gpu_any.argtypes = L.jpgx_pixels_gpu.argtypes
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -298,13 +310,26 @@ def chroma_blocks(width: int, row_begin: int, row_end: int, sample_ratio: int = 
     return int(lib.jpgx_chroma_blocks(width, row_begin, row_end, sample_ratio, flags))
 
 
+def coded_size(width: int, height: int, sample_ratio: int = 0) -> tuple[int, int]:
+    """jpgx_coded_size: (width, height) rounded up to the MCU of sample_ratio -- the frame a file of
+    that size codes, and the one its coefficients are of (nb = (cw // 8) * (ch // 8))."""
+    cw, ch = ctypes.c_int(), ctypes.c_int()
+    _check(lib.jpgx_coded_size(width, height, sample_ratio, ctypes.byref(cw), ctypes.byref(ch)), "jpgx_coded_size")
+    return cw.value, ch.value
+
+
 def _frame(fn: str, width: int, height: int, sample_ratio: int, flags: int | None = None, d_coef=None,
-           whole_blocks: bool = False):
+           whole_blocks: bool = False, any_size: bool = False):
     """(nb, nbc, int16 elements per frame, elements between frames) of a frame's coefficients,
     Y [nb][64] | Cb [nbc][64] | Cr [nbc][64].  flags None: a coded frame (csrc/jx_frame.h), its
     geometry checked and its chroma subsampled as sample_ratio says; else the forward path's output
     under `flags`.  d_coef ([nframes][...]): every frame must be contiguous and hold that much
-    (whole_blocks: and be laid out as the JFIF coder needs it); without it the fourth value is None."""
+    (whole_blocks: and be laid out as the JFIF coder needs it); without it the fourth value is None.
+    any_size: width and height are a file's, any 1 .. 65535; the counts are its coded frame's."""
+    if any_size:
+        if sample_ratio not in (0, 1, 2) or not (0 < width < 65536 and 0 < height < 65536):
+            raise ValueError(f"{fn}: bad geometry or sample_ratio")
+        width, height = coded_size(width, height, sample_ratio)
     if flags is None:
         if sample_ratio not in (0, 1, 2) or width <= 0 or height <= 0 or width % 8 or height % 8:
             raise ValueError(f"{fn}: bad geometry or sample_ratio")
@@ -431,7 +456,7 @@ def jfif_decode_sub_shape() -> tuple[int, int]:
 
 
 def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 0, stream=None,
-                    subinterval: bool = False):
+                    subinterval: bool = False, any_size: bool = False):
     """The coefficients of a batch of baseline JFIF files in device memory (jpgx_jfif_decode_gpu;
     entropy decoding only): d_files uint8 [nframes][cap] and lens int64 [nframes] as jfif_gpu returns
     them, every file of the stated width, height and sample_ratio ->
@@ -441,7 +466,9 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
     compat.read_jfif reports for the same bytes; a frame with a nonzero status has unspecified
     coefficients.  Nothing is copied to the host and nothing waits.  subinterval:
     JFIF_DECODE_SUBINTERVAL, a workgroup per restart interval instead of a lane (jpgx_jfif_decode_gpu_ex;
-    DESIGN.md 4.8a): the same outputs, faster where intervals are long or few."""
+    DESIGN.md 4.8a): the same outputs, faster where intervals are long or few.  any_size:
+    jpgx_jfif_decode_gpu_any -- width and height are the files' own, any 1 .. 65535, and nb, nbc are
+    the coded frame's (coded_size); statuses and coefficients are compat.read_jfif(any_size=True)'s."""
     import torch
     for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda:
@@ -452,7 +479,9 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
         raise ValueError("jfif_decode_gpu: d_files [nframes][cap] and lens [nframes]")
     if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
         raise ValueError("jfif_decode_gpu: each file must be contiguous")
-    nb, nbc, _, _ = _frame("jfif_decode_gpu", width, height, sample_ratio)
+    nb, nbc, _, _ = _frame("jfif_decode_gpu", width, height, sample_ratio, any_size=any_size)
+    size_fn = lib.jpgx_jfif_decode_gpu_any_workspace_size if any_size else lib.jpgx_jfif_decode_gpu_workspace_size_ex
+    decode_fn = lib.jpgx_jfif_decode_gpu_any if any_size else lib.jpgx_jfif_decode_gpu_ex
     nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
     fstride = int(d_files.stride(0)) if nf > 1 else cap
     if fstride < cap:
@@ -462,26 +491,27 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
     qt = torch.empty((nf, 2, 64), dtype=torch.uint16, device=dev)
     status = torch.empty(nf, dtype=torch.int32, device=dev)
     dflags = JFIF_DECODE_SUBINTERVAL if subinterval else 0
-    need = int(lib.jpgx_jfif_decode_gpu_workspace_size_ex(width, height, sample_ratio, nf, fstride, dflags))
+    need = int(size_fn(width, height, sample_ratio, nf, fstride, dflags))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    _check(lib.jpgx_jfif_decode_gpu_ex(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, sample_ratio,
-                                       dflags, coef.data_ptr(), (nb + 2 * nbc) * 64, qt.data_ptr(), status.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu")
+    _check(decode_fn(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, sample_ratio,
+                     dflags, coef.data_ptr(), (nb + 2 * nbc) * 64, qt.data_ptr(), status.data_ptr(),
+                     ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu")
     if stream is not None:
         ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
     return coef, qt, status
 
 
-def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False):
+def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False, any_size: bool = False):
     """One baseline JFIF file in host memory -> its coefficients on `device`: the header walk on the
     host for the geometry (compat.jfif_info), one host-to-device copy of the bytes, jfif_decode_gpu.
     Returns compat.read_jfif's dict with device tensors: coef int16 ([3][nb][64] for 4:4:4,
     [nb + 2 nbc][64] otherwise), qt uint16 [2][64], width, height, sample_ratio, restart_interval.
     Raises JpgxError on a nonzero status (that reads the status back, a synchronisation).
-    subinterval: as jfif_decode_gpu's."""
+    subinterval, any_size: as jfif_decode_gpu's (any_size: the coefficients are the coded frame's,
+    width and height the file's)."""
     import torch
     from . import compat
-    info = compat.jfif_info(data)
+    info = compat.jfif_info(data, any_size=any_size)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("decode_jpeg_coefficients: device must be a GPU")
@@ -489,7 +519,7 @@ def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False):
     d_files = host.to(dev).reshape(1, -1)
     lens = torch.tensor([len(data)], dtype=torch.int64, device=dev)
     coef, qt, status = jfif_decode_gpu(d_files, lens, info["width"], info["height"], info["sample_ratio"],
-                                       subinterval=subinterval)
+                                       subinterval=subinterval, any_size=any_size)
     _check(int(status[0]), "jpgx_jfif_decode_gpu")
     out = coef[0].reshape(3, -1, 64) if info["sample_ratio"] == 0 else coef[0]
     return dict(coef=out, qt=qt[0], width=info["width"], height=info["height"],
@@ -505,7 +535,7 @@ def jfif_qt(quality: int) -> np.ndarray:
 
 
 def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None, status=None, out=None,
-               pitch: int | None = None, stream=None):
+               pitch: int | None = None, stream=None, any_size: bool = False):
     """The pixels of a batch of coefficient frames (jpgx_pixels_gpu): d_coef int16
     [nframes][...] as jfif_decode_gpu returns it (each frame contiguous, frames d_coef.stride(0)
     elements apart), d_qt uint16 [nframes][2][64] (one pair per frame) or [2][64] (one for the batch),
@@ -513,14 +543,18 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     Returns uint8 [nframes][H][W][3] on the device: a fresh tensor, or, with a pitch (bytes between
     pixel rows, a multiple of 8, at least 3 W), a view of the padded buffer; out: a contiguous uint8
     buffer of nframes * H * pitch bytes to use instead of a fresh one.  Nothing is copied to the host
-    and nothing waits."""
+    and nothing waits.  any_size: jpgx_pixels_gpu_any -- d_coef holds the coded frame's coefficients
+    (jfif_decode_gpu(any_size=True)), width and height are the visible frame's, any 1 .. 65535; the
+    default pitch is 3 W rounded up to 8, and only bytes [0, 3 W) of the H rows are written."""
     import torch
     if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda or d_coef.dtype != torch.int16 or d_coef.dim() < 2:
         raise ValueError("pixels_gpu: d_coef must be an int16 [nframes][...] device tensor")
     if not isinstance(d_qt, torch.Tensor) or not d_qt.is_cuda or d_qt.dtype != torch.uint16 or not d_qt.is_contiguous():
         raise ValueError("pixels_gpu: d_qt must be a contiguous uint16 device tensor")
     nf = int(d_coef.shape[0])
-    _, _, _, cstride = _frame("pixels_gpu", width, height, sample_ratio, d_coef=d_coef)
+    _, _, _, cstride = _frame("pixels_gpu", width, height, sample_ratio, d_coef=d_coef, any_size=any_size)
+    size_fn = lib.jpgx_pixels_gpu_any_workspace_size if any_size else lib.jpgx_pixels_gpu_workspace_size
+    pixels_fn = lib.jpgx_pixels_gpu_any if any_size else lib.jpgx_pixels_gpu
     if d_qt.numel() == 128:
         qstride = 0
     elif d_qt.numel() == 128 * nf:
@@ -530,7 +564,9 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.int32
                                or status.numel() != nf or not status.is_contiguous()):
         raise ValueError("pixels_gpu: status must be a contiguous int32 [nframes] tensor")
-    pitch = 3 * width if pitch is None else int(pitch)
+    if pitch is None:
+        pitch = (3 * width + 7) // 8 * 8 if any_size else 3 * width
+    pitch = int(pitch)
     if pitch < 3 * width or pitch % 8:
         raise ValueError("pixels_gpu: pitch must be a multiple of 8 and at least 3 * width")
     dev = d_coef.device
@@ -539,9 +575,9 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
           or out.numel() != nf * height * pitch):
         raise ValueError("pixels_gpu: out must be a contiguous uint8 buffer of nframes * H * pitch bytes")
-    need = int(lib.jpgx_pixels_gpu_workspace_size(width, height, sample_ratio, nf))
+    need = int(size_fn(width, height, sample_ratio, nf))
     ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    _check(lib.jpgx_pixels_gpu(d_coef.data_ptr(), cstride, nf, width, height, sample_ratio, d_qt.data_ptr(), qstride,
+    _check(pixels_fn(d_coef.data_ptr(), cstride, nf, width, height, sample_ratio, d_qt.data_ptr(), qstride,
                                status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
                                height * pitch, ws.data_ptr() if need else None, need, _stream_ptr(stream)),
            "jpgx_pixels_gpu")
@@ -550,14 +586,15 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     return out.view(nf, height, pitch)[:, :, :3 * width].unflatten(2, (width, 3))
 
 
-def decode_jpeg(data, device, subinterval: bool = False):
+def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False):
     """Baseline JFIF file(s) in host memory -> RGB on `device`: decode_jpeg_coefficients' header step
     on the host for the geometry, one host-to-device copy of the bytes, then jfif_decode_gpu and
     pixels_gpu on one stream; the coefficients never leave the device.  data: bytes -> uint8 [H][W][3];
     a list of files of one geometry -> [n][H][W][3].  The pixels are libjpeg's default decoder's.
     Raises JpgxError for a frame whose status is nonzero (that reads the statuses back, a
     synchronisation).  subinterval: as jfif_decode_gpu's; the choice for files without restart
-    intervals, which one lane decodes otherwise."""
+    intervals, which one lane decodes otherwise.  any_size: files of any width and height (a list is
+    still files of one geometry); the default refuses a size that is no multiple of the MCU."""
     import torch
     from . import compat
     single = isinstance(data, (bytes, bytearray, memoryview))
@@ -567,7 +604,7 @@ def decode_jpeg(data, device, subinterval: bool = False):
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("decode_jpeg: device must be a GPU")
-    info = compat.jfif_info(files[0])
+    info = compat.jfif_info(files[0], any_size=any_size)
     W, H, sr = info["width"], info["height"], info["sample_ratio"]
     cap = max(len(f) for f in files)
     host = np.zeros((len(files), cap), np.uint8)
@@ -575,8 +612,8 @@ def decode_jpeg(data, device, subinterval: bool = False):
         host[k, :len(f)] = np.frombuffer(f, np.uint8)
     d_files = torch.from_numpy(host).to(dev)
     lens = torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
-    coef, qt, status = jfif_decode_gpu(d_files, lens, W, H, sr, subinterval=subinterval)
-    rgb = pixels_gpu(coef, W, H, sr, d_qt=qt, status=status)
+    coef, qt, status = jfif_decode_gpu(d_files, lens, W, H, sr, subinterval=subinterval, any_size=any_size)
+    rgb = pixels_gpu(coef, W, H, sr, d_qt=qt, status=status, any_size=any_size)
     for rc in status.cpu().tolist():
         _check(int(rc), "jpgx_jfif_decode_gpu")
     return rgb[0] if single else rgb

@@ -18,7 +18,7 @@ import ctypes
 
 import numpy as np
 
-from . import JpgxError, lib
+from . import JpgxError, coded_size, lib
 
 c_int_p = ctypes.POINTER(ctypes.c_int)
 
@@ -106,6 +106,8 @@ def _setup(L):
     L.jpgx_read_jfif_sub.argtypes = [vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_size_t, vp,
                                      ctypes.POINTER(JfifInfo), vp]
     L.jpgx_pixels_host.argtypes = [vp, i, i, i, vp, vp, ctypes.c_size_t, i]
+    for name in ("jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host"):
+        getattr(L, name + "_any").argtypes = getattr(L, name).argtypes
 
 
 _setup(lib)
@@ -295,28 +297,31 @@ def _info_dict(info: JfifInfo) -> dict:
                 nb_y=info.nb_y, nb_c=info.nb_c)
 
 
-def jfif_info(data) -> dict:
+def jfif_info(data, any_size: bool = False) -> dict:
     """jpgx_jfif_info_of: the header walk of a baseline JFIF file (bytes) -> width, height,
-    sample_ratio, restart_interval, scan_offset, nb_y, nb_c.  JpgxError(EJFIF_HEADER) when refused."""
+    sample_ratio, restart_interval, scan_offset, nb_y, nb_c.  JpgxError(EJFIF_HEADER) when refused.
+    any_size: jpgx_jfif_info_of_any -- any width and height; nb_y and nb_c are the coded frame's."""
     buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
     info = JfifInfo()
-    _check(lib.jpgx_jfif_info_of(buf.ctypes.data, len(data), ctypes.byref(info)), "jpgx_jfif_info_of")
+    fn = lib.jpgx_jfif_info_of_any if any_size else lib.jpgx_jfif_info_of
+    _check(fn(buf.ctypes.data, len(data), ctypes.byref(info)), "jpgx_jfif_info_of")
     return _info_dict(info)
 
 
-def read_jfif(data, nthreads: int = 1) -> dict:
+def read_jfif(data, nthreads: int = 1, any_size: bool = False) -> dict:
     """jpgx_read_jfif: a baseline JFIF file (bytes) -> dict(coef, qt, width, height, sample_ratio,
     restart_interval): coef int16 [3][nb][64] for 4:4:4, [nb + 2 nbc][64] (Y | Cb | Cr) for 4:2:2 /
     4:2:0 -- what the writers above take; qt uint16 [2][64] (Y's table, the chroma table; zig-zag
     order).  The restart intervals are decoded on `nthreads` threads (0: one per CPU).
-    JpgxError(EJFIF_HEADER / EJFIF_SCAN) when the file is refused."""
-    info = jfif_info(data)
+    JpgxError(EJFIF_HEADER / EJFIF_SCAN) when the file is refused.  any_size: jpgx_read_jfif_any --
+    a file of any width and height; width and height are the file's, coef the coded frame's."""
+    info = jfif_info(data, any_size)
     buf = np.frombuffer(bytes(data), np.uint8)
     nblk = info["nb_y"] + 2 * info["nb_c"]
     coef = np.empty((nblk, 64), np.int16)
     qt = np.zeros((2, 64), np.uint16)
     got = JfifInfo()
-    _check(lib.jpgx_read_jfif(buf.ctypes.data, len(buf), nthreads, coef.ctypes.data, coef.size,
+    _check((lib.jpgx_read_jfif_any if any_size else lib.jpgx_read_jfif)(buf.ctypes.data, len(buf), nthreads, coef.ctypes.data, coef.size,
                               qt.ctypes.data, ctypes.byref(got)), "jpgx_read_jfif")
     if info["sample_ratio"] == 0:
         coef = coef.reshape(3, info["nb_y"], 64)
@@ -330,17 +335,18 @@ class JfifSubStats(ctypes.Structure):
         "units_across_sub", "units_across_tile")]
 
 
-def read_jfif_sub(data, sub_bytes: int = 0, tile_subs: int = 0) -> dict:
+def read_jfif_sub(data, sub_bytes: int = 0, tile_subs: int = 0, any_size: bool = False) -> dict:
     """jpgx_read_jfif_sub: read_jfif by the routines of the device decoder that works inside a restart
     interval, subsequences of sub_bytes bytes and tiles of tile_subs subsequences
-    (0, 0: the kernel's shape).  read_jfif's dict and `stats`, a dict of the twin's counters."""
-    info = jfif_info(data)
+    (0, 0: the kernel's shape).  read_jfif's dict and `stats`, a dict of the twin's counters.
+    any_size: jpgx_read_jfif_sub_any, as read_jfif's."""
+    info = jfif_info(data, any_size)
     buf = np.frombuffer(bytes(data), np.uint8)
     nblk = info["nb_y"] + 2 * info["nb_c"]
     coef = np.empty((nblk, 64), np.int16)
     qt = np.zeros((2, 64), np.uint16)
     got, stats = JfifInfo(), JfifSubStats()
-    _check(lib.jpgx_read_jfif_sub(buf.ctypes.data, len(buf), sub_bytes, tile_subs, coef.ctypes.data, coef.size,
+    _check((lib.jpgx_read_jfif_sub_any if any_size else lib.jpgx_read_jfif_sub)(buf.ctypes.data, len(buf), sub_bytes, tile_subs, coef.ctypes.data, coef.size,
                                   qt.ctypes.data, ctypes.byref(got), ctypes.byref(stats)), "jpgx_read_jfif_sub")
     if info["sample_ratio"] == 0:
         coef = coef.reshape(3, info["nb_y"], 64)
@@ -350,19 +356,23 @@ def read_jfif_sub(data, sub_bytes: int = 0, tile_subs: int = 0) -> dict:
 
 
 def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt: np.ndarray,
-                nthreads: int = 0, pitch: int | None = None) -> np.ndarray:
+                nthreads: int = 0, pitch: int | None = None, any_size: bool = False) -> np.ndarray:
     """jpgx_pixels_host: one frame's coefficients (read_jfif's layout) and its uint16 [2][64] zig-zag
     tables -> uint8 [H][W][3], libjpeg's default decoder's pixels, on `nthreads`
-    threads (0: one per CPU).  pitch: bytes between pixel rows of the buffer the result is a view of."""
+    threads (0: one per CPU).  pitch: bytes between pixel rows of the buffer the result is a view of.
+    any_size: jpgx_pixels_host_any -- coef is the coded frame's, width and height the visible frame's."""
     coef = np.ascontiguousarray(coef, np.int16)
     qt = np.ascontiguousarray(qt, np.uint16)
-    nb = (width // 8) * (height // 8)
+    cw, ch = width, height
+    if any_size and sample_ratio in (0, 1, 2) and 0 < width < 65536 and 0 < height < 65536:
+        cw, ch = coded_size(width, height, sample_ratio)
+    nb = (cw // 8) * (ch // 8)
     nbc = (nb, nb // 2, nb // 4)[sample_ratio] if sample_ratio in (0, 1, 2) else nb
     if qt.shape != (2, 64) or width <= 0 or height <= 0 or coef.size < (nb + 2 * nbc) * 64:
         raise ValueError("pixels_host: qt [2][64], and coef must hold nb + 2 nbc blocks")
     pitch = 3 * width if pitch is None else int(pitch)
     buf = np.empty((height, max(pitch, 1)), np.uint8)
-    _check(lib.jpgx_pixels_host(coef.ctypes.data, width, height, sample_ratio, qt.ctypes.data, buf.ctypes.data,
+    _check((lib.jpgx_pixels_host_any if any_size else lib.jpgx_pixels_host)(coef.ctypes.data, width, height, sample_ratio, qt.ctypes.data, buf.ctypes.data,
                                 pitch, nthreads), "jpgx_pixels_host")
     return buf[:, :3 * width].reshape(height, width, 3)
 

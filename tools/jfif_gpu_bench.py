@@ -51,7 +51,21 @@ input and sample mode (4:4:4, and true 4:2:2 / 4:2:0 from JPGX_FLAG_SUBSAMPLE):
   host_route_s    the route without it: the coefficients copied to pinned host memory +
                   jpgx_pixels_host on 16 threads, frame after frame; best of 2 (host_route_d2h_s: the copy)
   pixels_equal    every frame == jpgx_pixels_host, before and after the timed calls
-Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels] [OUT.json]"""
+With --pixels --any-size the run times the entry points for files of any size (jpgx_pixels_gpu_any,
+jpgx_jfif_decode_gpu_any) beside the plain ones and writes profiles/jfif_gpu_px_any.json; per input and
+sample mode, the calls taken in turn, several passes, in one process:
+  plain_us        (a) jpgx_pixels_gpu at 3840 x 2160, this library; parent_plain_us: the same call on the
+                  library named by --parent-lib=PATH (a build of the parent commit), when given
+  any_full_us     (b) jpgx_pixels_gpu_any at 3840 x 2160; any_full_over_plain: the medians' ratio
+  any_odd_us      (c) jpgx_pixels_gpu_any at 3839 x 2159 on the same coefficients (the coded frame is the
+                  same); any_odd_over_plain
+  pixels_equal    (b) == (a) on every frame; (c) == jpgx_pixels_host_any on two frames, and no byte outside
+                  [0, 3 * 3839) x [0, 2159) written
+and once, for the photo-like input, "decoder_3839x2159": its frames cropped, written by Pillow with one MCU
+row per restart interval (4:4:4 and 4:2:0) and decoded by jpgx_jfif_decode_gpu_any with both scan kernels
+(decode_us, decode_sub_us; statuses 0, both equal, frame 0 == jpgx_read_jfif_any).
+Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels [--any-size
+[--parent-lib=PATH]]] [OUT.json]"""
 import json
 import os
 import sys
@@ -470,19 +484,160 @@ def measure_px(name, d_rgb, dev):
     return res
 
 
+PARENT = None                           # --parent-lib: the parent commit's library, loaded beside this one
+FILL = 0x7A
+
+
+def median(ts):
+    return sorted(ts)[len(ts) // 2]
+
+
+def decoder_any(d_rgb, dev):
+    """the photo-like frames at 3839 x 2159, Pillow's files with one MCU row per interval, both scan kernels"""
+    import io
+
+    from PIL import Image
+    Wo, Ho = W - 1, H - 1
+    host = d_rgb[:, :Ho, :Wo].cpu().numpy()
+    stream = torch.cuda.current_stream().cuda_stream
+    out = []
+    for sr in (0, 2):
+        files = []
+        for f in range(F):
+            b = io.BytesIO()
+            Image.fromarray(host[f]).save(b, "JPEG", quality=Q, subsampling=sr, restart_marker_rows=1)
+            files.append(b.getvalue())
+        cap = (max(len(x) for x in files) + 15) // 16 * 16
+        packed = np.zeros((F, cap), np.uint8)
+        for f, x in enumerate(files):
+            packed[f, :len(x)] = np.frombuffer(x, np.uint8)
+        d_files = torch.from_numpy(packed).to(dev)
+        d_lens = torch.tensor([len(x) for x in files], dtype=torch.int64, device=dev)
+        cw, ch = jpgx.coded_size(Wo, Ho, sr)
+        nb = (cw // 8) * (ch // 8)
+        per = (nb + 2 * (nb // (1, 2, 4)[sr])) * 64
+        qt = torch.empty((F, 2, 64), dtype=torch.int16, device=dev)
+        status = torch.empty(F, dtype=torch.int32, device=dev)
+        got, ts = {}, {}
+        for flags in (0, jpgx.JFIF_DECODE_SUBINTERVAL):
+            coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+            need = int(jpgx.lib.jpgx_jfif_decode_gpu_any_workspace_size(Wo, Ho, sr, F, cap, flags))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+            def dec():
+                rc = jpgx.lib.jpgx_jfif_decode_gpu_any(d_files.data_ptr(), cap, d_lens.data_ptr(), F, Wo, Ho, sr, flags,
+                                                       coef.data_ptr(), per, qt.data_ptr(), status.data_ptr(),
+                                                       ws.data_ptr(), need, stream)
+                assert rc == 0, rc
+
+            dec()
+            torch.cuda.synchronize()
+            ok = status.cpu().tolist() == [0] * F
+            ts[flags] = timed(dec, calls=5)
+            got[flags] = (coef, ok)
+        ref = C.read_jfif(files[0], HOST_THREADS, any_size=True)["coef"].reshape(-1)
+        equal = bool(got[0][1] and got[1][1] and torch.equal(got[0][0], got[1][0])
+                     and np.array_equal(got[0][0][0].cpu().numpy(), ref))
+        out.append({"sample_ratio": sr, "width": Wo, "height": Ho, "file_bytes": [len(x) for x in files],
+                    "decode_us": ts[0], "decode_sub_us": ts[1], "coefficients_equal": equal})
+    return out
+
+
+def measure_px_any(name, d_rgb, dev):
+    nb = (W // 8) * (H // 8)
+    Wo, Ho = W - 1, H - 1               # the same coded frame in all three sample modes
+    qt_host = jpgx.jfif_qt(Q)
+    d_qt = torch.from_numpy(qt_host.view(np.int16)).to(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"input": name, "modes": []}
+    for sr in (0, 1, 2):
+        assert jpgx.coded_size(Wo, Ho, sr) == (W, H)
+        flags = jpgx.FLAG_SUBSAMPLE if sr else 0
+        nbc = jpgx.chroma_blocks(W, 0, H // 8, sr, flags)
+        per = (nb + 2 * nbc) * 64
+        coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+        fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+        p = jpgx.default_params(W, H, Q, sr, flags=flags)
+        xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+        jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+        torch.cuda.synchronize()
+        rgb = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
+        wsb = int(jpgx.lib.jpgx_pixels_gpu_workspace_size(W, H, sr, F))
+        assert wsb == int(jpgx.lib.jpgx_pixels_gpu_any_workspace_size(Wo, Ho, sr, F))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+
+        def call(fn, w, h):
+            def run():
+                rc = fn(coef.data_ptr(), per, F, w, h, sr, d_qt.data_ptr(), 0, None, rgb.data_ptr(), 3 * W, 3 * W * H,
+                        ws.data_ptr() if wsb else None, wsb, stream)
+                assert rc == 0, rc
+            return run
+
+        fns = {"plain_us": call(jpgx.lib.jpgx_pixels_gpu, W, H),
+               "any_full_us": call(jpgx.lib.jpgx_pixels_gpu_any, W, H),
+               "any_odd_us": call(jpgx.lib.jpgx_pixels_gpu_any, Wo, Ho)}
+        if PARENT is not None:
+            fns["parent_plain_us"] = call(PARENT.jpgx_pixels_gpu, W, H)
+        # the checks: (b) == (a); (c) == the host on two frames, nothing written outside the visible frame
+        fns["plain_us"]()
+        want = rgb.clone()
+        rgb.fill_(FILL)
+        fns["any_full_us"]()
+        equal = bool(torch.equal(rgb, want))
+        rgb.fill_(FILL)
+        fns["any_odd_us"]()
+        torch.cuda.synchronize()
+        equal = equal and bool((rgb[:, :, Wo:] == FILL).all()) and bool((rgb[:, Ho:] == FILL).all())
+        host_coef = coef[:2].cpu().numpy()
+        for f in range(2):
+            ref = C.pixels_host(host_coef[f], Wo, Ho, sr, qt_host, HOST_THREADS, any_size=True)
+            equal = equal and bool(np.array_equal(rgb[f, :Ho, :Wo].cpu().numpy(), ref))
+        ts = {k: [] for k in fns}
+        for _ in range(3):                               # the calls taken in turn, pass after pass
+            for k in sorted(fns):
+                ts[k] += timed(fns[k], calls=10, rounds=3, settle=0.3)
+        m = {"sample_ratio": sr, "pixels_equal": equal, "repeat_equal": equal}
+        for k in fns:
+            m[k] = sorted(ts[k])
+        base = median(ts["plain_us"])
+        m["plain_median_us"] = base
+        m["any_full_over_plain"] = median(ts["any_full_us"]) / base
+        m["any_odd_over_plain"] = median(ts["any_odd_us"]) / base
+        if PARENT is not None:
+            m["parent_plain_median_us"] = median(ts["parent_plain_us"])
+            m["parent_spread_us"] = max(ts["parent_plain_us"]) - min(ts["parent_plain_us"])
+            m["plain_minus_parent_us"] = base - m["parent_plain_median_us"]
+        res["modes"].append(m)
+        del coef, rgb, ws, want
+    if name.startswith("flat"):
+        res["decoder_3839x2159"] = decoder_any(d_rgb, dev)
+    res["bytes_equal"] = all(m["pixels_equal"] for m in res["modes"]) and all(
+        d["coefficients_equal"] for d in res.get("decoder_3839x2159", []))
+    res["repeat_equal"] = res["bytes_equal"]
+    return res
+
+
 def main():
-    modes = ("--optimize", "--decode", "--pixels", "--subinterval")
-    args = [a for a in sys.argv[1:] if a not in modes]
-    optimize, decoding, pixels, sub = (m in sys.argv[1:] for m in modes)
+    global PARENT
+    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size")
+    for a in sys.argv[1:]:
+        if a.startswith("--parent-lib="):
+            # an older build has only the plain entry points: bind the one call that is timed
+            import ctypes
+            PARENT = ctypes.CDLL(os.path.abspath(a.split("=", 1)[1]))
+            PARENT.jpgx_pixels_gpu.argtypes = jpgx.lib.jpgx_pixels_gpu.argtypes
+    args = [a for a in sys.argv[1:] if a not in modes and not a.startswith("--parent-lib=")]
+    optimize, decoding, pixels, sub, any_size = (m in sys.argv[1:] for m in modes)
     assert decoding or not sub, "--subinterval goes with --decode"
-    run = measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
+    assert pixels or not any_size, "--any-size goes with --pixels"
+    run = measure_px_any if any_size else measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
         measure_opt if optimize else measure
     dst = args[0] if args else os.path.join(
-        REPO, "profiles", "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
+        REPO, "profiles", "jfif_gpu_px_any.json" if any_size else "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
         "jfif_gpu_dec.json" if decoding else "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py" + (" --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --pixels --any-size" if any_size else " --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
