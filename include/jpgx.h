@@ -358,6 +358,48 @@ int jpgx_pixels_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t 
                         uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
                         void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* ---- one-component (grayscale) files -------------------------------------
+ * The entry points above refuse a file with one component (JPGX_EJFIF_HEADER); the _gray family takes
+ * such files and only such files, of any width and height in 1 .. 65535.  What is accepted is stated
+ * at jpgx_read_jfif_gray (jpgx_compat.h): one component with any sampling factors 1 .. 4, which are
+ * ignored, in one scan.  The file codes nb = ceil(width / 8) * ceil(height / 8) blocks in raster
+ * order; DRI counts blocks.  Coefficients: Y [nb][64], zig-zag.  One table of [64] per frame.
+ *
+ * jpgx_jfif_decode_gpu_gray_workspace_size / jpgx_jfif_decode_gpu_gray: jpgx_jfif_decode_gpu_any's
+ * contract without sample_ratio, word for word: decode_flags 0 or JPGX_JFIF_DECODE_SUBINTERVAL;
+ * coef_frame_stride a multiple of 64 and at least nb * 64; frame f's table at d_qt + f * 64 (zeros
+ * for a refused header; d_qt may be NULL); d_status[f], the coefficients and the table equal
+ * jpgx_read_jfif_gray's for the same bytes; a file whose SOF states another size, or that has three
+ * components, has status JPGX_EJFIF_HEADER.  The argument checks, their order and their codes are
+ * the _any call's, all before the first device call; asynchronous, capturable, stateless, no memset;
+ * the same five launches with the header and scan kernels in their one-component instantiations.
+ * Workspace (0 from the query for bad arguments), every part rounded up to 16 bytes: per frame the
+ * header walk's notes (sizeof(jxd_frame), csrc/jx_jfif_dec.h) and four decode tables
+ * (4 * sizeof(jxd_tab)), 4 bytes of status, 4 bytes per 4 KiB chunk of file_cap, and 4 bytes per
+ * block (nmcu = nb restart markers' places at most). */
+size_t jpgx_jfif_decode_gpu_gray_workspace_size(int width, int height, size_t nframes, size_t file_cap,
+                                                unsigned decode_flags);
+int jpgx_jfif_decode_gpu_gray(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len,
+                              size_t nframes, int width, int height, unsigned decode_flags,
+                              int16_t *d_coef, size_t coef_frame_stride, uint16_t *d_qt,
+                              int32_t *d_status, void *d_workspace, size_t workspace_bytes,
+                              void *stream);
+
+/* The pixels of one-component frames: libjpeg's default decoder's, equal byte for byte to
+ * jpgx_pixels_host_gray.  channels 1: the range-limited inverse DCT's sample (JCS_GRAYSCALE);
+ * channels 3: that sample as R = G = B (libjpeg's gray-to-RGB).  No workspace.  d_coef: Y [nb][64] per
+ * frame, coef_frame_stride a multiple of 64 and at least nb * 64.  d_qt: frame f's table at
+ * d_qt + f * qt_frame_stride; 64 is what jpgx_jfif_decode_gpu_gray leaves, 0 means one table for the
+ * batch, [1, 63] is JPGX_EARG.  out_pitch is at least channels * width and a multiple of 8,
+ * out_frame_stride at least out_pitch * height and a multiple of 8; only bytes
+ * [0, channels * width) of rows [0, height) are written; a frame with d_status[f] != 0 is skipped and
+ * untouched.  channels other than 1 and 3 is JPGX_EARG; a side outside 1 .. 65535 is JPGX_EGEOMETRY.
+ * The alignments, the remaining checks, their order and everything else are jpgx_pixels_gpu_any's. */
+int jpgx_pixels_gpu_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes,
+                         int width, int height, const uint16_t *d_qt, size_t qt_frame_stride,
+                         const int32_t *d_status, uint8_t *d_out, size_t out_pitch,
+                         size_t out_frame_stride, int channels, void *stream);
+
 /* The two tables exactly as the JFIF writers put them into DQT for `quality` (the divisors the
  * forward path applied, zig-zag order): jpgx_blocks_gpu's output can be turned into pixels without
  * writing a file.  JPGX_EQUALITY outside 1..97, JPGX_EARG for a null qt. */

@@ -269,6 +269,33 @@ int jpgx_read_jfif_sub_any(const uint8_t *file, size_t len, uint32_t sub_bytes, 
 int jpgx_pixels_host_any(const int16_t *coef, int width, int height, int sample_ratio,
                          const uint16_t qt[2][64], uint8_t *rgb, size_t pitch, int nthreads);
 
+/* One-component (grayscale) baseline files (include/jpgx.h: the _gray family).  Accepted:
+ * SOF0, or SOF1 with 8-bit samples, with ONE component (any id, Tq <= 3, sampling factors 1 .. 4
+ * each, which are ignored: the scan is not interleaved, so its MCU is one block whatever SOF says,
+ * T.81 A.2.2) and one scan of that component (Td, Ta <= 1, Ss 0, Se 63, Ah / Al 0); DQT, DHT, DRI,
+ * APPn and COM as for jpgx_read_jfif, only the tables the component selects need to be there; any
+ * width and height in 1 .. 65535.  Everything else, a three-component file included, is
+ * JPGX_EJFIF_HEADER.  The file codes nb = ceil(width / 8) * ceil(height / 8) blocks in raster order;
+ * DRI counts blocks, and an interval may begin and end inside a block row.
+ * info: the SOF's width and height, sample_ratio 0, nb_y = nb, nb_c = 0, restart_interval in blocks.
+ * coef: Y [nb][64], zig-zag; coef_cap at least nb * 64.  qt: the component's table, zig-zag order.
+ * jpgx_read_jfif_gray keeps jpgx_read_jfif_any's contract and return codes otherwise, and
+ * jpgx_read_jfif_sub_gray, the host twin of the device decoder's one-component kernel, returns what
+ * jpgx_read_jfif_gray returns for every input and every shape.
+ * jpgx_pixels_host_gray: libjpeg's default decoder's pixels of such a frame, `channels` bytes per
+ * pixel: 1 is the range-limited inverse DCT's sample (JCS_GRAYSCALE), 3 is that sample as R = G = B
+ * (libjpeg's gray-to-RGB).  Writes bytes [0, channels * width) of rows [0, height), `pitch` bytes
+ * apart.  JPGX_EARG: null pointers, channels other than 1 and 3, pitch < channels * width,
+ * nthreads < 0; JPGX_EGEOMETRY: a side outside 1 .. 65535. */
+int jpgx_jfif_info_of_gray(const uint8_t *file, size_t len, jpgx_jfif_info *info);
+int jpgx_read_jfif_gray(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap,
+                        uint16_t qt[64], jpgx_jfif_info *info);
+int jpgx_read_jfif_sub_gray(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs,
+                            int16_t *coef, size_t coef_cap, uint16_t qt[64], jpgx_jfif_info *info,
+                            jpgx_jfif_sub_stats *stats);
+int jpgx_pixels_host_gray(const int16_t *coef, int width, int height, const uint16_t qt[64],
+                          uint8_t *out, size_t pitch, int channels, int nthreads);
+
 /* encode_bmp_to_jpeg with flags: JPGX_FLAG_SUBSAMPLE and sample_ratio 1/2 write a truly
  * subsampled JFIF (extension); otherwise exactly jpgx_encode_bmp_to_jpeg.  GPU `device`. */
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

@@ -22,6 +22,12 @@
  *                which the host twin jpgx_read_jfif_sub runs too
  * jpgx_jfif_decode_gpu_any (files of any width and height) differs in the header kernel's mode alone:
  * the other kernels see the coded frame's counts.
+ * jpgx_jfif_decode_gpu_gray (one-component files) launches k_jd_header_gray and
+ * k_jd_scan_gray or k_jd_sub_gray: the header walk in its one-component mode and the scan kernels' own
+ * bodies in their one-component forms (jd_scan_body<1>, jx_jd_sub_body.h): an MCU is a block, DRI
+ * counts blocks, one predictor.  k_jd_count, k_jd_frame and k_jd_place do not look at components and
+ * serve as they are.  The plain kernels are instruction for instruction what they were before the
+ * one-component ones came (profiles/gray_isa_identity.txt), which decided how the bodies are shared.
  * The interval's blocks are zeroed and filled by the lanes that decode them; no memset.
  * The call keeps no state and is capturable.
  */
@@ -105,6 +111,26 @@ __global__ __launch_bounds__(kWave) void k_jd_header(const JdArgs a)
         for (uint32_t i = t; i < 128u; i += kWave) a.qt[(size_t)f * 128 + i] = rc_s ? (uint16_t)0 : (&fr->qt[0][0])[i];
 }
 
+/* k_jd_header for the one-component frame: the walk's GRAY mode, the stated width and height compared
+ * (hs = vs = 1 on both sides), and ONE table per frame in d_qt */
+__global__ __launch_bounds__(kWave) void k_jd_header_gray(const JdArgs a)
+{
+    __shared__ int32_t rc_s;
+    const uint32_t f = blockIdx.x, t = threadIdx.x;
+    jxd_frame *fr = a.frames + f;
+    if (t == 0) {
+        const unsigned long long len = a.len[f];
+        int rc = JPGX_EJFIF_HEADER;
+        if (len <= a.fstride) rc = jxd_parse_header<1, 1>(a.files + (size_t)f * a.fstride, (size_t)len, fr, a.tabs + 4 * (size_t)f);
+        if (!rc && (fr->width != a.width || fr->height != a.height)) rc = JPGX_EJFIF_HEADER;
+        a.st[f] = rc;
+        rc_s = rc;
+    }
+    __syncthreads();                    /* thread 0's stores to *fr are visible to the workgroup */
+    if (a.qt)
+        for (uint32_t i = t; i < 64u; i += kWave) a.qt[(size_t)f * 64 + i] = rc_s ? (uint16_t)0 : fr->qt[0][i];
+}
+
 /* the restart markers that begin in this lane's piece of chunk c: a bit per byte */
 __device__ __forceinline__ uint32_t jd_piece(const uint8_t *file, size_t len, size_t scan_off, uint32_t c, uint32_t t)
 {
@@ -177,7 +203,8 @@ __global__ __launch_bounds__(kT) void k_jd_place(const JdArgs a)
     }
 }
 
-__global__ __launch_bounds__(kWave) void k_jd_scan(const JdArgs a)
+template <int GRAY>
+__device__ __forceinline__ void jd_scan_body(const JdArgs &a)
 {
     __shared__ jxd_tab tabs[4];
     static_assert(sizeof(jxd_tab) % 4 == 0, "tables are copied by dwords");
@@ -200,10 +227,16 @@ __global__ __launch_bounds__(kWave) void k_jd_scan(const JdArgs a)
     /* the header kernel has checked the file's geometry against the stated one, for which the
      * caller's coef_frame_stride was checked: fr->nblk blocks fit the frame's slot */
     if (fr->nblk != a.nblk) return;
-    if (jxd_decode_interval(a.files + (size_t)f * a.fstride, len, begin, end, fr, tabs, mcu0, count,
-                            a.coef + (size_t)f * a.cstride))
-        a.status[f] = JPGX_EJFIF_SCAN;
+    const int rc = GRAY ? jxd_decode_interval_gray(a.files + (size_t)f * a.fstride, len, begin, end, fr, tabs, mcu0,
+                                                   count, a.coef + (size_t)f * a.cstride)
+                        : jxd_decode_interval(a.files + (size_t)f * a.fstride, len, begin, end, fr, tabs, mcu0, count,
+                                              a.coef + (size_t)f * a.cstride);
+    if (rc) a.status[f] = JPGX_EJFIF_SCAN;
 }
+
+__global__ __launch_bounds__(kWave) void k_jd_scan(const JdArgs a) { jd_scan_body<0>(a); }
+
+__global__ __launch_bounds__(kWave) void k_jd_scan_gray(const JdArgs a) { jd_scan_body<1>(a); }
 
 /* ---- inside an interval: jx_jfif_sub.h's routines, a lane per subsequence -------- */
 constexpr uint32_t kS = JXS_SUB, kTile = JXS_TILE;
@@ -223,159 +256,31 @@ struct JdTile {
     }
 };
 
-__global__ __launch_bounds__(kT) void k_jd_sub(const JdArgs a)
-{
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    __shared__ jxd_tab tabs[4];
-    __shared__ uint32_t tile_s[(kTile + 2) * kRow];
-    __shared__ uint32_t ex_p[kT], ex_cz[kT];
-    __shared__ uint32_t wtot[kT / 64];
-    __shared__ uint32_t first_bad_s;
-    const uint32_t f = blockIdx.y, t = threadIdx.x;
-    if (a.st[f]) return;                /* the same for the whole workgroup */
-    const jxd_frame *fr = a.frames + f;
-    const uint32_t ni = fr->ni;
-    if (blockIdx.x >= ni || fr->nblk != a.nblk) return;     /* as k_jd_scan: the stated geometry's blocks fit the slot */
-    const uint32_t *src = (const uint32_t *)(a.tabs + 4 * (size_t)f);
-    for (uint32_t i = t; i < 4u * sizeof(jxd_tab) / 4u; i += kT) ((uint32_t *)tabs)[i] = src[i];
-    jxs_tabs tb;
-    jxs_tabs_of(fr, tabs, &tb);
-    const size_t len = (size_t)a.len[f];
-    const uint8_t *file = a.files + (size_t)f * a.fstride;
-    int16_t *coef = a.coef + (size_t)f * a.cstride;
-    const uint32_t *mpos = a.mpos + (size_t)f * a.nmcu;
-    uint32_t err = 0;
-    for (uint32_t iv = blockIdx.x; iv < ni; iv += gridDim.x) {
-        const size_t begin = iv ? (size_t)mpos[iv - 1] + 2 : (size_t)fr->scan_off;
-        const size_t end = iv + 1 < ni ? (size_t)mpos[iv] : len - 2;
-        const uint32_t mcu0 = iv * fr->mpi;
-        const uint32_t count = min(fr->mpi, fr->nmcu - mcu0);
-        const uint32_t nblocks = count * tb.bpm;
-        if (begin > end || end > len) {  /* the same for the whole workgroup */
-            err = 1;
-            continue;
-        }
-        /* the interval's blocks zeroed, 16 bytes a lane; the stores are complete before a coefficient's */
-        for (uint32_t o = t; o < nblocks * 8u; o += kT) {
-            const uint32_t blk = jxs_block_of(fr, mcu0, nblocks, o >> 3);
-            const u4 zero = {0u, 0u, 0u, 0u};
-            if (blk != JXS_INVALID) ((u4 *)(coef + (size_t)blk * 64))[o & 7u] = zero;
-            else err = 1;
-        }
-        __threadfence();
-        __syncthreads();                /* also: the tables are in LDS, the last interval's LDS is free */
-        jxs_state carry = {0u, 0u};
-        uint32_t carry_blocks = 0, done = 0;
-        for (size_t tbeg = begin; tbeg < end; tbeg += (size_t)kS * kTile) {
-            const jxs_tile tile = jxs_tile_of(end - tbeg, kS, kTile);
-            /* load: 16-byte pieces from the boundary before the tile, whole ones by one load */
-            const uint8_t *g0 = file + tbeg;
-            const uint32_t shift = (uint32_t)((uintptr_t)g0 & 15u);
-            const uint32_t npiece = (shift + tile.lim + 15u) / 16u;
-            for (uint32_t k = t; k < npiece; k += kT) {
-                const uint32_t q = 16u * k;         /* the piece's place in LDS, before the padding */
-                u4 v = {0u, 0u, 0u, 0u};
-                if (q >= shift && q + 16u - shift <= tile.lim) {
-                    v = *(const u4 *)(g0 + (q - shift));
-                } else {
-                    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-                    for (uint32_t j = 0; j < 16u; j++)
-                        if (q + j >= shift && q + j - shift < tile.lim) w[j >> 2] |= (uint32_t)g0[q + j - shift] << (8u * (j & 3u));
-                    v.x = w[0], v.y = w[1], v.z = w[2], v.w = w[3];
-                }
-                uint32_t *dst = tile_s + (q / kS) * kRow + (q % kS) / 4u;
-                dst[0] = v.x, dst[1] = v.y, dst[2] = v.z, dst[3] = v.w;
-            }
-            if (t == 0) first_bad_s = kT;
-            __syncthreads();
-            const JdTile rd = {(const uint8_t *)tile_s, shift};
-            const bool active = t * kS < tile.n;
-            const uint32_t sub_end = min((t + 1u) * kS, tile.n);
-            jxs_state entry = carry, exit = {JXS_INVALID, 0u};
-            uint32_t nblk = 0;
-            jxs_nowrite nw;
-            if (active) {
-                err |= jxs_bare_ff(rd, t * kS, sub_end, tile.end_rel);
-                if (t) entry = jxs_guess(rd, t, kS, (uint32_t *)nullptr);
-                jxs_decode_sub(rd, tile.lim, sub_end, entry, &tb, nw, &exit, &nblk);
-            }
-            /* rounds: at most kT, and after r of them the first r + 1 exits are the sequential decoder's */
-            for (uint32_t round = 0; round < kT; round++) {
-                ex_p[t] = exit.p;
-                ex_cz[t] = exit.cz;
-                __syncthreads();
-                int changed = 0;
-                if (active && t) {
-                    const jxs_state prev = {ex_p[t - 1], ex_cz[t - 1]};
-                    if (prev.p != JXS_INVALID && !jxs_same(prev, entry)) {
-                        entry = prev;
-                        jxs_decode_sub(rd, tile.lim, sub_end, entry, &tb, nw, &exit, &nblk);
-                        changed = 1;
-                    }
-                }
-                if (!__syncthreads_or(changed)) break;
-            }
-            /* the first lane whose exit is invalid decoded from a true state, as all before it did */
-            if (active && exit.p == JXS_INVALID) atomicMin(&first_bad_s, t);
-            uint32_t total;
-            const uint32_t ord = carry_blocks + jd_scan(active ? nblk : 0u, wtot, total);
-            const uint32_t first_bad = first_bad_s;
-            int mine = 0;
-            if (active && t <= first_bad && entry.p != JXS_INVALID && ord < nblocks) {
-                jxs_store wr;
-                wr.open(fr, coef, mcu0, nblocks, ord);
-                jxs_state out;
-                uint32_t nb;
-                jxs_decode_sub(rd, tile.lim, sub_end, entry, &tb, wr, &out, &nb);
-                if (out.p == JXS_INVALID) {
-                    err = 1;
-                } else if (wr.ord == nblocks) {             /* this lane completed the interval's last block */
-                    mine = 1;
-                    if (!jxs_tail_ok(rd, tile.lim, tile.end_rel, out.p)) err = 1;
-                }
-            }
-            const uint32_t last_p = ex_p[kT - 1], last_cz = ex_cz[kT - 1];
-            done = (uint32_t)__syncthreads_or(mine);        /* and: the tile's LDS is free */
-            if (done || first_bad < kT) break;              /* nothing behind an invalid state is true */
-            carry.p = last_p - kS * kTile * 8u;             /* seen from the next tile (if there is one) */
-            carry.cz = last_cz;
-            carry_blocks += total;
-        }
-        if (!done) err = 1;
-        /* the DC predictors: per component a running sum over the interval's blocks in decode order,
-         * 256 at a time, each chunk's sums checked against int16 before the carry moves on */
-        __threadfence();
-        if (__syncthreads_or((int)err)) {
-            err = 1;
-            continue;
-        }
-        for (uint32_t comp = 0; comp < 3u; comp++) {
-            const uint32_t per = comp ? 1u : tb.lum, nbk = count * per;
-            uint32_t pred = 0;
-            for (uint32_t i0 = 0; i0 < nbk; i0 += kT) {
-                const uint32_t i = i0 + t;
-                uint32_t blk = JXS_INVALID;
-                if (i < nbk) {
-                    const uint32_t m = i / per, j = comp ? tb.lum + comp - 1u : i - m * per;
-                    blk = jxs_block_of(fr, mcu0, nblocks, m * tb.bpm + j);
-                }
-                const uint32_t d = blk != JXS_INVALID ? (uint32_t)(int32_t)coef[(size_t)blk * 64] : 0u;
-                uint32_t sum;
-                const int32_t dc = (int32_t)(pred + jd_scan(d, wtot, sum) + d);
-                const int out_of_range = dc < -32768 || dc > 32767;
-                if (blk != JXS_INVALID && !out_of_range) coef[(size_t)blk * 64] = (int16_t)dc;
-                if (__syncthreads_or(out_of_range)) {
-                    err = 1;
-                    break;
-                }
-                pred += sum;
-            }
-            if (err) break;
-        }
-    }
-    if (err) a.status[f] = JPGX_EJFIF_SCAN;
-}
+/* the kernel's body, once per frame family (jx_jd_sub_body.h says why it is included and no template) */
+#define JD_SUB_KERNEL k_jd_sub
+#define JD_SUB_TABS_OF jxs_tabs_of
+#define JD_SUB_BLOCK_OF jxs_block_of
+#define JD_SUB_STORE jxs_store
+#define JD_SUB_COMPONENTS 3u
+#include "jx_jd_sub_body.h"
+#undef JD_SUB_KERNEL
+#undef JD_SUB_TABS_OF
+#undef JD_SUB_BLOCK_OF
+#undef JD_SUB_STORE
+#undef JD_SUB_COMPONENTS
+
+/* the one-component frame: jx_jfif_sub.h's one-component block walk, one DC predictor */
+#define JD_SUB_KERNEL k_jd_sub_gray
+#define JD_SUB_TABS_OF jxs_tabs_of_gray
+#define JD_SUB_BLOCK_OF jxs_block_of_gray
+#define JD_SUB_STORE jxs_store_t<1>
+#define JD_SUB_COMPONENTS 1u
+#include "jx_jd_sub_body.h"
+#undef JD_SUB_KERNEL
+#undef JD_SUB_TABS_OF
+#undef JD_SUB_BLOCK_OF
+#undef JD_SUB_STORE
+#undef JD_SUB_COMPONENTS
 
 struct JdLayout {
     size_t frames, tabs, st, cnt, mpos, total;
@@ -385,13 +290,22 @@ struct JdLayout {
  * JPGX_EGEOMETRY.  The kernels keep the six words of geometry their arguments always had (with the
  * whole jx_frame as argument and in jxd_frame the decoder was 0.9 - 3.1 % slower):
  * the host fills them from the frame */
-int jd_geometry(bool any, int width, int height, int sample_ratio, size_t nframes, size_t file_cap, JdArgs &a, JdLayout &l)
+enum { kPlain, kAny, kGray };           /* the entry points' families */
+
+int jd_geometry(int mode, int width, int height, int sample_ratio, size_t nframes, size_t file_cap, JdArgs &a, JdLayout &l)
 {
     jx_frame f;
     jx_frame_any fa;
-    const int why = any ? jx_frame_make_any(width, height, sample_ratio, &fa) : jx_frame_make(width, height, sample_ratio, &f);
+    jx_frame_gray fg;
+    const int why = mode == kGray ? jx_frame_make_gray(width, height, &fg)
+                    : mode == kAny ? jx_frame_make_any(width, height, sample_ratio, &fa)
+                                   : jx_frame_make(width, height, sample_ratio, &f);
     const int rc = jx_frame_rc_decoder(why);
-    if (any && !why) f = fa.c;          /* the coded frame: what the coefficients and the MCU counts are of */
+    if (mode == kAny && !why) f = fa.c; /* the coded frame: what the coefficients and the MCU counts are of */
+    if (mode == kGray && !why) {        /* one block per MCU: the words the kernels compare and size by */
+        f.hs = f.vs = 1;
+        f.nblk = f.nbc = fg.nb;
+    }
     if (rc == JPGX_EARG || !jx_frames_ok(nframes) || file_cap == 0 || file_cap > 0xffffffffull - kChunk)
         return JPGX_EARG;
     if (rc) return rc;
@@ -412,9 +326,10 @@ int jd_geometry(bool any, int width, int height, int sample_ratio, size_t nframe
     return JPGX_OK;
 }
 
-/* jpgx_jfif_decode_gpu_ex (any = false) and jpgx_jfif_decode_gpu_any: the checks, their order and the
- * launches are the same but for the geometry's rule and the header kernel's mode */
-int jd_decode(bool any, const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
+/* jpgx_jfif_decode_gpu_ex (kPlain), jpgx_jfif_decode_gpu_any and jpgx_jfif_decode_gpu_gray: the checks,
+ * their order and the launches are the same but for the geometry's rule, the header kernel's mode and,
+ * for kGray, the scan kernel's */
+int jd_decode(int mode, const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
               int height, int sample_ratio, unsigned decode_flags, int16_t *d_coef, size_t coef_frame_stride,
               uint16_t *d_qt, int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream)
 {
@@ -425,7 +340,7 @@ int jd_decode(bool any, const uint8_t *d_files, size_t file_stride, const uint64
         ((uintptr_t)d_coef & 15) || ((uintptr_t)d_status & 3) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_workspace & 15) ||
         (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL))
         return JPGX_EARG;
-    const int rc = jd_geometry(any, width, height, sample_ratio, nframes, file_stride, a, l);
+    const int rc = jd_geometry(mode, width, height, sample_ratio, nframes, file_stride, a, l);
     if (rc) return rc;
     if (!jx_coef_batch_ok(coef_frame_stride, a.nblk)) return JPGX_EARG;
     if (workspace_bytes < l.total) return JPGX_EWORKSPACE;
@@ -444,15 +359,20 @@ int jd_decode(bool any, const uint8_t *d_files, size_t file_stride, const uint64
     a.mpos = (uint32_t *)(ws + l.mpos);
     hipStream_t s = (hipStream_t)stream;
     const dim3 per_frame((unsigned)nframes), per_chunk(a.nchunk, (unsigned)nframes);
-    if (any) hipLaunchKernelGGL(k_jd_header<1>, per_frame, dim3(kWave), 0, s, a);
+    if (mode == kGray) hipLaunchKernelGGL(k_jd_header_gray, per_frame, dim3(kWave), 0, s, a);
+    else if (mode == kAny) hipLaunchKernelGGL(k_jd_header<1>, per_frame, dim3(kWave), 0, s, a);
     else hipLaunchKernelGGL(k_jd_header<0>, per_frame, dim3(kWave), 0, s, a);
     hipLaunchKernelGGL(k_jd_count, per_chunk, dim3(kT), 0, s, a);
     hipLaunchKernelGGL(k_jd_frame, per_frame, dim3(kT), 0, s, a);
     hipLaunchKernelGGL(k_jd_place, per_chunk, dim3(kT), 0, s, a);
-    if (decode_flags & JPGX_JFIF_DECODE_SUBINTERVAL)
-        hipLaunchKernelGGL(k_jd_sub, dim3(min(a.nmcu, kSubGrid), (unsigned)nframes), dim3(kT), 0, s, a);
-    else
-        hipLaunchKernelGGL(k_jd_scan, dim3((a.nmcu + kWave - 1) / kWave, (unsigned)nframes), dim3(kWave), 0, s, a);
+    const dim3 sub_grid(min(a.nmcu, kSubGrid), (unsigned)nframes), scan_grid((a.nmcu + kWave - 1) / kWave, (unsigned)nframes);
+    if (decode_flags & JPGX_JFIF_DECODE_SUBINTERVAL) {
+        if (mode == kGray) hipLaunchKernelGGL(k_jd_sub_gray, sub_grid, dim3(kT), 0, s, a);
+        else hipLaunchKernelGGL(k_jd_sub, sub_grid, dim3(kT), 0, s, a);
+    } else {
+        if (mode == kGray) hipLaunchKernelGGL(k_jd_scan_gray, scan_grid, dim3(kWave), 0, s, a);
+        else hipLaunchKernelGGL(k_jd_scan, scan_grid, dim3(kWave), 0, s, a);
+    }
     return jx_hip_rc(hipGetLastError());
 }
 
@@ -466,7 +386,7 @@ size_t jpgx_jfif_decode_gpu_workspace_size_ex(int width, int height, int sample_
     JdArgs a;
     JdLayout l;
     if (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL) return 0;
-    if (jd_geometry(false, width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
+    if (jd_geometry(kPlain, width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
     return l.total;
 }
 
@@ -480,7 +400,7 @@ int jpgx_jfif_decode_gpu_ex(const uint8_t *d_files, size_t file_stride, const ui
                             size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status, void *d_workspace,
                             size_t workspace_bytes, void *stream)
 {
-    return jd_decode(false, d_files, file_stride, d_len, nframes, width, height, sample_ratio, decode_flags, d_coef,
+    return jd_decode(kPlain, d_files, file_stride, d_len, nframes, width, height, sample_ratio, decode_flags, d_coef,
                      coef_frame_stride, d_qt, d_status, d_workspace, workspace_bytes, stream);
 }
 
@@ -490,7 +410,7 @@ size_t jpgx_jfif_decode_gpu_any_workspace_size(int width, int height, int sample
     JdArgs a;
     JdLayout l;
     if (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL) return 0;
-    if (jd_geometry(true, width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
+    if (jd_geometry(kAny, width, height, sample_ratio, nframes, file_cap, a, l)) return 0;
     return l.total;
 }
 
@@ -499,7 +419,24 @@ int jpgx_jfif_decode_gpu_any(const uint8_t *d_files, size_t file_stride, const u
                              size_t coef_frame_stride, uint16_t *d_qt, int32_t *d_status, void *d_workspace,
                              size_t workspace_bytes, void *stream)
 {
-    return jd_decode(true, d_files, file_stride, d_len, nframes, width, height, sample_ratio, decode_flags, d_coef,
+    return jd_decode(kAny, d_files, file_stride, d_len, nframes, width, height, sample_ratio, decode_flags, d_coef,
+                     coef_frame_stride, d_qt, d_status, d_workspace, workspace_bytes, stream);
+}
+
+size_t jpgx_jfif_decode_gpu_gray_workspace_size(int width, int height, size_t nframes, size_t file_cap, unsigned decode_flags)
+{
+    JdArgs a;
+    JdLayout l;
+    if (decode_flags & ~JPGX_JFIF_DECODE_SUBINTERVAL) return 0;
+    if (jd_geometry(kGray, width, height, 0, nframes, file_cap, a, l)) return 0;
+    return l.total;
+}
+
+int jpgx_jfif_decode_gpu_gray(const uint8_t *d_files, size_t file_stride, const uint64_t *d_len, size_t nframes, int width,
+                              int height, unsigned decode_flags, int16_t *d_coef, size_t coef_frame_stride, uint16_t *d_qt,
+                              int32_t *d_status, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return jd_decode(kGray, d_files, file_stride, d_len, nframes, width, height, 0, decode_flags, d_coef,
                      coef_frame_stride, d_qt, d_status, d_workspace, workspace_bytes, stream);
 }
 

@@ -1,7 +1,7 @@
 /*
  * jpgx_jfif_read.cpp -- the host decoder of baseline JFIF files back to the coefficient layout
- * (DESIGN.md 4.8): jpgx_jfif_info_of, jpgx_read_jfif and their _any siblings for files of any width and
- * height, and jpgx_coded_size (include/jpgx_compat.h, include/jpgx.h).  The routines are
+ * (DESIGN.md 4.8): jpgx_jfif_info_of, jpgx_read_jfif, their _any siblings for files of any width and
+ * height and their _gray siblings for one-component files, and jpgx_coded_size (include/jpgx_compat.h, include/jpgx.h).  The routines are
  * those of jx_jfif_dec.h, the ones the device decoder (jpgx_jfif_dec.hip) runs; this file adds the
  * search for the restart markers and the threads.  No HIP: built with g++, as jpgx_plan.cpp.
  */
@@ -24,8 +24,12 @@ struct Job {
     const size_t *marks;                /* [ni - 1] the restart markers' places */
     int16_t *coef;
     uint32_t iv0, iv1;                  /* this thread's intervals */
+    int gray;                           /* the one-component frame */
     int rc;
 };
+
+/* the header walk's modes (jx_jfif_dec.h) */
+enum { kPlain, kAny, kGray };
 
 void *run(void *arg)
 {
@@ -37,7 +41,9 @@ void *run(void *arg)
         const size_t end = iv + 1 < fr->ni ? j->marks[iv] : j->len - 2;
         const uint32_t mcu0 = iv * fr->mpi;
         const uint32_t count = fr->nmcu - mcu0 < fr->mpi ? fr->nmcu - mcu0 : fr->mpi;
-        if (jxd_decode_interval(j->file, j->len, begin, end, fr, j->tabs, mcu0, count, j->coef)) j->rc = JPGX_EJFIF_SCAN;
+        const int rc = j->gray ? jxd_decode_interval_gray(j->file, j->len, begin, end, fr, j->tabs, mcu0, count, j->coef)
+                               : jxd_decode_interval(j->file, j->len, begin, end, fr, j->tabs, mcu0, count, j->coef);
+        if (rc) j->rc = JPGX_EJFIF_SCAN;
     }
     return NULL;
 }
@@ -53,10 +59,17 @@ void fill_info(const jxd_frame &fr, jpgx_jfif_info *info)
     info->nb_c = fr.nbc;
 }
 
-/* the header walk in one of its two modes (jx_jfif_dec.h): any = the _any entry points' */
-int parse(bool any, const uint8_t *file, size_t len, jxd_frame *fr, jxd_tab *tabs)
+/* the header walk in one of its modes */
+int parse(int mode, const uint8_t *file, size_t len, jxd_frame *fr, jxd_tab *tabs)
 {
-    return any ? jxd_parse_header<1>(file, len, fr, tabs) : jxd_parse_header<0>(file, len, fr, tabs);
+    return mode == kGray ? jxd_parse_header<1, 1>(file, len, fr, tabs)
+           : mode == kAny ? jxd_parse_header<1>(file, len, fr, tabs) : jxd_parse_header<0>(file, len, fr, tabs);
+}
+
+/* the tables the caller gets: Y's and the chroma's, or the one-component frame's one */
+void copy_qt(int mode, const jxd_frame &fr, uint16_t *qt)
+{
+    if (qt) memcpy(qt, fr.qt, mode == kGray ? sizeof fr.qt[0] : sizeof fr.qt);
 }
 
 /* the restart markers: FF D0 .. D7 cannot occur inside entropy-coded data.  Their count must be the
@@ -74,21 +87,21 @@ int find_marks(const uint8_t *file, size_t len, const jxd_frame *fr, size_t *mar
     return found != fr->ni - 1 ? JPGX_EJFIF_SCAN : 0;
 }
 
-int info_of(bool any, const uint8_t *file, size_t len, jpgx_jfif_info *info)
+int info_of(int mode, const uint8_t *file, size_t len, jpgx_jfif_info *info)
 {
     if (!file || !info) return JPGX_EARG;
     jxd_frame fr;
     jxd_tab *tabs = (jxd_tab *)malloc(4 * sizeof(jxd_tab));
     if (!tabs) return JPGX_ENOMEM;
     memset(&fr, 0, sizeof fr);
-    const int rc = parse(any, file, len, &fr, tabs);
+    const int rc = parse(mode, file, len, &fr, tabs);
     free(tabs);
     if (rc) return rc;
     fill_info(fr, info);
     return JPGX_OK;
 }
 
-int read_jfif(bool any, const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
+int read_jfif(int mode, const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t *qt,
               jpgx_jfif_info *info)
 {
     if (!file || !coef || nthreads < 0) return JPGX_EARG;
@@ -96,13 +109,13 @@ int read_jfif(bool any, const uint8_t *file, size_t len, int nthreads, int16_t *
     memset(&fr, 0, sizeof fr);
     jxd_tab *tabs = (jxd_tab *)malloc(4 * sizeof(jxd_tab));
     if (!tabs) return JPGX_ENOMEM;
-    int rc = parse(any, file, len, &fr, tabs);
+    int rc = parse(mode, file, len, &fr, tabs);
     if (rc) {
         free(tabs);
         return rc;
     }
     if (info) fill_info(fr, info);
-    if (qt) memcpy(qt, fr.qt, sizeof fr.qt);
+    copy_qt(mode, fr, qt);
     if (coef_cap < (size_t)fr.nblk * 64) {
         free(tabs);
         return JPGX_EARG;
@@ -129,6 +142,7 @@ int read_jfif(bool any, const uint8_t *file, size_t len, int nthreads, int16_t *
             j.tabs = tabs;
             j.marks = marks;
             j.coef = coef;
+            j.gray = mode == kGray;
             j.iv0 = (uint32_t)((uint64_t)fr.ni * t / nt);
             j.iv1 = (uint32_t)((uint64_t)fr.ni * (t + 1) / nt);
             j.rc = 0;
@@ -150,20 +164,28 @@ int read_jfif(bool any, const uint8_t *file, size_t len, int nthreads, int16_t *
 
 extern "C" {
 
-int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(false, file, len, info); }
+int jpgx_jfif_info_of(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(kPlain, file, len, info); }
 
-int jpgx_jfif_info_of_any(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(true, file, len, info); }
+int jpgx_jfif_info_of_any(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(kAny, file, len, info); }
+
+int jpgx_jfif_info_of_gray(const uint8_t *file, size_t len, jpgx_jfif_info *info) { return info_of(kGray, file, len, info); }
 
 int jpgx_read_jfif(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
                    jpgx_jfif_info *info)
 {
-    return read_jfif(false, file, len, nthreads, coef, coef_cap, qt, info);
+    return read_jfif(kPlain, file, len, nthreads, coef, coef_cap, (uint16_t *)qt, info);
 }
 
 int jpgx_read_jfif_any(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[2][64],
                        jpgx_jfif_info *info)
 {
-    return read_jfif(true, file, len, nthreads, coef, coef_cap, qt, info);
+    return read_jfif(kAny, file, len, nthreads, coef, coef_cap, (uint16_t *)qt, info);
+}
+
+int jpgx_read_jfif_gray(const uint8_t *file, size_t len, int nthreads, int16_t *coef, size_t coef_cap, uint16_t qt[64],
+                        jpgx_jfif_info *info)
+{
+    return read_jfif(kGray, file, len, nthreads, coef, coef_cap, qt, info);
 }
 
 int jpgx_coded_size(int width, int height, int sample_ratio, int *coded_width, int *coded_height)
@@ -182,7 +204,8 @@ int jpgx_coded_size(int width, int height, int sample_ratio, int *coded_width, i
 namespace {
 
 /* the last pass's writer with the twin's counters */
-struct StatStore : jxs_store {
+template <int GRAY>
+struct StatStore : jxs_store_t<GRAY> {
     jpgx_jfif_sub_stats *stats;
     uint32_t sub_end, tile_bytes;
     void unit(uint32_t, uint32_t last)
@@ -198,7 +221,8 @@ struct Lane {
     uint32_t nblk;
 };
 
-/* one restart interval, as k_jd_sub's workgroup decodes it; lanes: [T] */
+/* one restart interval, as k_jd_sub's workgroup decodes it; lanes: [T].  GRAY: the one-component frame */
+template <int GRAY>
 int sub_interval(const uint8_t *file, size_t len, size_t begin, size_t end, const jxd_frame *fr, const jxd_tab *tabs,
                  uint32_t mcu0, uint32_t count, int16_t *coef, uint32_t S, uint32_t T, Lane *lanes,
                  jpgx_jfif_sub_stats *stats)
@@ -206,10 +230,11 @@ int sub_interval(const uint8_t *file, size_t len, size_t begin, size_t end, cons
     const int bad = JPGX_EJFIF_SCAN;
     if (begin > end || end > len || mcu0 > fr->nmcu || count > fr->nmcu - mcu0) return bad;
     jxs_tabs t;
-    jxs_tabs_of(fr, tabs, &t);
+    if (GRAY) jxs_tabs_of_gray(fr, tabs, &t);
+    else jxs_tabs_of(fr, tabs, &t);
     const uint32_t nblocks = count * t.bpm;
     for (uint32_t o = 0; o < nblocks; o++) {
-        const uint32_t blk = jxs_block_of(fr, mcu0, nblocks, o);
+        const uint32_t blk = jxs_block_of_t<GRAY>(fr, mcu0, nblocks, o);
         if (blk == JXS_INVALID) return bad;
         memset(coef + (size_t)blk * 64, 0, 64 * sizeof(int16_t));
     }
@@ -263,7 +288,7 @@ int sub_interval(const uint8_t *file, size_t len, size_t begin, size_t end, cons
             Lane &l = lanes[i];
             if (i <= first_bad && l.entry.p != JXS_INVALID && ord < nblocks) {
                 if (stats && i && !jxs_same(l.first, l.exit)) stats->wrong_first_guesses++;
-                StatStore wr;
+                StatStore<GRAY> wr;
                 wr.open(fr, coef, mcu0, nblocks, ord);
                 wr.stats = stats;
                 wr.sub_end = (i + 1) * S < tile.n ? (i + 1) * S : tile.n;
@@ -287,13 +312,13 @@ int sub_interval(const uint8_t *file, size_t len, size_t begin, size_t end, cons
     if (err || !done) return bad;
     /* the DC predictors: per component a running sum over the interval's blocks in decode order,
      * 256 at a time, each chunk's sums checked against int16 before the carry moves on */
-    for (uint32_t comp = 0; comp < 3; comp++) {
+    for (uint32_t comp = 0; comp < (GRAY ? 1u : 3u); comp++) {
         const uint32_t per = comp ? 1u : t.lum, nbk = count * per;
         int32_t pred = 0;
         for (uint32_t i0 = 0; i0 < nbk; i0 += 256) {
             for (uint32_t i = i0; i < nbk && i < i0 + 256; i++) {
                 const uint32_t m = i / per, j = comp ? t.lum + comp - 1u : i - m * per;
-                const uint32_t blk = jxs_block_of(fr, mcu0, nblocks, m * t.bpm + j);
+                const uint32_t blk = jxs_block_of_t<GRAY>(fr, mcu0, nblocks, m * t.bpm + j);
                 if (blk == JXS_INVALID) return bad;
                 pred += coef[(size_t)blk * 64];
                 if (pred < -32768 || pred > 32767) err = 1;
@@ -305,8 +330,8 @@ int sub_interval(const uint8_t *file, size_t len, size_t begin, size_t end, cons
     return 0;
 }
 
-int read_sub(bool any, const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
-             size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
+int read_sub(int mode, const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
+             size_t coef_cap, uint16_t *qt, jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
 {
     if (!file || !coef) return JPGX_EARG;
     if (!sub_bytes && !tile_subs) sub_bytes = JXS_SUB, tile_subs = JXS_TILE;
@@ -316,13 +341,13 @@ int read_sub(bool any, const uint8_t *file, size_t len, uint32_t sub_bytes, uint
     memset(&fr, 0, sizeof fr);
     jxd_tab *tabs = (jxd_tab *)malloc(4 * sizeof(jxd_tab));
     if (!tabs) return JPGX_ENOMEM;
-    int rc = parse(any, file, len, &fr, tabs);
+    int rc = parse(mode, file, len, &fr, tabs);
     if (rc) {
         free(tabs);
         return rc;
     }
     if (info) fill_info(fr, info);
-    if (qt) memcpy(qt, fr.qt, sizeof fr.qt);
+    copy_qt(mode, fr, qt);
     if (coef_cap < (size_t)fr.nblk * 64) {
         free(tabs);
         return JPGX_EARG;
@@ -341,7 +366,9 @@ int read_sub(bool any, const uint8_t *file, size_t len, uint32_t sub_bytes, uint
         const size_t end = iv + 1 < fr.ni ? marks[iv] : len - 2;
         const uint32_t mcu0 = iv * fr.mpi;
         const uint32_t count = fr.nmcu - mcu0 < fr.mpi ? fr.nmcu - mcu0 : fr.mpi;
-        rc = sub_interval(file, len, begin, end, &fr, tabs, mcu0, count, coef, sub_bytes, tile_subs, lanes, stats);
+        rc = mode == kGray
+                 ? sub_interval<1>(file, len, begin, end, &fr, tabs, mcu0, count, coef, sub_bytes, tile_subs, lanes, stats)
+                 : sub_interval<0>(file, len, begin, end, &fr, tabs, mcu0, count, coef, sub_bytes, tile_subs, lanes, stats);
     }
     free(lanes);
     free(marks);
@@ -362,13 +389,19 @@ void jpgx_jfif_decode_sub_shape(uint32_t *sub_bytes, uint32_t *tile_subs)
 int jpgx_read_jfif_sub(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
                        size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
 {
-    return read_sub(false, file, len, sub_bytes, tile_subs, coef, coef_cap, qt, info, stats);
+    return read_sub(kPlain, file, len, sub_bytes, tile_subs, coef, coef_cap, (uint16_t *)qt, info, stats);
 }
 
 int jpgx_read_jfif_sub_any(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
                            size_t coef_cap, uint16_t qt[2][64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
 {
-    return read_sub(true, file, len, sub_bytes, tile_subs, coef, coef_cap, qt, info, stats);
+    return read_sub(kAny, file, len, sub_bytes, tile_subs, coef, coef_cap, (uint16_t *)qt, info, stats);
+}
+
+int jpgx_read_jfif_sub_gray(const uint8_t *file, size_t len, uint32_t sub_bytes, uint32_t tile_subs, int16_t *coef,
+                            size_t coef_cap, uint16_t qt[64], jpgx_jfif_info *info, jpgx_jfif_sub_stats *stats)
+{
+    return read_sub(kGray, file, len, sub_bytes, tile_subs, coef, coef_cap, qt, info, stats);
 }
 
 }  /* extern "C" */

@@ -29,6 +29,11 @@
  *
  * jpgx_pixels_gpu_any (a frame of any width and height) launches the instantiations ANY = 1 of
  * k_px444 and k_px_sub, the plain call ANY = 0; k_px_chroma serves both.
+ *
+ * jpgx_pixels_gpu_gray (a one-component frame, Y [nb][64] and one table) launches k_px_gray<CHANNELS>:
+ * px_transform<1> on the same runs and the same LDS image, then 1 byte per pixel through a staging
+ * buffer of its own (px_store_gray1) or 3 equal bytes through px_store<1> with Cb = Cr = 128, for
+ * which jxi_rgb returns the sample three times.  No workspace.
  */
 #include <stdint.h>
 #include <string.h>
@@ -73,6 +78,11 @@ struct PxArgsAny : PxArgs {
     uint32_t w, h, wc, hc;
 };
 
+/* jpgx_pixels_gpu_gray's: g.bw x g.bh blocks, g.nb of them, no chroma; the visible frame */
+struct PxArgsGray : PxArgs {
+    uint32_t w, h;
+};
+
 template <int ANY>
 struct PxA {
     typedef PxArgs type;
@@ -113,6 +123,27 @@ __device__ __forceinline__ void px_lane(const PxArgs &a, uint32_t f, Lane &L)
     uint32_t qor = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) qor |= (uint32_t)L.q[0].h[i] | (uint32_t)L.q[1].h[i];
+    L.fast = __all(qor < 64u);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const uint32_t nat = kZZ[L.j * 8 + i];
+        L.at[i] = px_at(L.b, nat >> 3, nat & 7u);
+    }
+}
+
+/* px_lane for the one-component frame: a.qt has ONE table per frame, a.qstride apart, which takes
+ * both places (only the first is used) */
+__device__ __forceinline__ void px_lane_gray(const PxArgs &a, uint32_t f, Lane &L)
+{
+    L.b = threadIdx.x >> 3;
+    L.j = threadIdx.x & 7u;
+    const uint16_t *qt = a.qt + (size_t)f * a.qstride;
+    uint32_t qor = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        L.q[0].h[i] = L.q[1].h[i] = qt[L.j * 8 + i];
+        qor |= (uint32_t)L.q[0].h[i];
+    }
     L.fast = __all(qor < 64u);
 #pragma unroll
     for (int i = 0; i < 8; i++) {
@@ -217,6 +248,51 @@ __device__ __forceinline__ void px_store(const uint32_t (&y)[8], const uint32_t 
                 *(uint32_t *)tail = v;
                 tail += 4;
                 v = w.y;
+            }
+            if (nbytes & 2u) {
+                *(uint16_t *)tail = (uint16_t)v;
+                tail += 2;
+                v >>= 16;
+            }
+            if (nbytes & 1u) *tail = (uint8_t)v;
+        }
+    }
+    __syncthreads();                    /* the staging buffer is free for the next run's image */
+}
+
+/* One byte per pixel: lane (b, row j) has the 8 samples of its row, 8 bytes of pixel row j of the run.
+ * Stored from there, consecutive lanes would write to 8 different rows; through the staging buffer
+ * lane t writes piece t & 7 of row t >> 3, so 8 consecutive lanes write 64 contiguous bytes, and the
+ * 4 runs of a wave whole 128-byte lines.  kStageRowGray = 80 bytes between the staged rows: the 32
+ * lanes of a ds_write_b64 group (4 blocks x 8 rows) then take every one of the 32 banks exactly twice,
+ * the fewest 64 dwords can; the ds_read_b64 (64 banks) meets 12 of them twice, where 64 bytes between
+ * rows would read without a conflict and write four lanes to a bank.  rows, nbytes: as px_store<1>'s,
+ * nbytes <= 8 n; the row's last partial piece leaves as 4 + 2 + 1 bytes from lane r */
+constexpr uint32_t kStageRowGray = 80;
+
+__device__ __forceinline__ void px_store_gray1(const uint32_t (&y)[8], const Lane &L, uint8_t *stage, uint8_t *out,
+                                               size_t pitch, uint32_t rows, uint32_t nbytes)
+{
+    uint2 w;
+    w.x = y[0] | y[1] << 8 | y[2] << 16 | y[3] << 24;
+    w.y = y[4] | y[5] << 8 | y[6] << 16 | y[7] << 24;
+    *(uint2 *)(stage + L.j * kStageRowGray + L.b * 8u) = w;
+    __syncthreads();
+    {
+        const uint32_t r = threadIdx.x >> 3, c = threadIdx.x & 7u;
+        if (r < rows && c * 8u + 8u <= nbytes)
+            *(uint2 *)(out + (size_t)r * pitch + c * 8u) = *(const uint2 *)(stage + r * kStageRowGray + c * 8u);
+    }
+    if (nbytes & 7u) {                  /* the same for the whole wave: lane r finishes row r */
+        const uint32_t r = threadIdx.x, at = nbytes & ~7u;
+        if (r < rows) {
+            const uint2 v2 = *(const uint2 *)(stage + r * kStageRowGray + at);
+            uint8_t *tail = out + (size_t)r * pitch + at;           /* 8-byte aligned */
+            uint32_t v = v2.x;
+            if (nbytes & 4u) {
+                *(uint32_t *)tail = v;
+                tail += 4;
+                v = v2.y;
             }
             if (nbytes & 2u) {
                 *(uint16_t *)tail = (uint16_t)v;
@@ -380,6 +456,37 @@ __global__ __launch_bounds__(kWave) void k_px_sub(const typename PxA<ANY>::type 
     }
 }
 
+/* The one-component frame: Y alone, CHANNELS (1 or 3) equal bytes per pixel.  The grid has the block
+ * rows that hold a visible pixel row: by * 8 < h, and run * 64 < w for every run of a row */
+template <int CHANNELS>
+__global__ __launch_bounds__(kWave) void k_px_gray(const PxArgsGray a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t img[512];
+    const uint32_t f = blockIdx.z, by = blockIdx.y;
+    if (px_skip(a, f)) return;          /* the same for the whole workgroup */
+    Lane L;
+    px_lane_gray(a, f, L);
+    const uint32_t nruns = (a.g.bw + 7u) / 8u;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride;
+    uint8_t *out = a.rgb + (size_t)f * a.ostride + (size_t)by * 8u * a.pitch;
+    const uint32_t rows = min(8u, a.h - by * 8u);
+    const int tab[1] = {0};
+    for (uint32_t run = blockIdx.x * kRunsPerWave; run < min(nruns, (blockIdx.x + 1u) * kRunsPerWave); run++) {
+        const uint32_t n = min(8u, a.g.bw - run * 8u);
+        const int16_t *const src[1] = {frame + ((size_t)by * a.g.bw + (size_t)run * 8u) * 64};
+        uint32_t s[1][8];
+        px_transform<1>(src, tab, n, L, img, s);
+        if constexpr (CHANNELS == 1) {
+            px_store_gray1(s[0], L, (uint8_t *)img, out + (size_t)run * 64u, (size_t)a.pitch, rows,
+                           min(8u * n, a.w - run * 64u));
+        } else {
+            const uint32_t c128[8] = {128u, 128u, 128u, 128u, 128u, 128u, 128u, 128u};
+            px_store<1>(s[0], c128, c128, n, L, (uint8_t *)img, out + (size_t)run * 192u, (size_t)a.pitch, rows,
+                        min(24u * n, 3u * a.w - run * 192u));
+        }
+    }
+}
+
 /* the chroma sample planes (4:2:x): the workspace's one part */
 size_t px_workspace(const jx_frame &g, size_t nframes)
 {
@@ -451,6 +558,41 @@ int px_run(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int 
     return jx_hip_rc(hipGetLastError());
 }
 
+/* jpgx_pixels_gpu_gray: jpgx_pixels_gpu_any's checks in their order, with one table per frame, the
+ * channel count and no workspace */
+int px_run_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status, uint8_t *d_out, size_t out_pitch,
+                size_t out_frame_stride, int channels, void *stream)
+{
+    PxArgsGray a;
+    memset(&a, 0, sizeof a);
+    if (!d_coef || !d_qt || !d_out || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_out & 7) || !jx_frames_ok(nframes) || (channels != 1 && channels != 3))
+        return JPGX_EARG;
+    jx_frame_gray g;
+    const int rc = jx_frame_rc_pixels(jx_frame_make_gray(width, height, &g));
+    if (rc) return rc;
+    a.g = PxGeom{g.bw, g.bh, 0u, 0u, 1u, 1u, g.nb, 0u};
+    a.w = g.w, a.h = g.h;
+    if (!jx_coef_batch_ok(coef_frame_stride, g.nb)) return JPGX_EARG;
+    if (qt_frame_stride != 0 && qt_frame_stride < 64) return JPGX_EARG;
+    if (out_pitch < (size_t)width * (size_t)channels || out_pitch % 8) return JPGX_EARG;
+    if (out_frame_stride < out_pitch * (size_t)height || out_frame_stride % 8) return JPGX_EARG;
+    a.coef = d_coef;
+    a.cstride = coef_frame_stride;
+    a.qt = d_qt;
+    a.qstride = qt_frame_stride;
+    a.status = d_status;
+    a.rgb = d_out;
+    a.pitch = out_pitch;
+    a.ostride = out_frame_stride;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(px_grid_x(g.bw), g.bh, (unsigned)nframes);
+    if (channels == 1) hipLaunchKernelGGL(k_px_gray<1>, grid, dim3(kWave), 0, s, a);
+    else hipLaunchKernelGGL(k_px_gray<3>, grid, dim3(kWave), 0, s, a);
+    return jx_hip_rc(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
@@ -485,6 +627,14 @@ int jpgx_pixels_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t 
 {
     return px_run<1>(d_coef, coef_frame_stride, nframes, width, height, sample_ratio, d_qt, qt_frame_stride, d_status,
                      d_rgb, out_pitch, out_frame_stride, d_workspace, workspace_bytes, stream);
+}
+
+int jpgx_pixels_gpu_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                         const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status, uint8_t *d_out,
+                         size_t out_pitch, size_t out_frame_stride, int channels, void *stream)
+{
+    return px_run_gray(d_coef, coef_frame_stride, nframes, width, height, d_qt, qt_frame_stride, d_status, d_out,
+                       out_pitch, out_frame_stride, channels, stream);
 }
 
 }  /* extern "C" */

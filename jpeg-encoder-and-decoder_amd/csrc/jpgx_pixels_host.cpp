@@ -8,6 +8,9 @@
  * samples in three planes; then, pixel row by pixel row, the chroma upsampled (4:2:2 / 4:2:0)
  * and the colour converted.  A thread writes only its own rows, so the result does not depend on
  * the thread count.
+ *
+ * jpgx_pixels_host_gray (a one-component frame): one phase over block rows; a block's samples go
+ * straight to the output, once per channel.
  */
 #include <pthread.h>
 #include <stdlib.h>
@@ -175,6 +178,74 @@ int pixels_host(bool any, const int16_t *coef, int width, int height, int sample
     return JPGX_OK;
 }
 
+/* ---- the one-component frame: Y [nb][64] and one table to 1 or 3 equal channels ---------------- */
+struct GrayCtx {
+    const int16_t *coef;
+    const uint16_t *qt;
+    jx_frame_gray g;
+    uint8_t *out;
+    size_t pitch;
+    uint32_t channels;
+};
+
+struct GrayJob {
+    const GrayCtx *c;
+    uint32_t r0, r1;                /* block rows */
+};
+
+void *run_gray(void *arg)
+{
+    const GrayJob *j = (const GrayJob *)arg;
+    const GrayCtx &c = *j->c;
+    const uint32_t ch = c.channels;
+    for (uint32_t by = j->r0; by < j->r1; by++)
+        for (uint32_t bx = 0; bx < c.g.bw; bx++) {
+            uint8_t s[64];
+            block_samples(c.coef + ((size_t)by * c.g.bw + bx) * 64, c.qt, s, 8);
+            for (uint32_t r = 0; r < 8 && by * 8 + r < c.g.h; r++) {
+                uint8_t *row = c.out + (size_t)(by * 8 + r) * c.pitch;
+                for (uint32_t x = bx * 8; x < bx * 8 + 8 && x < c.g.w; x++)
+                    for (uint32_t k = 0; k < ch; k++) row[(size_t)ch * x + k] = s[r * 8 + (x & 7u)];
+            }
+        }
+    return NULL;
+}
+
+int pixels_host_gray(const int16_t *coef, int width, int height, const uint16_t *qt, uint8_t *out, size_t pitch,
+                     int channels, int nthreads)
+{
+    if (!coef || !qt || !out || nthreads < 0 || (channels != 1 && channels != 3)) return JPGX_EARG;
+    GrayCtx c;
+    memset(&c, 0, sizeof c);
+    const int rc = jx_frame_rc_pixels(jx_frame_make_gray(width, height, &c.g));
+    if (rc) return rc;
+    if (pitch < (size_t)width * (size_t)channels) return JPGX_EARG;
+    c.coef = coef;
+    c.qt = qt;
+    c.out = out;
+    c.pitch = pitch;
+    c.channels = (uint32_t)channels;
+    long ncpu = nthreads ? nthreads : sysconf(_SC_NPROCESSORS_ONLN);
+    if (ncpu < 1) ncpu = 1;
+    if (ncpu > 64) ncpu = 64;
+    const uint32_t nt = (uint32_t)ncpu < c.g.bh ? (uint32_t)ncpu : c.g.bh;
+    GrayJob jobs[64];
+    pthread_t th[64];
+    bool started[64];
+    for (uint32_t t = 0; t < nt; t++) {
+        GrayJob &j = jobs[t];
+        j.c = &c;
+        j.r0 = (uint32_t)((uint64_t)c.g.bh * t / nt);
+        j.r1 = (uint32_t)((uint64_t)c.g.bh * (t + 1) / nt);
+        /* the last run on this thread; a thread that does not start is run here as well */
+        started[t] = t + 1 < nt && pthread_create(&th[t], NULL, run_gray, &j) == 0;
+        if (!started[t]) run_gray(&j);
+    }
+    for (uint32_t t = 0; t < nt; t++)
+        if (started[t]) pthread_join(th[t], NULL);
+    return JPGX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -189,6 +260,12 @@ int jpgx_pixels_host_any(const int16_t *coef, int width, int height, int sample_
                          uint8_t *rgb, size_t pitch, int nthreads)
 {
     return pixels_host(true, coef, width, height, sample_ratio, qt, rgb, pitch, nthreads);
+}
+
+int jpgx_pixels_host_gray(const int16_t *coef, int width, int height, const uint16_t qt[64], uint8_t *out, size_t pitch,
+                          int channels, int nthreads)
+{
+    return pixels_host_gray(coef, width, height, qt, out, pitch, channels, nthreads);
 }
 
 }  /* extern "C" */

@@ -105,6 +105,26 @@ JXF_FN int jx_frame_make_any(int width, int height, int sample_ratio, jx_frame_a
     return 0;
 }
 
+/* A one-component (grayscale) file (the decode side's _gray entry points): its scan is
+ * not interleaved, so whatever sampling factors SOF states, the MCU is one block and the frame codes
+ * bw x bh = ceil(w / 8) x ceil(h / 8) blocks in raster order: coefficients Y [nb][64], no chroma. */
+typedef struct jx_frame_gray {
+    uint32_t w, h;          /* the visible frame, 1 .. 65535 each                                */
+    uint32_t bw, bh, nb;    /* blocks per block row, block rows, blocks (= MCUs)                 */
+} jx_frame_gray;
+
+/* JXF_RANGE is all it refuses */
+JXF_FN int jx_frame_make_gray(int width, int height, jx_frame_gray *g)
+{
+    if (width <= 0 || height <= 0 || width > 65535 || height > 65535) return JXF_RANGE;
+    g->w = (uint32_t)width;
+    g->h = (uint32_t)height;
+    g->bw = (g->w + 7u) / 8u;
+    g->bh = (g->h + 7u) / 8u;
+    g->nb = g->bw * g->bh;
+    return 0;
+}
+
 /* The codes the entry points refuse with are part of the ABI and differ; each is one mapping of
  * the reason:            SAMPLE         RANGE           MULT8           MCU
  *   the JFIF coder       EARG           EARG            EARG            EGEOMETRY

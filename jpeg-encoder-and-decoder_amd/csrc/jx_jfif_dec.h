@@ -90,8 +90,13 @@ JXD_FN int jxd_build_table(const uint8_t *bits, const uint8_t *vals, jxd_tab *t)
  * MCU, DQT with 8- or 16-bit entries, DHT (classes 0 / 1, ids 0 / 1), DRI; skips APPn and COM.
  * ANY = 1 (the _any entry points): any width and height 1 .. 65535; fr->width and fr->height are the
  * SOF's, the counts bpr .. nblk those of the coded frame, the size rounded up to the MCU.
+ * GRAY = 1 (the _gray entry points, with ANY = 1): instead ONE component in a scan of its own, any
+ * component id, Tq <= 3, sampling factors 1 .. 4 each, which are ignored: such a scan is not
+ * interleaved, its MCU is one block (T.81 A.2.2) and the frame has ceil(w / 8) x ceil(h / 8) of them
+ * in raster order.  hs = vs = 1, nbc = 0, DRI counts blocks, the one table is qt[0]; only the DQT and
+ * the two DHT tables the component selects need to be there.
  * Returns 0 or JPGX_EJFIF_HEADER. */
-template <int ANY = 0>
+template <int ANY = 0, int GRAY = 0>
 JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_tab *tabs /*[4]*/)
 {
     const int bad = JPGX_EJFIF_HEADER;
@@ -130,6 +135,19 @@ JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_
                 have_tab |= 1u << (tc + 2 * th);
                 j += 17 + total;
             }
+        } else if (GRAY && (m == 0xc0 || m == 0xc1)) {
+            if (have_sof || n != 6 + 3 || seg[0] != 8 || seg[5] != 1) return bad;
+            fr->sof = m;
+            fr->height = jxd_u16(seg, 1);
+            fr->width = jxd_u16(seg, 3);
+            const uint32_t s = seg[7];
+            if ((s >> 4) < 1 || (s >> 4) > 4 || (s & 15u) < 1 || (s & 15u) > 4 || seg[8] > 3) return bad;
+            /* the other components' places name the one component and its table */
+            fr->cid[0] = fr->cid[1] = fr->cid[2] = seg[6];
+            fr->tq[0] = fr->tq[1] = fr->tq[2] = seg[8];
+            fr->hs = fr->vs = 1;
+            if (!fr->width || !fr->height) return bad;
+            have_sof = 1;
         } else if (m == 0xc0 || m == 0xc1) {
             if (have_sof || n != 6 + 9 || seg[0] != 8 || seg[5] != 3) return bad;
             fr->sof = m;
@@ -151,6 +169,21 @@ JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_
         } else if (m == 0xdd) {
             if (n != 2) return bad;
             fr->ri = jxd_u16(seg, 0);
+        } else if (GRAY && m == 0xda) {
+            if (!have_sof || n != 6 || seg[0] != 1) return bad;
+            const uint32_t t = seg[2];
+            if (seg[1] != fr->cid[0] || (t >> 4) > 1 || (t & 15u) > 1) return bad;
+            fr->tdc[0] = fr->tdc[1] = fr->tdc[2] = 0 + 2 * (t >> 4);
+            fr->tac[0] = fr->tac[1] = fr->tac[2] = 1 + 2 * (t & 15u);
+            if (!(have_tab >> fr->tdc[0] & 1u) || !(have_tab >> fr->tac[0] & 1u)) return bad;
+            if (seg[3] != 0 || seg[4] != 63 || seg[5] != 0) return bad;       /* Ss, Se, Ah / Al */
+            if (!(have_q >> fr->tq[0] & 1u)) return bad;
+            const size_t at = (size_t)fr->q_at[fr->tq[0]];
+            const uint32_t wide = fr->q_pq[fr->tq[0]];
+            for (int k = 0; k < 64; k++)   /* both places: the table is one */
+                fr->qt[0][k] = fr->qt[1][k] = (uint16_t)(wide ? jxd_u16(file, at + 2 * (size_t)k) : file[at + k]);
+            fr->scan_off = i + 2 + ln;
+            break;
         } else if (m == 0xda) {
             if (!have_sof || n != 10 || seg[0] != 3) return bad;
             for (int c = 0; c < 3; c++) {
@@ -187,7 +220,7 @@ JXD_FN int jxd_parse_header(const uint8_t *file, size_t len, jxd_frame *fr, jxd_
         fr->nb = fr->bpr * (fr->height / 8);
     }
     fr->nmcu = fr->cpr * fr->mrows;
-    fr->nbc = fr->nmcu;
+    fr->nbc = GRAY ? 0u : fr->nmcu;
     fr->nblk = fr->nb + 2 * fr->nbc;
     fr->mpi = fr->ri && fr->ri < fr->nmcu ? fr->ri : fr->nmcu;
     fr->ni = (fr->nmcu + fr->mpi - 1) / fr->mpi;
@@ -346,6 +379,31 @@ JXD_FN int jxd_decode_interval(const uint8_t *file, size_t len, size_t begin, si
         if (jxd_block(&b, bdc, bac, &pb, coef + ((size_t)nb + cb) * 64)) return bad;
         if (jxd_block(&b, rdc, rac, &pr, coef + ((size_t)nb + nbc + cb) * 64)) return bad;
         if (++mx == cpr) mx = 0, my++;
+    }
+    if (b.bad || b.pos != b.end || b.n >= 8) return bad;
+    return 0;
+}
+
+/* jxd_decode_interval for the one-component frame (jxd_parse_header's GRAY): an MCU is a block, MCU m
+ * is block m of coef = Y [nb][64], one predictor.  The same contract and return codes. */
+JXD_FN int jxd_decode_interval_gray(const uint8_t *file, size_t len, size_t begin, size_t end, const jxd_frame *fr,
+                                    const jxd_tab *tabs /*[4]*/, uint32_t mcu0, uint32_t count, int16_t *coef)
+{
+    const int bad = JPGX_EJFIF_SCAN;
+    if (begin > end || end > len || mcu0 > fr->nmcu || count > fr->nmcu - mcu0) return bad;
+    jxd_bits b;
+    b.d = file;
+    b.pos = begin;
+    b.end = end;
+    b.acc = 0;
+    b.n = 0;
+    b.bad = 0;
+    const jxd_tab *dc = tabs + fr->tdc[0], *ac = tabs + fr->tac[0];
+    const uint32_t nb = fr->nb;
+    int pred = 0;
+    for (uint32_t m = 0; m < count; m++) {
+        const size_t blk = (size_t)mcu0 + m;
+        if (blk >= nb || jxd_block(&b, dc, ac, &pred, coef + blk * 64)) return bad;
     }
     if (b.bad || b.pos != b.end || b.n >= 8) return bad;
     return 0;

@@ -68,6 +68,14 @@ JXD_FN void jxs_tabs_of(const jxd_frame *fr, const jxd_tab *tabs, jxs_tabs *t)
     t->bpm = t->lum + 2u;
 }
 
+/* the one-component frame (jxd_parse_header's GRAY): the MCU is one block, and the unit walk below
+ * stays at c = 0.  The header walk has put the component's tables into all three places */
+JXD_FN void jxs_tabs_of_gray(const jxd_frame *fr, const jxd_tab *tabs, jxs_tabs *t)
+{
+    jxs_tabs_of(fr, tabs, t);
+    t->lum = t->bpm = 1u;
+}
+
 /* the reader of a plain buffer: byte r of the tile that begins at d */
 struct jxs_flat {
     const uint8_t *d;
@@ -143,9 +151,24 @@ JXD_FN uint32_t jxs_block_of(const jxd_frame *fr, uint32_t mcu0, uint32_t nblock
     return cb < fr->nbc ? fr->nb + (j - lum) * fr->nbc + cb : JXS_INVALID;
 }
 
+/* the same of the one-component frame: block `ord` of the interval is block mcu0 + ord of the frame */
+JXD_FN uint32_t jxs_block_of_gray(const jxd_frame *fr, uint32_t mcu0, uint32_t nblocks, uint32_t ord)
+{
+    if (ord >= nblocks || mcu0 >= fr->nmcu || ord >= fr->nmcu - mcu0) return JXS_INVALID;
+    const uint32_t blk = mcu0 + ord;
+    return blk < fr->nb ? blk : JXS_INVALID;
+}
+
+template <int GRAY>
+JXD_FN uint32_t jxs_block_of_t(const jxd_frame *fr, uint32_t mcu0, uint32_t nblocks, uint32_t ord)
+{
+    return GRAY ? jxs_block_of_gray(fr, mcu0, nblocks, ord) : jxs_block_of(fr, mcu0, nblocks, ord);
+}
+
 /* ... or the last pass: the nonzero coefficients and the DC difference into the frame, from block
- * `ord` of the interval on, up to its last block */
-struct jxs_store {
+ * `ord` of the interval on, up to its last block.  GRAY: of the one-component frame */
+template <int GRAY>
+struct jxs_store_t {
     const jxd_frame *fr;
     int16_t *coef;          /* the frame's */
     uint32_t mcu0, nblocks, ord;
@@ -157,7 +180,7 @@ struct jxs_store {
     }
     JXD_FN_M void seek()
     {
-        const uint32_t blk = jxs_block_of(fr, mcu0, nblocks, ord);
+        const uint32_t blk = jxs_block_of_t<GRAY>(fr, mcu0, nblocks, ord);
         cur = blk == JXS_INVALID ? NULL : coef + (size_t)blk * 64;
     }
     JXD_FN_M void put(uint32_t k, int v)
@@ -172,6 +195,7 @@ struct jxs_store {
     }
     JXD_FN_M void unit(uint32_t, uint32_t) {}
 };
+typedef jxs_store_t<0> jxs_store;
 
 JXD_FN int jxs_extend(uint32_t v, uint32_t s) { return v < (1u << (s - 1u)) ? (int)v - (1 << s) + 1 : (int)v; }
 

@@ -14,6 +14,8 @@ decode_jpeg_coefficients -- baseline JFIF files back to the coefficients (DESIGN
 pixels_gpu, decode_jpeg -- the coefficients to RGB, libjpeg's default decoder's pixels (4.9).
 These four take any_size=True for files whose width and height are no multiple of the MCU (the
 library's _any entry points); coded_size is the size such a file's coefficients are of.
+One-component (grayscale) files go through jfif_decode_gpu_gray and pixels_gpu_gray (the library's
+_gray entry points), or through decode_jpeg / decode_jpeg_coefficients with gray=True.
 """
 from __future__ import annotations
 
@@ -58,6 +60,7 @@ EXPORTS = [
     "jpgx_pixels_gpu_workspace_size", "jpgx_pixels_gpu", "jpgx_jfif_qt",
     "jpgx_coded_size", "jpgx_jfif_decode_gpu_any_workspace_size", "jpgx_jfif_decode_gpu_any",
     "jpgx_pixels_gpu_any_workspace_size", "jpgx_pixels_gpu_any",
+    "jpgx_jfif_decode_gpu_gray_workspace_size", "jpgx_jfif_decode_gpu_gray", "jpgx_pixels_gpu_gray",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -69,6 +72,7 @@ COMPAT_EXPORTS = [
     "jpgx_encode_rgb_to_jpeg", "jpgx_write_jfif_ex", "jpgx_write_jfif_opt",
     "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host",
     "jpgx_jfif_info_of_any", "jpgx_read_jfif_any", "jpgx_read_jfif_sub_any", "jpgx_pixels_host_any",
+    "jpgx_jfif_info_of_gray", "jpgx_read_jfif_gray", "jpgx_read_jfif_sub_gray", "jpgx_pixels_host_gray",
 ]
 
 
@@ -157,6 +161,10 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_pixels_gpu_any_workspace_size.argtypes = L.jpgx_pixels_gpu_workspace_size.argtypes
     L.jpgx_pixels_gpu_any_workspace_size.restype = sz
     L.jpgx_pixels_gpu_any.argtypes = L.jpgx_pixels_gpu.argtypes
+    L.jpgx_jfif_decode_gpu_gray_workspace_size.argtypes = [i, i, sz, sz, ctypes.c_uint]
+    L.jpgx_jfif_decode_gpu_gray_workspace_size.restype = sz
+    L.jpgx_jfif_decode_gpu_gray.argtypes = [vp, sz, vp, sz, i, i, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp]
+    L.jpgx_pixels_gpu_gray.argtypes = [vp, sz, sz, i, i, vp, sz, vp, vp, sz, sz, i, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -501,20 +509,83 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
     return coef, qt, status
 
 
-def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False, any_size: bool = False):
+def _gray_blocks(fn: str, width: int, height: int) -> int:
+    """the blocks a one-component file of width x height codes: ceil(W / 8) * ceil(H / 8)"""
+    if not (0 < width < 65536 and 0 < height < 65536):
+        raise ValueError(f"{fn}: bad geometry")
+    return ((width + 7) // 8) * ((height + 7) // 8)
+
+
+def jfif_decode_gpu_gray(d_files, lens, width: int, height: int, stream=None, subinterval: bool = False):
+    """jfif_decode_gpu for one-component (grayscale) baseline files (jpgx_jfif_decode_gpu_gray): d_files
+    uint8 [nframes][cap], lens int64 [nframes], every file of the stated width and height, any
+    1 .. 65535 -> (coef int16 [nframes][nb][64] with nb = ceil(W / 8) * ceil(H / 8), qt uint16
+    [nframes][64], status int32 [nframes]), all on the device; status[f], the coefficients and the table
+    are compat.read_jfif_gray's for the same bytes, and a three-component file has EJFIF_HEADER.
+    Nothing is copied to the host and nothing waits.  subinterval: as jfif_decode_gpu's."""
+    import torch
+    for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"jfif_decode_gpu_gray: {name} must be a device tensor")
+        if t.dtype != dt:
+            raise ValueError(f"jfif_decode_gpu_gray: {name} must be {dt}")
+    if d_files.dim() != 2 or lens.dim() != 1 or lens.shape[0] != d_files.shape[0] or d_files.shape[0] == 0:
+        raise ValueError("jfif_decode_gpu_gray: d_files [nframes][cap] and lens [nframes]")
+    if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
+        raise ValueError("jfif_decode_gpu_gray: each file must be contiguous")
+    nb = _gray_blocks("jfif_decode_gpu_gray", width, height)
+    nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
+    fstride = int(d_files.stride(0)) if nf > 1 else cap
+    if fstride < cap:
+        raise ValueError("jfif_decode_gpu_gray: overlapping files")
+    dev = d_files.device
+    coef = torch.empty((nf, nb, 64), dtype=torch.int16, device=dev)
+    qt = torch.empty((nf, 64), dtype=torch.uint16, device=dev)
+    status = torch.empty(nf, dtype=torch.int32, device=dev)
+    dflags = JFIF_DECODE_SUBINTERVAL if subinterval else 0
+    need = int(lib.jpgx_jfif_decode_gpu_gray_workspace_size(width, height, nf, fstride, dflags))
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    _check(lib.jpgx_jfif_decode_gpu_gray(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, dflags,
+                                         coef.data_ptr(), nb * 64, qt.data_ptr(), status.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu_gray")
+    if stream is not None:
+        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
+    return coef, qt, status
+
+
+def _upload_files(files, dev):
+    """host files -> (d_files uint8 [n][cap], lens int64 [n]) on dev"""
+    import torch
+    cap = max(len(f) for f in files)
+    host = np.zeros((len(files), cap), np.uint8)
+    for k, f in enumerate(files):
+        host[k, :len(f)] = np.frombuffer(f, np.uint8)
+    return torch.from_numpy(host).to(dev), torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
+
+
+def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False, any_size: bool = False,
+                             gray: bool = False):
     """One baseline JFIF file in host memory -> its coefficients on `device`: the header walk on the
     host for the geometry (compat.jfif_info), one host-to-device copy of the bytes, jfif_decode_gpu.
     Returns compat.read_jfif's dict with device tensors: coef int16 ([3][nb][64] for 4:4:4,
     [nb + 2 nbc][64] otherwise), qt uint16 [2][64], width, height, sample_ratio, restart_interval.
     Raises JpgxError on a nonzero status (that reads the status back, a synchronisation).
     subinterval, any_size: as jfif_decode_gpu's (any_size: the coefficients are the coded frame's,
-    width and height the file's)."""
+    width and height the file's).  gray: the file is a one-component one of any size
+    (jfif_decode_gpu_gray): coef [nb][64], qt [64], sample_ratio 0, restart_interval in blocks."""
     import torch
     from . import compat
-    info = compat.jfif_info(data, any_size=any_size)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("decode_jpeg_coefficients: device must be a GPU")
+    if gray:
+        info = compat.jfif_info_gray(data)
+        d_files, lens = _upload_files([bytes(data)], dev)
+        coef, qt, status = jfif_decode_gpu_gray(d_files, lens, info["width"], info["height"], subinterval=subinterval)
+        _check(int(status[0]), "jpgx_jfif_decode_gpu_gray")
+        return dict(coef=coef[0], qt=qt[0], width=info["width"], height=info["height"], sample_ratio=0,
+                    restart_interval=info["restart_interval"])
+    info = compat.jfif_info(data, any_size=any_size)
     host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
     d_files = host.to(dev).reshape(1, -1)
     lens = torch.tensor([len(data)], dtype=torch.int64, device=dev)
@@ -586,7 +657,51 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     return out.view(nf, height, pitch)[:, :, :3 * width].unflatten(2, (width, 3))
 
 
-def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False):
+def pixels_gpu_gray(d_coef, width: int, height: int, d_qt, status=None, channels: int = 1, out=None,
+                    pitch: int | None = None, stream=None):
+    """The pixels of a batch of one-component frames (jpgx_pixels_gpu_gray): d_coef int16
+    [nframes][>= nb][64] as jfif_decode_gpu_gray returns it, d_qt uint16 [nframes][64] (a table per
+    frame) or [64] (one for the batch), status as pixels_gpu's.  Returns uint8 [nframes][H][W]
+    (channels 1) or [nframes][H][W][3] (channels 3, R = G = B) on the device: libjpeg's default
+    decoder's pixels.  pitch (bytes between pixel rows, a multiple of 8, at least channels * W; default:
+    channels * W rounded up to 8) and out as pixels_gpu's.  Nothing is copied to the host and nothing waits."""
+    import torch
+    if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda or d_coef.dtype != torch.int16 or d_coef.dim() < 2:
+        raise ValueError("pixels_gpu_gray: d_coef must be an int16 [nframes][...] device tensor")
+    if not isinstance(d_qt, torch.Tensor) or not d_qt.is_cuda or d_qt.dtype != torch.uint16 or not d_qt.is_contiguous():
+        raise ValueError("pixels_gpu_gray: d_qt must be a contiguous uint16 device tensor")
+    if channels not in (1, 3):
+        raise ValueError("pixels_gpu_gray: channels must be 1 or 3")
+    nf = int(d_coef.shape[0])
+    nb = _gray_blocks("pixels_gpu_gray", width, height)
+    if not d_coef[0].is_contiguous() or d_coef[0].numel() < nb * 64:
+        raise ValueError("pixels_gpu_gray: each frame must be contiguous and hold nb blocks")
+    cstride = int(d_coef.stride(0)) if nf > 1 else int(d_coef[0].numel())
+    if d_qt.numel() == 64:
+        qstride = 0
+    elif d_qt.numel() == 64 * nf:
+        qstride = 64
+    else:
+        raise ValueError("pixels_gpu_gray: d_qt must be [64] or [nframes][64]")
+    if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.int32
+                               or status.numel() != nf or not status.is_contiguous()):
+        raise ValueError("pixels_gpu_gray: status must be a contiguous int32 [nframes] tensor")
+    pitch = (channels * width + 7) // 8 * 8 if pitch is None else int(pitch)
+    if pitch < channels * width or pitch % 8:
+        raise ValueError("pixels_gpu_gray: pitch must be a multiple of 8 and at least channels * width")
+    if out is None:
+        out = torch.empty(nf * height * pitch, dtype=torch.uint8, device=d_coef.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.numel() != nf * height * pitch):
+        raise ValueError("pixels_gpu_gray: out must be a contiguous uint8 buffer of nframes * H * pitch bytes")
+    _check(lib.jpgx_pixels_gpu_gray(d_coef.data_ptr(), cstride, nf, width, height, d_qt.data_ptr(), qstride,
+                                    status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
+                                    height * pitch, channels, _stream_ptr(stream)), "jpgx_pixels_gpu_gray")
+    px = out.view(nf, height, pitch)[:, :, :channels * width]
+    return px if channels == 1 else px.unflatten(2, (width, 3))
+
+
+def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False, gray: bool = False):
     """Baseline JFIF file(s) in host memory -> RGB on `device`: decode_jpeg_coefficients' header step
     on the host for the geometry, one host-to-device copy of the bytes, then jfif_decode_gpu and
     pixels_gpu on one stream; the coefficients never leave the device.  data: bytes -> uint8 [H][W][3];
@@ -594,7 +709,9 @@ def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False)
     Raises JpgxError for a frame whose status is nonzero (that reads the statuses back, a
     synchronisation).  subinterval: as jfif_decode_gpu's; the choice for files without restart
     intervals, which one lane decodes otherwise.  any_size: files of any width and height (a list is
-    still files of one geometry); the default refuses a size that is no multiple of the MCU."""
+    still files of one geometry); the default refuses a size that is no multiple of the MCU.  gray:
+    one-component files of any size (jfif_decode_gpu_gray, pixels_gpu_gray): uint8 [H][W], or
+    [n][H][W] for a list; the default refuses such files."""
     import torch
     from . import compat
     single = isinstance(data, (bytes, bytearray, memoryview))
@@ -604,6 +721,14 @@ def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("decode_jpeg: device must be a GPU")
+    if gray:
+        info = compat.jfif_info_gray(files[0])
+        d_files, lens = _upload_files(files, dev)
+        coef, qt, status = jfif_decode_gpu_gray(d_files, lens, info["width"], info["height"], subinterval=subinterval)
+        px = pixels_gpu_gray(coef, info["width"], info["height"], qt, status=status)
+        for rc in status.cpu().tolist():
+            _check(int(rc), "jpgx_jfif_decode_gpu_gray")
+        return px[0] if single else px
     info = compat.jfif_info(files[0], any_size=any_size)
     W, H, sr = info["width"], info["height"], info["sample_ratio"]
     cap = max(len(f) for f in files)

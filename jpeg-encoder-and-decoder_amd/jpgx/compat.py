@@ -108,6 +108,9 @@ def _setup(L):
     L.jpgx_pixels_host.argtypes = [vp, i, i, i, vp, vp, ctypes.c_size_t, i]
     for name in ("jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host"):
         getattr(L, name + "_any").argtypes = getattr(L, name).argtypes
+    for name in ("jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub"):
+        getattr(L, name + "_gray").argtypes = getattr(L, name).argtypes
+    L.jpgx_pixels_host_gray.argtypes = [vp, i, i, vp, vp, ctypes.c_size_t, i, i]
 
 
 _setup(lib)
@@ -375,6 +378,62 @@ def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt
     _check((lib.jpgx_pixels_host_any if any_size else lib.jpgx_pixels_host)(coef.ctypes.data, width, height, sample_ratio, qt.ctypes.data, buf.ctypes.data,
                                 pitch, nthreads), "jpgx_pixels_host")
     return buf[:, :3 * width].reshape(height, width, 3)
+
+
+def jfif_info_gray(data) -> dict:
+    """jpgx_jfif_info_of_gray: jfif_info for a one-component (grayscale) file of any width and height:
+    sample_ratio 0, nb_y = ceil(W / 8) * ceil(H / 8), nb_c 0, restart_interval in blocks."""
+    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    info = JfifInfo()
+    _check(lib.jpgx_jfif_info_of_gray(buf.ctypes.data, len(data), ctypes.byref(info)), "jpgx_jfif_info_of_gray")
+    return _info_dict(info)
+
+
+def read_jfif_gray(data, nthreads: int = 1) -> dict:
+    """jpgx_read_jfif_gray: a one-component baseline file -> dict(coef int16 [nb][64], qt uint16 [64],
+    width, height, sample_ratio 0, restart_interval).  JpgxError(EJFIF_HEADER / EJFIF_SCAN) when refused."""
+    info = jfif_info_gray(data)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    coef = np.empty((info["nb_y"], 64), np.int16)
+    qt = np.zeros(64, np.uint16)
+    got = JfifInfo()
+    _check(lib.jpgx_read_jfif_gray(buf.ctypes.data, len(buf), nthreads, coef.ctypes.data, coef.size, qt.ctypes.data,
+                                   ctypes.byref(got)), "jpgx_read_jfif_gray")
+    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"], sample_ratio=0,
+                restart_interval=info["restart_interval"])
+
+
+def read_jfif_sub_gray(data, sub_bytes: int = 0, tile_subs: int = 0) -> dict:
+    """jpgx_read_jfif_sub_gray: read_jfif_gray by the routines of the device decoder that works inside a
+    restart interval (read_jfif_sub's shapes and `stats`)."""
+    info = jfif_info_gray(data)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    coef = np.empty((info["nb_y"], 64), np.int16)
+    qt = np.zeros(64, np.uint16)
+    got, stats = JfifInfo(), JfifSubStats()
+    _check(lib.jpgx_read_jfif_sub_gray(buf.ctypes.data, len(buf), sub_bytes, tile_subs, coef.ctypes.data, coef.size,
+                                       qt.ctypes.data, ctypes.byref(got), ctypes.byref(stats)), "jpgx_read_jfif_sub_gray")
+    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"], sample_ratio=0,
+                restart_interval=info["restart_interval"],
+                stats={n: int(getattr(stats, n)) for n, _ in JfifSubStats._fields_})
+
+
+def pixels_host_gray(coef: np.ndarray, width: int, height: int, qt: np.ndarray, channels: int = 1,
+                     nthreads: int = 0, pitch: int | None = None) -> np.ndarray:
+    """jpgx_pixels_host_gray: a one-component frame's coefficients [nb][64] and its uint16 [64] zig-zag
+    table -> uint8 [H][W] (channels 1) or [H][W][3] (channels 3, R = G = B): libjpeg's default decoder's
+    pixels.  pitch: bytes between pixel rows of the buffer the result is a view of."""
+    coef = np.ascontiguousarray(coef, np.int16)
+    qt = np.ascontiguousarray(qt, np.uint16)
+    if qt.size != 64 or (0 < width < 65536 and 0 < height < 65536
+                         and coef.size < ((width + 7) // 8) * ((height + 7) // 8) * 64):
+        raise ValueError("pixels_host_gray: qt [64], and coef must hold ceil(W / 8) * ceil(H / 8) blocks")
+    pitch = channels * width if pitch is None else int(pitch)
+    buf = np.empty((max(height, 1), max(pitch, 1)), np.uint8)
+    _check(lib.jpgx_pixels_host_gray(coef.ctypes.data, width, height, qt.ctypes.data, buf.ctypes.data, pitch,
+                                     channels, nthreads), "jpgx_pixels_host_gray")
+    px = buf[:height, :channels * width]
+    return px if channels == 1 else px.reshape(height, width, 3)
 
 
 def encode_bmp_to_jpeg_ex(src: str, dst: str, quality: int, sample_ratio: int, flags: int,

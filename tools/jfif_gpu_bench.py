@@ -64,8 +64,24 @@ sample mode, the calls taken in turn, several passes, in one process:
 and once, for the photo-like input, "decoder_3839x2159": its frames cropped, written by Pillow with one MCU
 row per restart interval (4:4:4 and 4:2:0) and decoded by jpgx_jfif_decode_gpu_any with both scan kernels
 (decode_us, decode_sub_us; statuses 0, both equal, frame 0 == jpgx_read_jfif_any).
+With --gray the run times the one-component (grayscale) entry points (jpgx_jfif_decode_gpu_gray,
+jpgx_pixels_gpu_gray) on 8 grayscale files of 3840 x 2160 at q 90 and writes
+profiles/jfif_gpu_gray.json.  The inputs are made on the host (noise, and flat 8 x 8 tiles plus +-6 of noise) and
+the files written by Pillow -- or read from --gray-files=DIR, which a run with Pillow fills when it is given and
+empty.  Per input, "with_dri" (one block row per restart interval) and "no_dri":
+  decode_us, decode_sub_us    jpgx_jfif_decode_gpu_gray with flags 0 and JPGX_JFIF_DECODE_SUBINTERVAL per batch
+                  (events, as above; without DRI 1 call per round, 3 rounds: flags 0 is one lane's work per file)
+  coefficients_equal          statuses 0, both ways equal, frame 0 == jpgx_read_jfif_gray
+and per input:
+  px1_us, px3_us  k_px_gray with 1 and 3 channels per batch; px1_fraction_of_8TBps at 3 B per pixel (2 read,
+                  1 written), px3_fraction_of_8TBps at 5
+  px444_us, px444_fraction_of_8TBps   k_px444 (jpgx_pixels_gpu, 4:4:4) at 9 B per pixel in the same session, on
+                  the forward transform's coefficients of the same image as R = G = B
+  host_route_s    the files copied to pinned host memory + jpgx_read_jfif_gray + jpgx_pixels_host_gray (1 channel)
+                  on 16 threads, frame after frame; best of 2
+  pixels_equal    both channel counts == jpgx_pixels_host_gray on two frames, before and after the timed calls
 Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels [--any-size
-[--parent-lib=PATH]]] [OUT.json]"""
+[--parent-lib=PATH]] | --gray [--gray-files=DIR]] [OUT.json]"""
 import json
 import os
 import sys
@@ -617,17 +633,192 @@ def measure_px_any(name, d_rgb, dev):
     return res
 
 
+GRAY_FILES = None                       # --gray-files=DIR
+
+
+def gray_inputs():
+    """[(name, slug, uint8 [F][H][W])], made on the host: the files must be the same wherever they are written"""
+    g = np.random.default_rng(7)
+    noise = g.integers(0, 256, (F, H, W), dtype=np.uint8)
+    tiles = g.integers(0, 256, (F, H // 8, W // 8), dtype=np.int16).repeat(8, 1).repeat(8, 2)
+    flat = np.clip(tiles + g.integers(-6, 7, tiles.shape, dtype=np.int16), 0, 255).astype(np.uint8)
+    return [("noise", "noise", noise), ("flat 8x8 tiles + noise of +-6", "flat", flat)]
+
+
+def gray_files(slug, images, dri):
+    """the F files of an input: from --gray-files=DIR when they are there, else from Pillow (and into DIR)"""
+    names = ["%s_%s_%d.jpg" % (slug, "dri" if dri else "nodri", f) for f in range(F)]
+    if GRAY_FILES and all(os.path.exists(os.path.join(GRAY_FILES, n)) for n in names):
+        return [open(os.path.join(GRAY_FILES, n), "rb").read() for n in names]
+    import io
+
+    from PIL import Image
+    files = []
+    for f in range(F):
+        b = io.BytesIO()
+        Image.fromarray(images[f], "L").save(b, "JPEG", quality=Q, **(dict(restart_marker_rows=1) if dri else {}))
+        files.append(b.getvalue())
+    if GRAY_FILES:
+        os.makedirs(GRAY_FILES, exist_ok=True)
+        for n, data in zip(names, files):
+            with open(os.path.join(GRAY_FILES, n), "wb") as fh:
+                fh.write(data)
+    return files
+
+
+def measure_gray(name, slug, images, dev):
+    nb = (W // 8) * (H // 8)
+    per = nb * 64
+    SUB = jpgx.JFIF_DECODE_SUBINTERVAL
+    stream = torch.cuda.current_stream().cuda_stream
+    res = {"input": name}
+    ok = True
+    coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+    qt = torch.empty((F, 64), dtype=torch.int16, device=dev)
+    status = torch.empty(F, dtype=torch.int32, device=dev)
+    for key, dri in (("with_dri", True), ("no_dri", False)):
+        files = gray_files(slug, images, dri)
+        cap = (max(len(x) for x in files) + 15) // 16 * 16
+        packed = np.zeros((F, cap), np.uint8)
+        for f, x in enumerate(files):
+            packed[f, :len(x)] = np.frombuffer(x, np.uint8)
+        d_files = torch.from_numpy(packed).to(dev)
+        d_lens = torch.tensor([len(x) for x in files], dtype=torch.int64, device=dev)
+        info = C.jfif_info_gray(files[0])
+        assert (info["width"], info["height"], info["restart_interval"]) == (W, H, W // 8 if dri else 0), info
+        ref = C.read_jfif_gray(files[0], HOST_THREADS)["coef"].reshape(-1)
+        part = {"file_bytes": [len(x) for x in files], "intervals": F * (H // 8 if dri else 1)}
+        got = {}
+        for tkey, flags in (("decode_us", 0), ("decode_sub_us", SUB)):
+            need = int(jpgx.lib.jpgx_jfif_decode_gpu_gray_workspace_size(W, H, F, cap, flags))
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+
+            def dec():
+                rc = jpgx.lib.jpgx_jfif_decode_gpu_gray(d_files.data_ptr(), cap, d_lens.data_ptr(), F, W, H, flags,
+                                                        coef.data_ptr(), per, qt.data_ptr(), status.data_ptr(),
+                                                        ws.data_ptr(), need, stream)
+                assert rc == 0, rc
+
+            coef.fill_(0x5A5A)
+            dec()
+            torch.cuda.synchronize()
+            ok = ok and status.cpu().tolist() == [0] * F
+            part[tkey] = timed(dec) if dri else timed(dec, calls=1, rounds=3, settle=0.0)
+            ok = ok and status.cpu().tolist() == [0] * F and bool(np.array_equal(coef[0].cpu().numpy(), ref))
+            got[flags] = coef.clone()
+        ok = ok and bool(torch.equal(got[0], got[SUB]))
+        part["sub_over_plain"] = median(part["decode_sub_us"]) / median(part["decode_us"])
+        part["gpx_per_s_sub"] = F * W * H / part["decode_sub_us"][0] / 1e3
+        res[key] = part
+        del got
+        if not dri:
+            continue
+        # the host route on the files with restart intervals, which is also the pixels' check
+        pinned = torch.empty((F, cap), dtype=torch.uint8).pin_memory()
+        hcoef, hqt = np.empty((F, per), np.int16), np.empty((F, 64), np.uint16)
+        want = np.empty((F, H, W), np.uint8)
+        host_s = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pinned.copy_(d_files)
+            torch.cuda.synchronize()
+            for f in range(F):
+                rc = jpgx.lib.jpgx_read_jfif_gray(pinned.data_ptr() + f * cap, len(files[f]), HOST_THREADS,
+                                                  hcoef[f].ctypes.data, per, hqt[f].ctypes.data, None)
+                assert rc == 0, rc
+                rc = jpgx.lib.jpgx_pixels_host_gray(hcoef[f].ctypes.data, W, H, hqt[f].ctypes.data, want[f].ctypes.data,
+                                                    W, 1, HOST_THREADS)
+                assert rc == 0, rc
+            host_s.append(time.perf_counter() - t0)
+        res["host_route_s"], res["host_threads"] = min(host_s), HOST_THREADS
+        # the pixel kernel on what the decoder left
+        equal = True
+        for ch in (1, 3):
+            out = torch.empty((F, H, W * ch), dtype=torch.uint8, device=dev)
+
+            def pixels():
+                rc = jpgx.lib.jpgx_pixels_gpu_gray(coef.data_ptr(), per, F, W, H, qt.data_ptr(), 64, status.data_ptr(),
+                                                   out.data_ptr(), ch * W, ch * W * H, ch, stream)
+                assert rc == 0, rc
+
+            def check():
+                px = out[:2].cpu().numpy().reshape(2, H, W, ch)
+                return all(np.array_equal(px[f, :, :, c], want[f]) for f in range(2) for c in range(ch))
+
+            out.fill_(FILL)
+            pixels()
+            torch.cuda.synchronize()
+            equal = equal and check()
+            t = timed(pixels)
+            equal = equal and check()
+            bpp = 2 + ch
+            res["px%d_us" % ch] = t
+            res["px%d_bytes_per_px" % ch] = bpp
+            res["px%d_fraction_of_8TBps" % ch] = F * W * H * bpp / (t[0] * 1e-6) / 8e12
+            del out
+        res["speedup"] = min(host_s) / ((median(res["with_dri"]["decode_sub_us"]) + median(res["px1_us"])) * 1e-6)
+        res["pixels_equal"] = bool(equal)
+    # k_px444 in the same session: the same image as R = G = B through the forward transform
+    per3 = 3 * per
+    d_rgb = torch.from_numpy(images).to(dev).unsqueeze(3).expand(F, H, W, 3).contiguous()
+    coef3 = torch.empty((F, per3), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per3)
+    p = jpgx.default_params(W, H, Q, 0)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+    jpgx.blocks_gpu(fr, p, d_rgb, coef3, xws)
+    torch.cuda.synchronize()
+    d_qt2 = torch.from_numpy(jpgx.jfif_qt(Q).view(np.int16)).to(dev)
+    rgb = d_rgb                                              # the input is no longer needed: the output takes its place
+
+    def px444():
+        rc = jpgx.lib.jpgx_pixels_gpu(coef3.data_ptr(), per3, F, W, H, 0, d_qt2.data_ptr(), 0, None, rgb.data_ptr(),
+                                      3 * W, 3 * W * H, None, 0, stream)
+        assert rc == 0, rc
+
+    t = timed(px444)
+    res["px444_us"] = t
+    res["px444_fraction_of_8TBps"] = F * W * H * 9 / (t[0] * 1e-6) / 8e12
+    res["px1_fraction_over_px444"] = res["px1_fraction_of_8TBps"] / res["px444_fraction_of_8TBps"]
+    res["coefficients_equal"] = bool(ok)
+    res["bytes_equal"] = bool(ok and res["pixels_equal"])
+    res["repeat_equal"] = res["bytes_equal"]
+    return res
+
+
+def main_gray(dst):
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = torch.device("cuda:0")
+    res = {"what": "tools/jfif_gpu_bench.py --gray", "width": W, "height": H, "frames": F, "quality": Q,
+           "device": torch.cuda.get_device_name(0), "version": jpgx.version(), "runs": []}
+    for name, slug, images in gray_inputs():
+        res["runs"].append(measure_gray(name, slug, images, dev))
+        print(json.dumps(res["runs"][-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    with open(dst, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    ok = all(r["bytes_equal"] and r["repeat_equal"] for r in res["runs"])
+    print("bytes equal:", ok)
+    sys.exit(0 if ok else 1)
+
+
 def main():
-    global PARENT
-    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size")
+    global PARENT, GRAY_FILES
+    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size", "--gray")
     for a in sys.argv[1:]:
         if a.startswith("--parent-lib="):
             # an older build has only the plain entry points: bind the one call that is timed
             import ctypes
             PARENT = ctypes.CDLL(os.path.abspath(a.split("=", 1)[1]))
             PARENT.jpgx_pixels_gpu.argtypes = jpgx.lib.jpgx_pixels_gpu.argtypes
-    args = [a for a in sys.argv[1:] if a not in modes and not a.startswith("--parent-lib=")]
-    optimize, decoding, pixels, sub, any_size = (m in sys.argv[1:] for m in modes)
+        if a.startswith("--gray-files="):
+            GRAY_FILES = os.path.abspath(a.split("=", 1)[1])
+    args = [a for a in sys.argv[1:] if a not in modes and not a.startswith(("--parent-lib=", "--gray-files="))]
+    optimize, decoding, pixels, sub, any_size, gray = (m in sys.argv[1:] for m in modes)
+    if gray:
+        assert not (optimize or decoding or pixels), "--gray stands alone"
+        return main_gray(args[0] if args else os.path.join(REPO, "profiles", "jfif_gpu_gray.json"))
     assert decoding or not sub, "--subinterval goes with --decode"
     assert pixels or not any_size, "--any-size goes with --pixels"
     run = measure_px_any if any_size else measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
