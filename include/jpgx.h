@@ -358,6 +358,52 @@ int jpgx_pixels_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t 
                         uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
                         void *d_workspace, size_t workspace_bytes, void *stream);
 
+/* The encode side of the family.  The edge rule: the coded frame of a width x
+ * height image is the image with its last column repeated to the right and its last row repeated
+ * downwards, up to jpgx_coded_size's cw x ch -- numpy's np.pad(rgb, ((0, ch - H), (0, cw - W), (0, 0)),
+ * mode="edge").  It is this project's own rule, not libjpeg's (which fills the blocks beyond a
+ * component's width with a DC-only copy of the block before); decoders crop to SOF's size, so the file
+ * is valid either way.
+ *
+ * jpgx_workspace_size_any / jpgx_blocks_gpu_any: jpgx_blocks_gpu for a batch of images of any width
+ * and height.  fr->width and fr->height are the visible size, 1 .. 65535 each; whole frames only:
+ * fr->row_begin 0 and fr->row_end ch / 8.  d_rgb: any alignment, fr->in_pitch >= 3 width with no
+ * multiple-of-8 rule, any fr->in_frame_stride that keeps the frames of a batch apart (at least
+ * in_pitch (height - 1) + 3 width); nothing is read outside bytes [0, 3 width) of rows [0, height) of a
+ * frame.  d_out and fr->out_frame_stride follow jpgx_blocks_gpu's rules for the coded frame.  The call
+ * builds the coded frames in the workspace (k_pad_edge, csrc/jpgx_pad.hip) and runs jpgx_blocks_gpu's
+ * launch over them: the output is exactly jpgx_blocks_gpu's for the padded images with the caller's
+ * quality, sample_ratio and flags (parity mode, JPGX_FLAG_SUBSAMPLE, JPGX_FLAG_FORCE_EXACT), in the
+ * coded frame's layout Y [nb][64] | Cb [nbc][64] | Cr [nbc][64] -- what jpgx_jfif_decode_gpu_any
+ * returns.  cw x ch is the coded size of p->sample_ratio whatever the flags.  The underflow bytes
+ * depend on the image size: where p->underflow equals jpgx_default_params' for width x height the
+ * bytes of the coded size are used (jpgx_default_params(cw, ch)), other bytes are the caller's own and
+ * stay.  Workspace: the padded batch, nframes * ch * 3 cw bytes, plus jpgx_workspace_size of the coded
+ * frame, every part rounded up to 16 bytes; 16-byte aligned.  Asynchronous on `stream`, capturable, no
+ * global state.  All checks happen before the first device call, the first that applies:
+ * JPGX_EARG (null fr or p), JPGX_ESAMPLE, JPGX_EQUALITY, JPGX_EGEOMETRY (a side outside 1 .. 65535),
+ * JPGX_EARG (nframes < 1, a stripe that is not the whole frame, in_pitch, in_frame_stride, null
+ * d_rgb, d_out or d_workspace), JPGX_EWORKSPACE (too small or misaligned), then jpgx_blocks_gpu's own
+ * for the coded frame.  The size query returns 0 where the call returns one of the first five. */
+size_t jpgx_workspace_size_any(const jpgx_frames *fr, const jpgx_params *p);
+int jpgx_blocks_gpu_any(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb,
+                        int16_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream);
+
+/* jpgx_jfif_gpu_workspace_size_ex / jpgx_jfif_gpu_ex (jfif_flags 0 or JPGX_JFIF_OPTIMIZE) for files of
+ * any width and height, 1 .. 65535 each: d_coef holds the coded frames (jpgx_blocks_gpu_any's output,
+ * coef_frame_stride at least the coded frame's (nb + 2 nbc) * 64), every block of which is coded by
+ * the same kernels; SOF states width x height; the restart interval still counts MCUs of the coded
+ * frame.  Frame f's file is jpgx_write_jfif_any's for the same arguments (restart_rows -1 there: 1),
+ * which is jpgx_jfif_gpu_ex's file for the coded size with the four size bytes of SOF replaced.  A
+ * sample_ratio outside 0 .. 2 or a side outside 1 .. 65535 is JPGX_EARG (0 from the size query);
+ * JPGX_EGEOMETRY does not occur; the contract of jpgx_jfif_gpu_ex holds otherwise, word for word. */
+size_t jpgx_jfif_gpu_any_workspace_size(int width, int height, int sample_ratio, int restart_rows,
+                                        size_t nframes, size_t out_cap, unsigned jfif_flags);
+int jpgx_jfif_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width,
+                      int height, int quality, int sample_ratio, int restart_rows,
+                      unsigned jfif_flags, uint8_t *d_out, size_t out_frame_stride, size_t out_cap,
+                      uint64_t *d_len, void *d_workspace, size_t workspace_bytes, void *stream);
+
 /* ---- one-component (grayscale) files -------------------------------------
  * The entry points above refuse a file with one component (JPGX_EJFIF_HEADER); the _gray family takes
  * such files and only such files, of any width and height in 1 .. 65535.  What is accepted is stated

@@ -187,6 +187,28 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
                         int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out,
                         size_t cap, size_t *len);
 
+/* jpgx_write_jfif_opt for a file of any width and height, 1 .. 65535 each: coef holds
+ * the coded frame's blocks -- the size rounded up to the MCU of sample_ratio (jpgx_coded_size), what
+ * jpgx_blocks_gpu_any writes and jpgx_read_jfif_any returns -- all of which are coded; SOF states
+ * width x height; the restart interval counts MCUs of the coded frame.  Byte for byte the file is
+ * jpgx_write_jfif_opt's for the coded size with the four size bytes of SOF replaced, and for a size
+ * that is a multiple of the MCU it is that file.  jpgx_jfif_bound(coded width, coded height) bounds
+ * its size.  JPGX_EARG for a sample_ratio outside 0 .. 2 or a side outside 1 .. 65535;
+ * JPGX_EGEOMETRY does not occur; everything else as jpgx_write_jfif_opt. */
+int jpgx_write_jfif_any(const int16_t *coef, int width, int height, int quality, int sample_ratio,
+                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out,
+                        size_t cap, size_t *len);
+
+/* The edge rule of the encode side's _any entry points, on the host: out, coded_height rows of
+ * 3 coded_width bytes, is the width x height image rgb (rows `pitch` >= 3 width bytes apart) with its
+ * last column repeated to the right and its last row repeated downwards -- numpy's
+ * np.pad(rgb, ((0, ch - H), (0, cw - W), (0, 0)), mode="edge").  This is the project's own rule, not
+ * libjpeg's (which fills the blocks beyond a component's width with a DC-only copy of the block
+ * before); decoders crop to SOF's size, so the file is valid either way.  JPGX_EARG: null pointers,
+ * pitch below 3 width; JPGX_EGEOMETRY: a side <= 0 or a coded side below the image's. */
+int jpgx_pad_edge(const uint8_t *rgb, int width, int height, size_t pitch, int coded_width,
+                  int coded_height, uint8_t *out);
+
 /* ---- 6. The way back: a baseline JFIF file's coefficients (entropy decoding only) ------------- */
 
 typedef struct jpgx_jfif_info {
@@ -311,6 +333,15 @@ int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int qualit
 int jpgx_encode_rgb_to_jpeg(const uint8_t *rgb, int width, int height, size_t pitch,
                             const char *output, int quality, int sample_ratio, unsigned flags,
                             int device);
+
+/* The same for an image of any width and height, 1 .. 65535 each: the coded frame by the edge rule
+ * (jpgx_pad_edge, into a staging buffer), jpgx_blocks over it with the coded size's default
+ * parameters, jpgx_write_jfif_any.  The coded frame is that of the file's sampling: sample_ratio with
+ * JPGX_FLAG_SUBSAMPLE, 0 (4:4:4, MCU 8 x 8) without.  JPGX_ESAMPLE, JPGX_EQUALITY, JPGX_EGEOMETRY (a
+ * side outside 1 .. 65535), JPGX_EARG (null pointers, pitch below 3 width) before any work. */
+int jpgx_encode_rgb_to_jpeg_any(const uint8_t *rgb, int width, int height, size_t pitch,
+                                const char *output, int quality, int sample_ratio, unsigned flags,
+                                int device);
 
 /* The reference's public entry point (src/headers/jpg_encode.h:85): BMP in, JPEG file out --
  * the block transform on GPU 0, then jpgx_write_jfif.  Returns 0 or a JPGX_E* code. */

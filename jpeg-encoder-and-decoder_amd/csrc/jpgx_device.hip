@@ -1,6 +1,7 @@
 /*
  * jpgx_device.hip -- the device C ABI of include/jpgx.h: jpgx_blocks_gpu and its _ev / _timed
- * forms (argument checks, the launch arguments, one launcher), the on-device input generators
+ * forms (argument checks, the launch arguments, one launcher), jpgx_blocks_gpu_any (k_pad_edge of
+ * csrc/jpgx_pad.hip into the workspace, then the same launch), the on-device input generators
  * and jpgx_device_count.  Compiled twice; the launcher is the only difference.  The product
  * (libjpgx.so) runs one kernel per mode on the matrix cores (jx_launch_mx, csrc/jpgx_mx.hip):
  * k_mxs for 4:4:4, k_mxs422 / k_mxs420 for true 4:2:2 / 4:2:0.  The test-only cross-check library
@@ -13,6 +14,7 @@
 #include <algorithm>
 
 #include "jpgx_internal.h"
+#include "jx_frame.h"
 #include "jx_hip.h"
 
 namespace {
@@ -64,10 +66,19 @@ __global__ void k_gen_tie(uint8_t *dst, int W, int H)
 
 constexpr size_t kMaxPitch = (size_t)1 << 27;     /* 16 rows x pitch + 256 < 2^32 */
 
-int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb, int16_t *d_out,
-               void *d_workspace, size_t workspace_bytes, void *stream, void *event_after, void *ev_start,
-               void *ev_stop)
+/* what a checked call launches; empty: a stripe of no rows, nothing to do */
+struct BlocksPlan {
+    jx_xform_args xa;
+    int sr;                 /* the kernel's mode: 0, or the ratio of true subsampling */
+    size_t nbc;
+    bool empty;
+};
+
+/* every argument check of jpgx_blocks_gpu, and the launch arguments; no device call */
+int blocks_plan(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb, int16_t *d_out,
+                void *d_workspace, size_t workspace_bytes, BlocksPlan &pl)
 {
+    pl.empty = true;
     if (!fr || !p) return JPGX_EARG;
     int rc = jpgx_validate(fr->width, fr->height, p);
     if (rc) return rc;
@@ -97,7 +108,7 @@ int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb
     if (workspace_bytes < jpgx_workspace_size(fr) || ((uintptr_t)d_workspace & 15))
         return JPGX_EWORKSPACE;
 
-    jx_xform_args xa;
+    jx_xform_args &xa = pl.xa;
     memset(&xa, 0, sizeof xa);
     jx_geom &g = xa.g;
     g.rgb = d_rgb;
@@ -119,14 +130,70 @@ int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb
     xa.quality = p->quality;
     xa.force_exact = (p->flags & JPGX_FLAG_FORCE_EXACT) ? 1 : 0;
     xa.luma_only = sub ? 1 : 0;
-    const int sr = sub ? p->sample_ratio : 0;
+    pl.sr = sub ? p->sample_ratio : 0;
+    pl.nbc = nbc;
+    pl.empty = false;
+    return JPGX_OK;
+}
+
+int blocks_launch(const BlocksPlan &pl, void *stream, void *event_after, void *ev_start, void *ev_stop)
+{
 #if JPGX_ALT_DISPATCH
-    rc = jx_launch_alt(&xa, sr, nbc, stream, ev_start, ev_stop);
+    int rc = jx_launch_alt(&pl.xa, pl.sr, pl.nbc, stream, ev_start, ev_stop);
 #else
-    rc = jx_launch_mx(&xa, sr, stream, ev_start, ev_stop);
+    int rc = jx_launch_mx(&pl.xa, pl.sr, stream, ev_start, ev_stop);
 #endif
     if (!rc && event_after) rc = jx_hip_rc(hipEventRecord((hipEvent_t)event_after, (hipStream_t)stream));
     return rc;
+}
+
+int blocks_gpu(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb, int16_t *d_out,
+               void *d_workspace, size_t workspace_bytes, void *stream, void *event_after, void *ev_start,
+               void *ev_stop)
+{
+    BlocksPlan pl;
+    const int rc = blocks_plan(fr, p, d_rgb, d_out, d_workspace, workspace_bytes, pl);
+    if (rc || pl.empty) return rc;
+    return blocks_launch(pl, stream, event_after, ev_start, ev_stop);
+}
+
+/* ---- images of any width and height ------------------------------------------ */
+struct AnyLayout {
+    jpgx_frames cf;         /* the padded batch as the plain entry point takes it */
+    jpgx_params cp;         /* the caller's parameters, for the coded size */
+    size_t padded, inner, total;
+};
+
+/* the refusals of the table in include/jpgx.h but for the pointers and the workspace; no device call */
+int any_layout(const jpgx_frames *fr, const jpgx_params *p, AnyLayout &l)
+{
+    if (!fr || !p) return JPGX_EARG;
+    if (p->sample_ratio < 0 || p->sample_ratio > 2) return JPGX_ESAMPLE;
+    if (p->quality < 1 || p->quality > JX_MAXQ) return JPGX_EQUALITY;
+    jx_frame_any a;
+    if (jx_frame_make_any(fr->width, fr->height, p->sample_ratio, &a)) return JPGX_EGEOMETRY;
+    const int cw = (int)a.c.bw * 8, ch = (int)a.c.bh * 8;
+    if (fr->nframes < 1 || fr->row_begin != 0 || fr->row_end != ch / 8) return JPGX_EARG;
+    if (fr->in_pitch < (size_t)fr->width * 3) return JPGX_EARG;
+    if (fr->nframes > 1 && fr->in_frame_stride < fr->in_pitch * (size_t)(fr->height - 1) + (size_t)fr->width * 3)
+        return JPGX_EARG;
+    l.cf = *fr;
+    l.cf.width = cw;
+    l.cf.height = ch;
+    l.cf.in_pitch = (size_t)cw * 3;
+    l.cf.in_frame_stride = l.cf.in_pitch * (size_t)ch;
+    /* the underflow bytes depend on the size: the caller's defaults become the coded size's, bytes
+     * the caller chose stay */
+    jpgx_params dv, dc;
+    jpgx_default_params(&dv, fr->width, fr->height, p->quality, p->sample_ratio);
+    jpgx_default_params(&dc, cw, ch, p->quality, p->sample_ratio);
+    l.cp = *p;
+    if (!memcmp(p->underflow, dv.underflow, sizeof dv.underflow)) memcpy(l.cp.underflow, dc.underflow, sizeof dc.underflow);
+    jx_carve ws;
+    l.padded = ws.take(l.cf.in_frame_stride * (size_t)fr->nframes);
+    l.inner = ws.take(jpgx_workspace_size(&l.cf));
+    l.total = ws.at;
+    return JPGX_OK;
 }
 
 }  // namespace
@@ -152,6 +219,30 @@ int jpgx_blocks_gpu_timed(const jpgx_frames *fr, const jpgx_params *p, const uin
 {
     if (!ev_start || !ev_stop) return JPGX_EARG;
     return blocks_gpu(fr, p, d_rgb, d_out, d_workspace, workspace_bytes, stream, nullptr, ev_start, ev_stop);
+}
+
+size_t jpgx_workspace_size_any(const jpgx_frames *fr, const jpgx_params *p)
+{
+    AnyLayout l;
+    return any_layout(fr, p, l) ? 0 : l.total;
+}
+
+int jpgx_blocks_gpu_any(const jpgx_frames *fr, const jpgx_params *p, const uint8_t *d_rgb,
+                        int16_t *d_out, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    AnyLayout l;
+    int rc = any_layout(fr, p, l);
+    if (rc) return rc;
+    if (!d_rgb || !d_out || !d_workspace) return JPGX_EARG;
+    if (workspace_bytes < l.total || ((uintptr_t)d_workspace & 15)) return JPGX_EWORKSPACE;
+    uint8_t *padded = (uint8_t *)d_workspace + l.padded;
+    BlocksPlan pl;
+    rc = blocks_plan(&l.cf, &l.cp, padded, d_out, (uint8_t *)d_workspace + l.inner, workspace_bytes - l.inner, pl);
+    if (rc || pl.empty) return rc;
+    rc = jx_launch_pad(d_rgb, padded, fr->width, fr->height, l.cf.width, l.cf.height, fr->nframes, fr->in_pitch,
+                       fr->in_frame_stride, stream);
+    if (rc) return rc;
+    return blocks_launch(pl, stream, nullptr, nullptr, nullptr);
 }
 
 int jpgx_gen_splitmix_gpu(uint8_t *d_dst, size_t nbytes, uint64_t seed, void *stream)

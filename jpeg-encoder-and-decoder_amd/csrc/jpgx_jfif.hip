@@ -658,11 +658,14 @@ __global__ __launch_bounds__(kT) void k_jf_tables(const JfOpt o)
 
 /* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0.  The
  * device codes with restart intervals only: restart_rows 0 is refused, -1 is one MCU row */
-int jf_geometry(int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
+int jf_geometry(bool any, int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
 {
     if (restart_rows == 0 || restart_rows < -1 || !jx_frames_ok(nframes)) return JPGX_EARG;
-    const int rc = jx_frame_rc_coder(jx_frame_make(width, height, sample_ratio, &a.g));
+    jx_frame_any fa;                                       /* any: the coded frame of a width x height file */
+    const int rc = jx_frame_rc_coder(any ? jx_frame_make_any(width, height, sample_ratio, &fa)
+                                         : jx_frame_make(width, height, sample_ratio, &a.g));
     if (rc) return rc;
+    if (any) a.g = fa.c;
     a.rpi = restart_rows > 0 ? (uint32_t)restart_rows : 1u;
     if (a.rpi > jx_frame_max_rows(&a.g)) return JPGX_EARG;
     a.ni = (a.g.cbh + a.rpi - 1) / a.rpi;
@@ -698,6 +701,15 @@ JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap, unsigned jfi
     return l;
 }
 
+size_t jf_workspace_size(bool any, int width, int height, int sample_ratio, int restart_rows, size_t nframes,
+                         size_t out_cap, unsigned jfif_flags)
+{
+    JfArgs a;
+    if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return 0;
+    if (jf_geometry(any, width, height, sample_ratio, restart_rows, nframes, a)) return 0;
+    return jf_layout(a, nframes, out_cap, jfif_flags).total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -711,10 +723,13 @@ size_t jpgx_jfif_gpu_workspace_size(int width, int height, int sample_ratio, int
 size_t jpgx_jfif_gpu_workspace_size_ex(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
                                        size_t out_cap, unsigned jfif_flags)
 {
-    JfArgs a;
-    if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return 0;
-    if (jf_geometry(width, height, sample_ratio, restart_rows, nframes, a)) return 0;
-    return jf_layout(a, nframes, out_cap, jfif_flags).total;
+    return jf_workspace_size(false, width, height, sample_ratio, restart_rows, nframes, out_cap, jfif_flags);
+}
+
+size_t jpgx_jfif_gpu_any_workspace_size(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
+                                        size_t out_cap, unsigned jfif_flags)
+{
+    return jf_workspace_size(true, width, height, sample_ratio, restart_rows, nframes, out_cap, jfif_flags);
 }
 
 int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
@@ -725,10 +740,17 @@ int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframe
                             0u, d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
 }
 
-int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
-                     int quality, int sample_ratio, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
-                     size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
-                     size_t workspace_bytes, void *stream)
+}  /* extern "C" */
+
+namespace {
+
+/* jpgx_jfif_gpu_ex, and with `any` jpgx_jfif_gpu_any: the same kernels over the coded frame of a
+ * width x height file; the header states the file's own size, the restart interval counts the coded
+ * frame's MCUs */
+int jf_code(bool any, const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+            int quality, int sample_ratio, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
+            size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
+            size_t workspace_bytes, void *stream)
 {
     JfArgs a;
     memset(&a, 0, sizeof a);
@@ -736,7 +758,7 @@ int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nfr
     if (!d_coef || !d_out || !d_len || !d_workspace || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_out & 15) ||
         ((uintptr_t)d_len & 7) || ((uintptr_t)d_workspace & 15))
         return JPGX_EARG;
-    int rc = jf_geometry(width, height, sample_ratio, restart_rows, nframes, a);
+    int rc = jf_geometry(any, width, height, sample_ratio, restart_rows, nframes, a);
     if (rc) return rc;
     if (!jx_coef_batch_ok(coef_frame_stride, a.g.nblk) || out_frame_stride < out_cap) return JPGX_EARG;
     JfHdr hdr;
@@ -807,6 +829,28 @@ int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nfr
     hipLaunchKernelGGL(k_jf_frame<JfHdr>, per_frame, dim3(kT), 0, s, a, hdr);
     hipLaunchKernelGGL(k_jf_stuff, per_interval, dim3(kT), 0, s, a);
     return jx_hip_rc(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" {
+
+int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                     int quality, int sample_ratio, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
+                     size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
+                     size_t workspace_bytes, void *stream)
+{
+    return jf_code(false, d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
+                   jfif_flags, d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
+}
+
+int jpgx_jfif_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                      int quality, int sample_ratio, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
+                      size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
+                      size_t workspace_bytes, void *stream)
+{
+    return jf_code(true, d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
+                   jfif_flags, d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
 }
 
 }  /* extern "C" */

@@ -1,6 +1,6 @@
 /*
  * jpgx_jfif_write.cpp -- the host JFIF writer's scan: jpgx_write_jfif,
- * jpgx_write_jfif_sub, jpgx_write_jfif_ex, jpgx_write_jfif_opt, jpgx_jfif_bound
+ * jpgx_write_jfif_sub, jpgx_write_jfif_ex, jpgx_write_jfif_opt, jpgx_write_jfif_any, jpgx_jfif_bound
  * (include/jpgx_compat.h).  What a block's symbols are, the clamps, the scan's geometry and its
  * block order are jx_jfif_enc.h's, the routines the device coder (jpgx_jfif.hip) runs; this file
  * adds the bit writer with its 0xFF stuffing, the restart-row policy and the threads.  Tables and
@@ -223,49 +223,20 @@ void run_jobs(Job *jobs, pthread_t *tid, long T)
     for (long t = 1; t < nthr; t++) pthread_join(tid[t], NULL);
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t jpgx_jfif_bound(int width, int height)
-{
-    if (width <= 0 || height <= 0) return 0;
-    /* headers + a per-block maximum with margin -- DC code + magnitude <= 16 + 16 bits, 63 AC
-     * codes + magnitudes <= 63 x (16 + 16) bits, EOB <= 16 bits -- doubled for 0xFF stuffing,
-     * plus per restart interval (at most one per MCU row) the padding byte, its possible stuffing
-     * byte and RSTm: 4 bytes */
-    const size_t blocks = (size_t)(width / 8 + 1) * (height / 8 + 1) * 3;
-    return 1024 + blocks * 2 * (32 + 63 * 32 + 16) / 8 + 4 * (size_t)(height / 8 + 1);
-}
-
-int jpgx_write_jfif(const int16_t *coef, int width, int height, int quality, uint8_t *out,
-                    size_t cap, size_t *len)
-{
-    return jpgx_write_jfif_ex(coef, width, height, quality, 0, 0, 1, out, cap, len);
-}
-
-int jpgx_write_jfif_sub(const int16_t *coef, int width, int height, int quality,
-                        int sample_ratio, uint8_t *out, size_t cap, size_t *len)
-{
-    return jpgx_write_jfif_ex(coef, width, height, quality, sample_ratio, 0, 1, out, cap, len);
-}
-
-int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, int sample_ratio,
-                       int restart_rows, int nthreads, uint8_t *out, size_t cap, size_t *len)
-{
-    return jpgx_write_jfif_opt(coef, width, height, quality, sample_ratio, restart_rows, nthreads, 0u, out,
-                               cap, len);
-}
-
-int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality, int sample_ratio,
-                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
-                        size_t *len)
+/* jpgx_write_jfif_opt, and with `any` jpgx_write_jfif_any: the scan of the coded frame of a
+ * width x height file; the header states the file's own size, the restart interval counts the coded
+ * frame's MCUs */
+int write_jfif(bool any, const int16_t *coef, int width, int height, int quality, int sample_ratio,
+               int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap, size_t *len)
 {
     if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return JPGX_EARG;
     if (!coef || !out || restart_rows < -1 || nthreads < 0) return JPGX_EARG;
     Scan S;
-    int rc = jx_frame_rc_coder(jx_frame_make(width, height, sample_ratio, &S.g));
+    jx_frame_any fa;
+    int rc = jx_frame_rc_coder(any ? jx_frame_make_any(width, height, sample_ratio, &fa)
+                                   : jx_frame_make(width, height, sample_ratio, &S.g));
     if (rc) return rc;
+    if (any) S.g = fa.c;
     if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
     S.coef = coef;
     const size_t mrows = S.g.cbh;
@@ -357,6 +328,56 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
     free(tid);
     free(cnt);
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t jpgx_jfif_bound(int width, int height)
+{
+    if (width <= 0 || height <= 0) return 0;
+    /* headers + a per-block maximum with margin -- DC code + magnitude <= 16 + 16 bits, 63 AC
+     * codes + magnitudes <= 63 x (16 + 16) bits, EOB <= 16 bits -- doubled for 0xFF stuffing,
+     * plus per restart interval (at most one per MCU row) the padding byte, its possible stuffing
+     * byte and RSTm: 4 bytes */
+    const size_t blocks = (size_t)(width / 8 + 1) * (height / 8 + 1) * 3;
+    return 1024 + blocks * 2 * (32 + 63 * 32 + 16) / 8 + 4 * (size_t)(height / 8 + 1);
+}
+
+int jpgx_write_jfif(const int16_t *coef, int width, int height, int quality, uint8_t *out,
+                    size_t cap, size_t *len)
+{
+    return jpgx_write_jfif_ex(coef, width, height, quality, 0, 0, 1, out, cap, len);
+}
+
+int jpgx_write_jfif_sub(const int16_t *coef, int width, int height, int quality,
+                        int sample_ratio, uint8_t *out, size_t cap, size_t *len)
+{
+    return jpgx_write_jfif_ex(coef, width, height, quality, sample_ratio, 0, 1, out, cap, len);
+}
+
+int jpgx_write_jfif_ex(const int16_t *coef, int width, int height, int quality, int sample_ratio,
+                       int restart_rows, int nthreads, uint8_t *out, size_t cap, size_t *len)
+{
+    return jpgx_write_jfif_opt(coef, width, height, quality, sample_ratio, restart_rows, nthreads, 0u, out,
+                               cap, len);
+}
+
+int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality, int sample_ratio,
+                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
+                        size_t *len)
+{
+    return write_jfif(false, coef, width, height, quality, sample_ratio, restart_rows, nthreads, jfif_flags, out,
+                      cap, len);
+}
+
+int jpgx_write_jfif_any(const int16_t *coef, int width, int height, int quality, int sample_ratio,
+                        int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
+                        size_t *len)
+{
+    return write_jfif(true, coef, width, height, quality, sample_ratio, restart_rows, nthreads, jfif_flags, out,
+                      cap, len);
 }
 
 }  /* extern "C" */

@@ -30,4 +30,14 @@ static inline bool jx_coef_batch_ok(size_t coef_frame_stride, uint32_t nblk)
 {
     return coef_frame_stride % 64 == 0 && coef_frame_stride >= (size_t)nblk * 64;
 }
+
+/* k_pad_edge (jpgx_pad.hip, both libraries): the coded frames of nframes images of
+ * width x height -- rows of 3 coded_width bytes, frames coded_height rows apart, from the 16-byte
+ * aligned d_coded -- with the last column repeated to the right and the last row downwards.  d_rgb: any
+ * alignment, in_pitch >= 3 width; nothing is read outside bytes [0, 3 width) of rows [0, height) of a
+ * frame.  The caller (jpgx_blocks_gpu_any, jpgx_device.hip) has checked the geometry.  It stands here
+ * and not in jpgx_internal.h, whose text is part of the transform kernels' source hash
+ * (tools/pmc_summary.py). */
+extern "C" int jx_launch_pad(const uint8_t *d_rgb, uint8_t *d_coded, int width, int height, int coded_width,
+                             int coded_height, int nframes, size_t in_pitch, size_t in_frame_stride, void *stream);
 #endif

@@ -289,13 +289,9 @@ static int file_begin(FileJob *j, size_t nblocks, int width, int height, int nom
     return (j->coef && j->buf) ? JPGX_OK : nomem;
 }
 
-/* rc: what came of filling j->coef */
-static int file_end(FileJob *j, int rc, int width, int height, int quality, int sr, const char *output)
+/* rc: what came of the scan; the first len bytes of j->buf become the file, and the job ends */
+static int file_put(FileJob *j, int rc, size_t len, const char *output)
 {
-    size_t len = 0;
-    if (!rc)
-        rc = sr ? jpgx_write_jfif_sub(j->coef, width, height, quality, sr, j->buf, j->cap, &len)
-                : jpgx_write_jfif(j->coef, width, height, quality, j->buf, j->cap, &len);
     if (!rc) {
         FILE *f = fopen(output, "wb");
         if (!f || fwrite(j->buf, 1, len, f) != len) rc = JPGX_EARG;
@@ -304,6 +300,16 @@ static int file_end(FileJob *j, int rc, int width, int height, int quality, int 
     free(j->coef);
     free(j->buf);
     return rc;
+}
+
+/* rc: what came of filling j->coef */
+static int file_end(FileJob *j, int rc, int width, int height, int quality, int sr, const char *output)
+{
+    size_t len = 0;
+    if (!rc)
+        rc = sr ? jpgx_write_jfif_sub(j->coef, width, height, quality, sr, j->buf, j->cap, &len)
+                : jpgx_write_jfif(j->coef, width, height, quality, j->buf, j->cap, &len);
+    return file_put(j, rc, len, output);
 }
 
 int jpgx_encode_rgb_to_jpeg(const uint8_t *rgb, int width, int height, size_t pitch,
@@ -324,6 +330,36 @@ int jpgx_encode_rgb_to_jpeg(const uint8_t *rgb, int width, int height, size_t pi
     rc = file_begin(&j, nblocks, width, height, JPGX_ENOMEM);
     if (!rc) rc = jpgx_blocks(rgb, width, height, pitch, &p, j.coef, device);
     return file_end(&j, rc, width, height, quality, sub ? sample_ratio : 0, output);
+}
+
+/* jpgx_encode_rgb_to_jpeg for an image of any width and height: the coded frame by the edge rule
+ * (jpgx_pad_edge) into a staging buffer, the forward path over it, then jpgx_write_jfif_any */
+int jpgx_encode_rgb_to_jpeg_any(const uint8_t *rgb, int width, int height, size_t pitch,
+                                const char *output, int quality, int sample_ratio, unsigned flags,
+                                int device)
+{
+    if (!rgb || !output) return JPGX_EARG;
+    const int sub = (flags & JPGX_FLAG_SUBSAMPLE) && sample_ratio != 0;
+    const int sr = sub ? sample_ratio : 0;                 /* the file's, and the coded frame's */
+    if (sample_ratio < 0 || sample_ratio > 2) return JPGX_ESAMPLE;
+    if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
+    jx_frame_any a;
+    if (jx_frame_make_any(width, height, sr, &a)) return JPGX_EGEOMETRY;
+    if (pitch < (size_t)width * 3) return JPGX_EARG;
+    const int cw = (int)a.c.bw * 8, ch = (int)a.c.bh * 8;
+    jpgx_params p;
+    jpgx_default_params(&p, cw, ch, quality, sr);
+    p.flags = sub ? JPGX_FLAG_SUBSAMPLE : 0u;
+    FileJob j;
+    uint8_t *coded = (uint8_t *)malloc((size_t)cw * 3 * (size_t)ch);
+    int rc = file_begin(&j, a.c.nblk, cw, ch, JPGX_ENOMEM);
+    if (!coded) rc = JPGX_ENOMEM;
+    if (!rc) rc = jpgx_pad_edge(rgb, width, height, pitch, cw, ch, coded);
+    if (!rc) rc = jpgx_blocks(coded, cw, ch, (size_t)cw * 3, &p, j.coef, device);
+    free(coded);
+    size_t len = 0;
+    if (!rc) rc = jpgx_write_jfif_any(j.coef, width, height, quality, sr, 0, 1, 0u, j.buf, j.cap, &len);
+    return file_put(&j, rc, len, output);
 }
 
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

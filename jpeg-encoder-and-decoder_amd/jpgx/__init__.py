@@ -14,6 +14,9 @@ decode_jpeg_coefficients -- baseline JFIF files back to the coefficients (DESIGN
 pixels_gpu, decode_jpeg -- the coefficients to RGB, libjpeg's default decoder's pixels (4.9).
 These four take any_size=True for files whose width and height are no multiple of the MCU (the
 library's _any entry points); coded_size is the size such a file's coefficients are of.
+The way there takes images of any size too: encode_blocks, jfif_gpu and encode_jpeg with any_size=True
+(jpgx_blocks_gpu_any, jpgx_jfif_gpu_any) transform and code the image's coded frame, the image with its
+last column and row repeated up to the MCU (pad_edge), and the file states the image's own size.
 One-component (grayscale) files go through jfif_decode_gpu_gray and pixels_gpu_gray (the library's
 _gray entry points), or through decode_jpeg / decode_jpeg_coefficients with gray=True.
 """
@@ -61,6 +64,7 @@ EXPORTS = [
     "jpgx_coded_size", "jpgx_jfif_decode_gpu_any_workspace_size", "jpgx_jfif_decode_gpu_any",
     "jpgx_pixels_gpu_any_workspace_size", "jpgx_pixels_gpu_any",
     "jpgx_jfif_decode_gpu_gray_workspace_size", "jpgx_jfif_decode_gpu_gray", "jpgx_pixels_gpu_gray",
+    "jpgx_workspace_size_any", "jpgx_blocks_gpu_any", "jpgx_jfif_gpu_any_workspace_size", "jpgx_jfif_gpu_any",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -73,6 +77,7 @@ COMPAT_EXPORTS = [
     "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host",
     "jpgx_jfif_info_of_any", "jpgx_read_jfif_any", "jpgx_read_jfif_sub_any", "jpgx_pixels_host_any",
     "jpgx_jfif_info_of_gray", "jpgx_read_jfif_gray", "jpgx_read_jfif_sub_gray", "jpgx_pixels_host_gray",
+    "jpgx_write_jfif_any", "jpgx_pad_edge", "jpgx_encode_rgb_to_jpeg_any",
 ]
 
 
@@ -165,6 +170,13 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_decode_gpu_gray_workspace_size.restype = sz
     L.jpgx_jfif_decode_gpu_gray.argtypes = [vp, sz, vp, sz, i, i, ctypes.c_uint, vp, sz, vp, vp, vp, sz, vp]
     L.jpgx_pixels_gpu_gray.argtypes = [vp, sz, sz, i, i, vp, sz, vp, vp, sz, sz, i, vp]
+    L.jpgx_workspace_size_any.argtypes = [Fp, P]
+    L.jpgx_workspace_size_any.restype = sz
+    L.jpgx_blocks_gpu_any.argtypes = L.jpgx_blocks_gpu.argtypes
+    L.jpgx_jfif_gpu_any_workspace_size.argtypes = L.jpgx_jfif_gpu_workspace_size_ex.argtypes
+    L.jpgx_jfif_gpu_any_workspace_size.restype = sz
+    L.jpgx_jfif_gpu_any.argtypes = L.jpgx_jfif_gpu_ex.argtypes
+    L.jpgx_pad_edge.argtypes = [vp, i, i, sz, i, i, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -399,7 +411,8 @@ def entropy_stats_gpu_batch(d_coef, nb_y: int, nb_c: int, stream=None):
 
 
 def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 0,
-             restart_rows: int = -1, cap: int | None = None, stream=None, optimize: bool = False):
+             restart_rows: int = -1, cap: int | None = None, stream=None, optimize: bool = False,
+             any_size: bool = False):
     """The JFIF files of a frame batch, coded on the device (jpgx_jfif_gpu): d_coef int16
     [nframes][...] as encode_blocks / blocks_gpu write each frame ([3][nb][64], or Y | Cb | Cr with
     FLAG_SUBSAMPLE for sample_ratio 1, 2; each frame contiguous, frames d_coef.stride(0) elements
@@ -409,13 +422,18 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     compat.write_jfif_ex); when a frame needs more, one retry with the capacity the library
     reports (that reads lens back, a synchronisation).  optimize: JFIF_OPTIMIZE, every frame coded
     with Huffman tables built from its own symbols (jpgx_jfif_gpu_ex), byte for byte
-    compat.write_jfif_ex(..., optimize=True)."""
+    compat.write_jfif_ex(..., optimize=True).  any_size: jpgx_jfif_gpu_any -- width and height are the
+    file's own, any 1 .. 65535, d_coef holds the coded frames (encode_blocks(any_size=True)); byte for
+    byte compat.write_jfif_ex(..., any_size=True)."""
     import torch
     if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda:
         raise ValueError("jfif_gpu: d_coef must be a device tensor")
     if d_coef.dtype != torch.int16 or d_coef.dim() < 2:
         raise ValueError("jfif_gpu: d_coef must be an int16 [nframes][...] tensor")
-    _, _, per_frame, fstride = _frame("jfif_gpu", width, height, sample_ratio, d_coef=d_coef, whole_blocks=True)
+    _, _, per_frame, fstride = _frame("jfif_gpu", width, height, sample_ratio, d_coef=d_coef, whole_blocks=True,
+                                      any_size=any_size)
+    size_fn = lib.jpgx_jfif_gpu_any_workspace_size if any_size else lib.jpgx_jfif_gpu_workspace_size_ex
+    code_fn = lib.jpgx_jfif_gpu_any if any_size else lib.jpgx_jfif_gpu_ex
     nf = d_coef.shape[0]
     dev = d_coef.device
     cap = int(cap) if cap else max(1 << 20, per_frame // 2)
@@ -423,11 +441,11 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     for attempt in range(2):
         out = torch.empty((nf, cap), dtype=torch.uint8, device=dev)
         lens = torch.empty(nf, dtype=torch.int64, device=dev)
-        need = int(lib.jpgx_jfif_gpu_workspace_size_ex(width, height, sample_ratio, restart_rows, nf, cap, jflags))
+        need = int(size_fn(width, height, sample_ratio, restart_rows, nf, cap, jflags))
         ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        _check(lib.jpgx_jfif_gpu_ex(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
-                                    restart_rows, jflags, out.data_ptr(), cap, cap, lens.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
+        _check(code_fn(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
+                       restart_rows, jflags, out.data_ptr(), cap, cap, lens.data_ptr(),
+                       ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
         if stream is not None:
             stream.synchronize()
         host = lens.cpu()
@@ -438,17 +456,21 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
 
 
 def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restart_rows: int = -1,
-                optimize: bool = False) -> bytes:
+                optimize: bool = False, any_size: bool = False) -> bytes:
     """One device image (H, W, 3 uint8 torch tensor on a GPU) -> its JFIF file: encode_blocks, then
     jfif_gpu, then a device-to-host copy of the file's bytes.  With FLAG_SUBSAMPLE and sample_ratio
-    1 / 2 the file is 4:2:2 / 4:2:0, otherwise 4:4:4.  optimize: per-image Huffman tables (jfif_gpu)."""
+    1 / 2 the file is 4:2:2 / 4:2:0, otherwise 4:4:4.  optimize: per-image Huffman tables (jfif_gpu).  any_size: an image of
+    any width and height, 1 .. 65535 each: the file states H x W and codes the coded frame of its own
+    sampling (pad_edge; the forward path gets the file's ratio, 0 without FLAG_SUBSAMPLE, so that both
+    agree on the MCU); decode_jpeg(..., any_size=True) reads it back."""
     import torch
     if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
         raise ValueError("encode_jpeg: rgb must be a device tensor")
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     sub = sample_ratio if flags & FLAG_SUBSAMPLE else 0
-    coef = encode_blocks(rgb, quality, sample_ratio, flags=flags if sub else flags & ~FLAG_SUBSAMPLE)
-    out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows, optimize=optimize)
+    coef = encode_blocks(rgb, quality, sub if any_size else sample_ratio,
+                         flags=flags if sub else flags & ~FLAG_SUBSAMPLE, any_size=any_size)
+    out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows, optimize=optimize, any_size=any_size)
     n = int(lens[0])
     if n < 0:
         raise JpgxError(EARG, "jpgx_jfif_gpu (capacity)")
@@ -749,12 +771,31 @@ def split_sub(out, nb: int, nbc: int):
     return out[:nb], out[nb:nb + 2 * nbc].reshape(2, nbc, 64)
 
 
+def pad_edge(rgb: np.ndarray, sample_ratio: int = 0) -> np.ndarray:
+    """jpgx_pad_edge: a host image (H, W, 3 uint8) -> its coded frame (ch, cw, 3), coded_size(W, H,
+    sample_ratio), by the edge rule of the encode side's any-size entry points: the last column repeated
+    to the right, the last row downwards -- np.pad(rgb, ((0, ch - H), (0, cw - W), (0, 0)), mode="edge")."""
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.strides[1:] != (3, 1) or rgb.strides[0] < 3 * rgb.shape[1]:
+        raise ValueError("pad_edge: rgb must be (H, W, 3) uint8 with packed pixels and top-down rows")
+    H, W = rgb.shape[:2]
+    cw, ch = coded_size(W, H, sample_ratio)
+    out = np.empty((ch, cw, 3), np.uint8)
+    _check(lib.jpgx_pad_edge(rgb.ctypes.data, W, H, rgb.strides[0], cw, ch, out.ctypes.data), "jpgx_pad_edge")
+    return out
+
+
 def encode_blocks(rgb, quality: int, sample_ratio: int = 0, underflow: bytes | None = None,
-                  flags: int = 0, device=None):
+                  flags: int = 0, device=None, any_size: bool = False, stream=None):
     """Convenience: one image (H,W,3 uint8 torch tensor on a GPU, or numpy on the host) ->
     int16 [3][nb][64] (with FLAG_SUBSAMPLE: [nb + 2 nbc][64], see split_sub).  Device tensors
-    stay on the device; numpy goes through jpgx_blocks."""
+    stay on the device; numpy goes through jpgx_blocks.  any_size: W and H are any 1 .. 65535; the
+    result is the plain call's for the image's coded frame (pad_edge; coded_size(W, H, sample_ratio)),
+    the underflow bytes, unless given, those of the coded size.  A device tensor goes through
+    jpgx_blocks_gpu_any, rows of any pitch as they are (only the pixels must be packed); numpy is padded
+    on the host and takes the plain route.  stream (any_size, device tensors): the stream to launch on."""
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
+    if any_size:
+        return _encode_blocks_any(rgb, W, H, quality, sample_ratio, underflow, flags, device, stream)
     nb, nbc, per_frame, _ = _frame("encode_blocks", W, H, sample_ratio, flags)
     shape = (nb + 2 * nbc, 64) if flags & FLAG_SUBSAMPLE else (3, nb, 64)
     if isinstance(rgb, np.ndarray):
@@ -774,6 +815,36 @@ def encode_blocks(rgb, quality: int, sample_ratio: int = 0, underflow: bytes | N
     out = torch.empty(shape, dtype=torch.int16, device=rgb.device)
     ws = torch.empty(workspace_size(fr), dtype=torch.uint8, device=rgb.device)
     blocks_gpu(fr, p, rgb.contiguous(), out, ws)
+    return out
+
+
+def _encode_blocks_any(rgb, W, H, quality, sample_ratio, underflow, flags, device, stream):
+    """encode_blocks(any_size=True)"""
+    nb, nbc, per_frame, _ = _frame("encode_blocks", W, H, sample_ratio, flags, any_size=True)
+    if isinstance(rgb, np.ndarray):
+        return encode_blocks(pad_edge(np.ascontiguousarray(rgb, np.uint8), sample_ratio), quality, sample_ratio,
+                             underflow, flags, device)
+    import torch
+    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+        raise ValueError("encode_blocks: rgb must be a numpy array or a device tensor")
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
+        raise ValueError("encode_blocks: rgb must be (H, W, 3) uint8")
+    if (W > 1 and tuple(rgb.stride()[1:]) != (3, 1)) or (H > 1 and rgb.stride(0) < 3 * W):
+        rgb = rgb.contiguous()
+    pitch = int(rgb.stride(0)) if H > 1 else 3 * W
+    cw, ch = coded_size(W, H, sample_ratio)
+    p = default_params(cw, ch, quality, sample_ratio, underflow, flags)
+    fr = frames(W, H, rows=(0, ch // 8), in_pitch=pitch, in_frame_stride=pitch * H, out_frame_stride=per_frame)
+    out = torch.empty((nb + 2 * nbc, 64) if flags & FLAG_SUBSAMPLE else (3, nb, 64), dtype=torch.int16,
+                      device=rgb.device)
+    need = int(lib.jpgx_workspace_size_any(ctypes.byref(fr), ctypes.byref(p)))
+    if not need:                                    # the refusal, by its code
+        _check(lib.jpgx_blocks_gpu_any(ctypes.byref(fr), ctypes.byref(p), None, None, None, 0, None), "jpgx_blocks_gpu_any")
+    ws = torch.empty(need, dtype=torch.uint8, device=rgb.device)
+    _check(lib.jpgx_blocks_gpu_any(ctypes.byref(fr), ctypes.byref(p), rgb.data_ptr(), out.data_ptr(),
+                                   ws.data_ptr(), need, _stream_ptr(stream)), "jpgx_blocks_gpu_any")
+    if stream is not None:
+        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
     return out
 
 

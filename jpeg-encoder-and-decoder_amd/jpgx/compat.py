@@ -99,6 +99,8 @@ def _setup(L):
                                       ctypes.POINTER(ctypes.c_size_t)]
     L.jpgx_encode_rgb_to_jpeg.argtypes = [vp, i, i, ctypes.c_size_t, ctypes.c_char_p, i, i,
                                           ctypes.c_uint, i]
+    L.jpgx_encode_rgb_to_jpeg_any.argtypes = L.jpgx_encode_rgb_to_jpeg.argtypes
+    L.jpgx_write_jfif_any.argtypes = L.jpgx_write_jfif_opt.argtypes
 
 
     L.jpgx_jfif_info_of.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(JfifInfo)]
@@ -258,17 +260,24 @@ def write_jfif(coef: np.ndarray, width: int, height: int, quality: int) -> bytes
 
 def write_jfif_ex(coef: np.ndarray, width: int, height: int, quality: int, sample_ratio: int = 0,
                   restart_rows: int = -1, nthreads: int = 0, cap: int | None = None,
-                  optimize: bool = False) -> bytes:
+                  optimize: bool = False, any_size: bool = False) -> bytes:
     """jpgx_write_jfif_ex: restart intervals of `restart_rows` MCU rows (-1 auto, 0 none) coded on
     `nthreads` host threads (0: one per CPU).  `cap`: output buffer size (default: grown on
     demand from the size the library reports).  optimize: jpgx_write_jfif_opt with
-    JPGX_JFIF_OPTIMIZE, Huffman tables built from the image's own symbols."""
+    JPGX_JFIF_OPTIMIZE, Huffman tables built from the image's own symbols.  any_size:
+    jpgx_write_jfif_any -- width and height are the file's own, any 1 .. 65535, and coef holds the
+    blocks of its coded frame (coded_size), all of which are coded."""
     coef = np.ascontiguousarray(coef, np.int16)
     n = ctypes.c_size_t()
     cap = cap or max(1 << 20, coef.size // 2)
+    write = lib.jpgx_write_jfif_any if any_size else lib.jpgx_write_jfif_opt
+    if any_size and sample_ratio in (0, 1, 2) and 0 < width < 65536 and 0 < height < 65536:
+        cw, ch = coded_size(width, height, sample_ratio)
+        if coef.size < (cw // 8) * (ch // 8) * (3, 2, 1.5)[sample_ratio] * 64:
+            raise ValueError("write_jfif_ex: coef must hold the coded frame's nb + 2 nbc blocks")
     for _ in range(2):
         buf = np.empty(cap, np.uint8)
-        rc = lib.jpgx_write_jfif_opt(coef.ctypes.data, width, height, quality, sample_ratio,
+        rc = write(coef.ctypes.data, width, height, quality, sample_ratio,
                                      restart_rows, nthreads, 1 if optimize else 0, buf.ctypes.data, cap,
                                      ctypes.byref(n))
         if rc == 0:
@@ -449,11 +458,12 @@ def encode_bmp_to_jpeg(src: str, dst: str, quality: int, sample_ratio: int = 0) 
 
 
 def encode_rgb_to_jpeg(rgb: np.ndarray, dst: str, quality: int, sample_ratio: int = 0,
-                       flags: int = 0, device: int = 0) -> None:
-    """In-memory (H, W, 3) uint8 image -> JFIF file (jpgx_encode_rgb_to_jpeg)."""
+                       flags: int = 0, device: int = 0, any_size: bool = False) -> None:
+    """In-memory (H, W, 3) uint8 image -> JFIF file (jpgx_encode_rgb_to_jpeg).  any_size:
+    jpgx_encode_rgb_to_jpeg_any, an image of any width and height."""
     if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.strides[1:] != (3, 1):
         raise ValueError("rgb must be (H, W, 3) uint8 with packed pixels")
     H, W = rgb.shape[:2]
-    _check(lib.jpgx_encode_rgb_to_jpeg(rgb.ctypes.data, W, H, rgb.strides[0], dst.encode(),
-                                       quality, sample_ratio, ctypes.c_uint(flags), device),
-           "jpgx_encode_rgb_to_jpeg")
+    fn = lib.jpgx_encode_rgb_to_jpeg_any if any_size else lib.jpgx_encode_rgb_to_jpeg
+    _check(fn(rgb.ctypes.data, W, H, rgb.strides[0], dst.encode(), quality, sample_ratio, ctypes.c_uint(flags),
+              device), "jpgx_encode_rgb_to_jpeg")

@@ -80,8 +80,22 @@ and per input:
   host_route_s    the files copied to pinned host memory + jpgx_read_jfif_gray + jpgx_pixels_host_gray (1 channel)
                   on 16 threads, frame after frame; best of 2
   pixels_equal    both channel counts == jpgx_pixels_host_gray on two frames, before and after the timed calls
+With --encode-any the run times the encode side's entry points for images of any size (jpgx_blocks_gpu_any with
+k_pad_edge, jpgx_jfif_gpu_any) on 8 frames of 3839 x 2159 -- the inputs' top left, rows 11517 bytes
+apart -- beside the plain ones on 3840 x 2160 and writes profiles/jfif_gpu_enc_any.json; per input, the four calls
+taken in turn, several passes, in one process:
+  plain_xform_us, any_xform_us    jpgx_blocks_gpu at 3840 x 2160 and jpgx_blocks_gpu_any at 3839 x 2159 per batch
+                  (events around 10 calls; all passes, sorted); any_xform_over_plain: the medians' ratio
+  plain_coder_us, any_coder_us, any_coder_over_plain   jpgx_jfif_gpu_ex and jpgx_jfif_gpu_any the same way
+  any_route_over_plain            (any_xform + any_coder) / (plain_xform + plain_coder), medians
+  pad_us_by_difference, pad_fraction_of_8TBps_by_difference   any_xform - plain_xform (medians): k_pad_edge and the
+                  gap between the two launches, and 6 B per pixel of the coded frames (3 read, 3 written) over it
+  pad_kernel_us, pad_fraction_of_8TBps   k_pad_edge's own time, the average of a kernel trace taken in a run of its
+                  own and named by --kernel-stats=FILE.csv (rocprofv3 --kernel-trace --stats); absent without one
+  bytes_equal     every frame's coefficients == jpgx_blocks_gpu's for the image padded by torch's replicate rule,
+                  and frame 0's file == jpgx_write_jfif_any's on the host; repeat_equal: the same after the timed calls
 Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels [--any-size
-[--parent-lib=PATH]] | --gray [--gray-files=DIR]] [OUT.json]"""
+[--parent-lib=PATH]] | --gray [--gray-files=DIR] | --encode-any [--kernel-stats=FILE.csv]] [OUT.json]"""
 import json
 import os
 import sys
@@ -633,6 +647,113 @@ def measure_px_any(name, d_rgb, dev):
     return res
 
 
+KERNEL_STATS = None                     # --kernel-stats=FILE.csv
+
+
+def pad_kernel_us():
+    """k_pad_edge's average time in a rocprofv3 --kernel-trace --stats table, in microseconds; None without one"""
+    if not KERNEL_STATS:
+        return None
+    import csv
+    with open(KERNEL_STATS, newline="") as fh:
+        for row in csv.DictReader(fh):
+            if "k_pad_edge" in row.get("Name", ""):
+                return float(row["AverageNs"]) / 1e3
+    raise SystemExit("no k_pad_edge in " + KERNEL_STATS)
+
+
+def measure_enc_any(name, d_rgb, dev):
+    import ctypes
+    VW, VH = W - 1, H - 1
+    nb = (W // 8) * (H // 8)
+    per = 3 * nb * 64
+    d_any = d_rgb[:, :VH, :VW].contiguous()              # rows of 11517 bytes, frames an odd number apart
+    coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+    coef_any = torch.empty((F, per), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+    p = jpgx.default_params(W, H, Q, 0)
+    fra = jpgx.frames(VW, VH, nframes=F, rows=(0, H // 8), in_pitch=3 * VW, in_frame_stride=3 * VW * VH,
+                      out_frame_stride=per)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 16), dtype=torch.uint8, device=dev)
+    need = int(jpgx.lib.jpgx_workspace_size_any(ctypes.byref(fra), ctypes.byref(p)))
+    aws = torch.empty(need, dtype=torch.uint8, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def plain_xform():
+        jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)
+
+    def any_xform():
+        rc = jpgx.lib.jpgx_blocks_gpu_any(ctypes.byref(fra), ctypes.byref(p), d_any.data_ptr(), coef_any.data_ptr(),
+                                          aws.data_ptr(), need, stream)
+        assert rc == 0, rc
+
+    # what the any-size call must equal: the plain one on the image padded by the edge rule
+    padded = torch.cat([d_any, d_any[:, :, -1:]], 2)
+    padded = torch.cat([padded, padded[:, -1:]], 1).contiguous()
+    want = torch.empty((F, per), dtype=torch.int16, device=dev)
+    jpgx.blocks_gpu(fr, p, padded, want, xws)
+    plain_xform()
+    any_xform()
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(coef_any, want))
+    del padded
+
+    _, lens0 = jpgx.jfif_gpu(coef, W, H, Q, 0, 1, cap=1 << 20)
+    _, lens1 = jpgx.jfif_gpu(coef_any, VW, VH, Q, 0, 1, cap=1 << 20, any_size=True)
+    cap = (int(max(lens0.max(), lens1.max())) + 4095) // 4096 * 4096
+    out = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+    out_any = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+    lens, lens_any = (torch.empty(F, dtype=torch.int64, device=dev) for _ in range(2))
+    wsb = int(jpgx.lib.jpgx_jfif_gpu_workspace_size_ex(W, H, 0, 1, F, cap, 0))
+    assert wsb == int(jpgx.lib.jpgx_jfif_gpu_any_workspace_size(VW, VH, 0, 1, F, cap, 0))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+    def plain_coder():
+        rc = jpgx.lib.jpgx_jfif_gpu_ex(coef.data_ptr(), per, F, W, H, Q, 0, 1, 0, out.data_ptr(), cap, cap,
+                                       lens.data_ptr(), ws.data_ptr(), wsb, stream)
+        assert rc == 0, rc
+
+    def any_coder():
+        rc = jpgx.lib.jpgx_jfif_gpu_any(coef_any.data_ptr(), per, F, VW, VH, Q, 0, 1, 0, out_any.data_ptr(), cap, cap,
+                                        lens_any.data_ptr(), ws.data_ptr(), wsb, stream)
+        assert rc == 0, rc
+
+    def file0():
+        n = int(lens_any[0])
+        return out_any[0, :n].cpu().numpy().tobytes()
+
+    any_coder()
+    torch.cuda.synchronize()
+    host = C.write_jfif_ex(coef_any[0].cpu().numpy().reshape(-1, 64), VW, VH, Q, 0, restart_rows=1,
+                           nthreads=HOST_THREADS, cap=cap, any_size=True)
+    equal = equal and file0() == host
+    calls = (("plain_xform_us", plain_xform), ("any_xform_us", any_xform), ("plain_coder_us", plain_coder),
+             ("any_coder_us", any_coder))
+    ts = {k: [] for k, _ in calls}
+    for _ in range(7):                                   # the four in turn, pass after pass
+        for k, fn in calls:
+            ts[k] += timed(fn, rounds=1, settle=0.2)
+    ts = {k: sorted(v) for k, v in ts.items()}
+    torch.cuda.synchronize()
+    repeat_equal = bool(torch.equal(coef_any, want)) and file0() == host
+    m = {k: median(v) for k, v in ts.items()}
+    pad = m["any_xform_us"] - m["plain_xform_us"]
+    moved = 6 * F * W * H                                # the coded frames: 3 B read and 3 B written per pixel
+    res = {"input": name, **ts,
+           "any_xform_over_plain": m["any_xform_us"] / m["plain_xform_us"],
+           "any_coder_over_plain": m["any_coder_us"] / m["plain_coder_us"],
+           "any_route_over_plain": (m["any_xform_us"] + m["any_coder_us"]) / (m["plain_xform_us"] + m["plain_coder_us"]),
+           "pad_us_by_difference": pad, "pad_bytes": moved,
+           "pad_fraction_of_8TBps_by_difference": moved / (pad * 1e-6) / 8e12 if pad > 0 else None,
+           "workspace_bytes": need, "file_bytes_per_frame": [int(x) for x in lens_any.cpu()],
+           "bytes_equal": equal, "repeat_equal": repeat_equal}
+    k_us = pad_kernel_us()
+    if k_us is not None:
+        res["pad_kernel_us"] = k_us
+        res["pad_fraction_of_8TBps"] = moved / (k_us * 1e-6) / 8e12
+    return res
+
+
 GRAY_FILES = None                       # --gray-files=DIR
 
 
@@ -804,8 +925,8 @@ def main_gray(dst):
 
 
 def main():
-    global PARENT, GRAY_FILES
-    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size", "--gray")
+    global PARENT, GRAY_FILES, KERNEL_STATS
+    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size", "--gray", "--encode-any")
     for a in sys.argv[1:]:
         if a.startswith("--parent-lib="):
             # an older build has only the plain entry points: bind the one call that is timed
@@ -814,21 +935,24 @@ def main():
             PARENT.jpgx_pixels_gpu.argtypes = jpgx.lib.jpgx_pixels_gpu.argtypes
         if a.startswith("--gray-files="):
             GRAY_FILES = os.path.abspath(a.split("=", 1)[1])
-    args = [a for a in sys.argv[1:] if a not in modes and not a.startswith(("--parent-lib=", "--gray-files="))]
-    optimize, decoding, pixels, sub, any_size, gray = (m in sys.argv[1:] for m in modes)
+        if a.startswith("--kernel-stats="):
+            KERNEL_STATS = os.path.abspath(a.split("=", 1)[1])
+    args = [a for a in sys.argv[1:] if a not in modes and not a.startswith(("--parent-lib=", "--gray-files=", "--kernel-stats="))]
+    optimize, decoding, pixels, sub, any_size, gray, enc_any = (m in sys.argv[1:] for m in modes)
+    assert not enc_any or not (optimize or decoding or pixels or gray), "--encode-any stands alone"
     if gray:
         assert not (optimize or decoding or pixels), "--gray stands alone"
         return main_gray(args[0] if args else os.path.join(REPO, "profiles", "jfif_gpu_gray.json"))
     assert decoding or not sub, "--subinterval goes with --decode"
     assert pixels or not any_size, "--any-size goes with --pixels"
-    run = measure_px_any if any_size else measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
+    run = measure_enc_any if enc_any else measure_px_any if any_size else measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
         measure_opt if optimize else measure
     dst = args[0] if args else os.path.join(
-        REPO, "profiles", "jfif_gpu_px_any.json" if any_size else "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
+        REPO, "profiles", "jfif_gpu_enc_any.json" if enc_any else "jfif_gpu_px_any.json" if any_size else "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
         "jfif_gpu_dec.json" if decoding else "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py" + (" --pixels --any-size" if any_size else " --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --encode-any" if enc_any else " --pixels --any-size" if any_size else " --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
