@@ -18,6 +18,7 @@ import jpgx
 import jpgx.compat as C
 import san_build
 from conftest import GOLDEN, REPO
+from jfif_bits import category, walk
 from jfif_decode import decode
 from jfif_inputs import CASES, hand_made, stuffing_heavy          # the geometries of tests/test_jfif_gpu.py
 from jfif_inputs import lap as _lap, nblocks as _nblocks
@@ -158,46 +159,19 @@ def _host(coef, W, H, q, sr, rr, optimize=True, nthreads=1):
                            optimize=optimize)
 
 
-def _category(v):
-    return int(abs(int(v))).bit_length()
-
-
 def symbol_counts(coef, W, H, sr, rr):
     """[4][256]: DC luma, AC luma, DC chroma, AC chroma symbols of the scan, in MCU order with the
-    predictors reset at every interval of rr MCU rows (0: never) and the writer's clamps"""
-    hs, vs = (1, 2, 2)[sr], (1, 1, 2)[sr]
-    bpr = W // 8
-    nb, nbc = _nblocks(W, H, sr)
-    cpr, mrows = bpr // hs, H // 8 // vs
-    rows = mrows if rr == 0 else (1 if rr == -1 else rr)
+    predictors reset at every interval of rr MCU rows (0: never) and the writer's clamps; the walk is
+    tests/jfif_bits.py's"""
     cnt = np.zeros((4, 256), np.uint64)
-    pred = [0, 0, 0]
 
-    def block(z, comp):
+    def visit(iv, comp, row, step, diff, acs):
         t = 0 if comp == 0 else 2
-        d = max(-2047, min(2047, int(z[0]) - pred[comp]))
-        pred[comp] = int(z[0])
-        cnt[t, _category(d)] += 1
-        prev = 0
-        for k in np.nonzero(z[1:])[0] + 1:
-            run = int(k) - prev - 1
-            prev = int(k)
-            while run > 15:
-                cnt[t + 1, 0xf0] += 1
-                run -= 16
-            cnt[t + 1, run << 4 | _category(max(-1023, min(1023, int(z[k]))))] += 1
-        if prev < 63:
-            cnt[t + 1, 0] += 1
+        cnt[t, category(diff)] += 1
+        for sym, _ in acs:
+            cnt[t + 1, sym] += 1
 
-    for my in range(mrows):
-        if my % rows == 0:
-            pred = [0, 0, 0]
-        for mx in range(cpr):
-            for dy in range(vs):
-                for dx in range(hs):
-                    block(coef[(my * vs + dy) * bpr + mx * hs + dx], 0)
-            block(coef[nb + my * cpr + mx], 1)
-            block(coef[nb + nbc + my * cpr + mx], 2)
+    walk(coef, W, H, sr, rr, visit)
     return cnt
 
 
