@@ -5,14 +5,13 @@
  * those of jx_jfif_dec.h, the ones the device decoder (jpgx_jfif_dec.hip) runs; this file adds the
  * search for the restart markers and the threads.  No HIP: built with g++, as jpgx_plan.cpp.
  */
-#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 
 #include "../../include/jpgx_compat.h"
 #include "jx_jfif_dec.h"
 #include "jx_jfif_sub.h"
+#include "jx_par.h"
 
 namespace {
 
@@ -23,29 +22,27 @@ struct Job {
     const jxd_tab *tabs;
     const size_t *marks;                /* [ni - 1] the restart markers' places */
     int16_t *coef;
-    uint32_t iv0, iv1;                  /* this thread's intervals */
     int gray;                           /* the one-component frame */
-    int rc;
+    int rc[JX_PAR_MAX];                 /* per thread */
 };
 
 /* the header walk's modes (jx_jfif_dec.h) */
 enum { kPlain, kAny, kGray };
 
-void *run(void *arg)
+/* thread t's intervals (jx_par.h) */
+void run(void *ctx, uint32_t t, uint64_t iv0, uint64_t iv1)
 {
-    Job *j = (Job *)arg;
+    Job *j = (Job *)ctx;
     const jxd_frame *fr = j->fr;
-    j->rc = 0;
-    for (uint32_t iv = j->iv0; iv < j->iv1; iv++) {
+    for (uint32_t iv = (uint32_t)iv0; iv < (uint32_t)iv1; iv++) {
         const size_t begin = iv ? j->marks[iv - 1] + 2 : (size_t)fr->scan_off;
         const size_t end = iv + 1 < fr->ni ? j->marks[iv] : j->len - 2;
         const uint32_t mcu0 = iv * fr->mpi;
         const uint32_t count = fr->nmcu - mcu0 < fr->mpi ? fr->nmcu - mcu0 : fr->mpi;
         const int rc = j->gray ? jxd_decode_interval_gray(j->file, j->len, begin, end, fr, j->tabs, mcu0, count, j->coef)
                                : jxd_decode_interval(j->file, j->len, begin, end, fr, j->tabs, mcu0, count, j->coef);
-        if (rc) j->rc = JPGX_EJFIF_SCAN;
+        if (rc) j->rc[t] = JPGX_EJFIF_SCAN;
     }
-    return NULL;
 }
 
 void fill_info(const jxd_frame &fr, jpgx_jfif_info *info)
@@ -127,33 +124,10 @@ int read_jfif(int mode, const uint8_t *file, size_t len, int nthreads, int16_t *
     }
     rc = find_marks(file, len, &fr, marks);
     if (!rc) {
-        long ncpu = nthreads ? nthreads : sysconf(_SC_NPROCESSORS_ONLN);
-        if (ncpu < 1) ncpu = 1;
-        if (ncpu > 64) ncpu = 64;
-        uint32_t nt = (uint32_t)ncpu < fr.ni ? (uint32_t)ncpu : fr.ni;
-        Job jobs[64];
-        pthread_t th[64];
-        bool started[64];
-        for (uint32_t t = 0; t < nt; t++) {
-            Job &j = jobs[t];
-            j.file = file;
-            j.len = len;
-            j.fr = &fr;
-            j.tabs = tabs;
-            j.marks = marks;
-            j.coef = coef;
-            j.gray = mode == kGray;
-            j.iv0 = (uint32_t)((uint64_t)fr.ni * t / nt);
-            j.iv1 = (uint32_t)((uint64_t)fr.ni * (t + 1) / nt);
-            j.rc = 0;
-            /* the last run on this thread; a thread that does not start is run here as well */
-            started[t] = t + 1 < nt && pthread_create(&th[t], NULL, run, &j) == 0;
-            if (!started[t]) run(&j);
-        }
-        for (uint32_t t = 0; t < nt; t++) {
-            if (started[t]) pthread_join(th[t], NULL);
-            if (jobs[t].rc) rc = jobs[t].rc;
-        }
+        Job j = {file, len, &fr, tabs, marks, coef, mode == kGray, {0}};
+        jx_par_run(fr.ni, jx_thread_count(nthreads), run, &j);
+        for (uint32_t t = 0; t < JX_PAR_MAX; t++)
+            if (j.rc[t]) rc = j.rc[t];
     }
     free(marks);
     free(tabs);

@@ -6,10 +6,8 @@
  * adds the bit writer with its 0xFF stuffing, the restart-row policy and the threads.  Tables and
  * header bytes come from host/jpgx_jfif.c.  No HIP: built with g++, as jpgx_jfif_read.cpp.
  */
-#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 #ifdef __SSE2__
 #include <emmintrin.h>
 #endif
@@ -18,6 +16,7 @@
 #include "jpgx_internal.h"
 #include "jx_consts.h"
 #include "jx_jfif_enc.h"
+#include "jx_par.h"
 
 namespace {
 
@@ -196,31 +195,16 @@ void walk_intervals(const Scan *S, size_t i0, size_t i1, Sink sink)
 
 struct Job {
     const Scan *S;
-    size_t i0, i1;
     BW w;
     uint64_t (*cnt)[256];                                  /* non-NULL: count, do not code */
 };
 
-void *job_main(void *arg)
+/* job t of jobs[T]: restart intervals [t NI / T, (t + 1) NI / T) (jx_par.h) */
+void job_main(void *jobs, uint32_t t, uint64_t i0, uint64_t i1)
 {
-    Job *j = (Job *)arg;
-    if (j->cnt) walk_intervals(j->S, j->i0, j->i1, CountSink{j->cnt, NULL, NULL});
-    else walk_intervals(j->S, j->i0, j->i1, CodeSink{j->S, &j->w, NULL, NULL});
-    return NULL;
-}
-
-/* jobs 1 .. T - 1 on threads of their own, job 0 and whatever got no thread on the caller's */
-void run_jobs(Job *jobs, pthread_t *tid, long T)
-{
-    long nthr = T;
-    for (long t = 1; t < T; t++)
-        if (pthread_create(&tid[t], NULL, job_main, &jobs[t])) {
-            nthr = t;
-            break;
-        }
-    job_main(&jobs[0]);
-    for (long t = nthr; t < T; t++) job_main(&jobs[t]);
-    for (long t = 1; t < nthr; t++) pthread_join(tid[t], NULL);
+    Job *j = (Job *)jobs + t;
+    if (j->cnt) walk_intervals(j->S, (size_t)i0, (size_t)i1, CountSink{j->cnt, NULL, NULL});
+    else walk_intervals(j->S, (size_t)i0, (size_t)i1, CodeSink{j->S, &j->w, NULL, NULL});
 }
 
 /* jpgx_write_jfif_opt, and with `any` jpgx_write_jfif_any: the scan of the coded frame of a
@@ -240,12 +224,9 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
     if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
     S.coef = coef;
     const size_t mrows = S.g.cbh;
-    long T = nthreads;
-    if (T == 0) {
-        T = sysconf(_SC_NPROCESSORS_ONLN);
-        if (T < 1) T = 1;
-        if (T > 64) T = 64;
-    }
+    /* T enters the automatic restart interval below, so a file's bytes depend on it: a stated count is
+     * taken as it is, above 64 as well, and only the automatic one goes through jx_thread_count */
+    long T = nthreads ? nthreads : (long)jx_thread_count(0);
     /* restart interval: rows of MCUs, Ri = rows x MCUs per row (a 16-bit field) */
     const size_t maxrows = jx_frame_max_rows(&S.g);
     size_t rr = 0;
@@ -262,16 +243,11 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
     if ((size_t)T > S.nintervals) T = (long)S.nintervals;
     const int opt = (jfif_flags & JPGX_JFIF_OPTIMIZE) != 0;
 
-    /* thread t takes intervals [t NI / T, (t + 1) NI / T) */
+    /* a job per thread, T of them */
     Job *jobs = (Job *)calloc((size_t)T, sizeof(Job));
-    pthread_t *tid = (pthread_t *)calloc((size_t)T, sizeof(pthread_t));
     uint64_t (*cnt)[256] = opt ? (uint64_t (*)[256])calloc((size_t)T * 4, sizeof *cnt) : NULL;
-    rc = (jobs && tid && (cnt || !opt)) ? JPGX_OK : JPGX_ENOMEM;
-    for (long t = 0; t < T && !rc; t++) {
-        jobs[t].S = &S;
-        jobs[t].i0 = (size_t)t * S.nintervals / (size_t)T;
-        jobs[t].i1 = (size_t)(t + 1) * S.nintervals / (size_t)T;
-    }
+    rc = (jobs && (cnt || !opt)) ? JPGX_OK : JPGX_ENOMEM;
+    for (long t = 0; t < T && !rc; t++) jobs[t].S = &S;
 
     /* the tables: Annex K.3's, or Annex K.2's from the image's own symbols (each thread counts the
      * intervals it will code; integer sums, so the thread count does not show) */
@@ -279,7 +255,7 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
     uint8_t obits[4][16], ovals[4][256];
     if (opt && !rc) {
         for (long t = 0; t < T; t++) jobs[t].cnt = cnt + 4 * t;
-        run_jobs(jobs, tid, T);
+        jx_par_run(S.nintervals, (uint64_t)T, job_main, jobs);
         for (long t = 1; t < T; t++)
             for (int k = 0; k < 4; k++)
                 for (int s = 0; s < 256; s++) cnt[k][s] += cnt[4 * t + k][s];
@@ -306,7 +282,7 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
     }
 
     /* the scan: every thread codes into its own buffer */
-    if (!rc) run_jobs(jobs, tid, T);
+    if (!rc) jx_par_run(S.nintervals, (uint64_t)T, job_main, jobs);
     for (long t = 0; t < T && !rc; t++)
         if (jobs[t].w.oom) rc = JPGX_ENOMEM;
     if (!rc) {
@@ -325,7 +301,6 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
     if (jobs)
         for (long t = 0; t < T; t++) free(jobs[t].w.p);
     free(jobs);
-    free(tid);
     free(cnt);
     return rc;
 }

@@ -12,14 +12,13 @@
  * jpgx_pixels_host_gray (a one-component frame): one phase over block rows; a block's samples go
  * straight to the output, once per channel.
  */
-#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
-#include <unistd.h>
 
 #include "../../include/jpgx_compat.h"
 #include "jx_frame.h"
 #include "jx_idct.h"
+#include "jx_par.h"
 
 namespace {
 
@@ -33,12 +32,6 @@ struct Ctx {
     uint8_t *plane[3];              /* Y: 8 bh x 8 bw, Cb / Cr: 8 cbh x 8 cbw */
     uint8_t *rgb;
     size_t pitch;
-};
-
-struct Job {
-    const Ctx *c;
-    int phase;
-    uint32_t m0, m1;                /* MCU rows */
 };
 
 /* one block: dequantise, columns, rows, range limit */
@@ -114,33 +107,10 @@ void pixel_rows(const Ctx &c, uint32_t m0, uint32_t m1)
     }
 }
 
-void *run(void *arg)
-{
-    const Job *j = (const Job *)arg;
-    if (j->phase == 0) samples_rows(*j->c, j->m0, j->m1);
-    else pixel_rows(*j->c, j->m0, j->m1);
-    return NULL;
-}
+/* the two phases over a thread's MCU rows (jx_par.h) */
+void run_samples(void *c, uint32_t, uint64_t m0, uint64_t m1) { samples_rows(*(const Ctx *)c, (uint32_t)m0, (uint32_t)m1); }
 
-void run_phase(const Ctx &c, int phase, uint32_t nt)
-{
-    const uint32_t mrows = c.g.cbh;     /* MCU rows: a chroma block row each */
-    Job jobs[64];
-    pthread_t th[64];
-    bool started[64];
-    for (uint32_t t = 0; t < nt; t++) {
-        Job &j = jobs[t];
-        j.c = &c;
-        j.phase = phase;
-        j.m0 = (uint32_t)((uint64_t)mrows * t / nt);
-        j.m1 = (uint32_t)((uint64_t)mrows * (t + 1) / nt);
-        /* the last run on this thread; a thread that does not start is run here as well */
-        started[t] = t + 1 < nt && pthread_create(&th[t], NULL, run, &j) == 0;
-        if (!started[t]) run(&j);
-    }
-    for (uint32_t t = 0; t < nt; t++)
-        if (started[t]) pthread_join(th[t], NULL);
-}
+void run_pixels(void *c, uint32_t, uint64_t m0, uint64_t m1) { pixel_rows(*(const Ctx *)c, (uint32_t)m0, (uint32_t)m1); }
 
 int pixels_host(bool any, const int16_t *coef, int width, int height, int sample_ratio, const uint16_t qt[2][64],
                 uint8_t *rgb, size_t pitch, int nthreads)
@@ -168,12 +138,10 @@ int pixels_host(bool any, const int16_t *coef, int width, int height, int sample
     c.plane[2] = planes + ny + nc;
     c.rgb = rgb;
     c.pitch = pitch;
-    long ncpu = nthreads ? nthreads : sysconf(_SC_NPROCESSORS_ONLN);
-    if (ncpu < 1) ncpu = 1;
-    if (ncpu > 64) ncpu = 64;
-    const uint32_t nt = (uint32_t)ncpu < c.g.cbh ? (uint32_t)ncpu : c.g.cbh;
-    run_phase(c, 0, nt);            /* joined: every plane is whole before a pixel row reads its neighbours */
-    run_phase(c, 1, nt);
+    const uint32_t nt = jx_thread_count(nthreads);
+    /* over MCU rows, a chroma block row each; joined: every plane is whole before a pixel row reads its neighbours */
+    jx_par_run(c.g.cbh, nt, run_samples, &c);
+    jx_par_run(c.g.cbh, nt, run_pixels, &c);
     free(planes);
     return JPGX_OK;
 }
@@ -188,17 +156,12 @@ struct GrayCtx {
     uint32_t channels;
 };
 
-struct GrayJob {
-    const GrayCtx *c;
-    uint32_t r0, r1;                /* block rows */
-};
-
-void *run_gray(void *arg)
+/* a thread's block rows (jx_par.h) */
+void run_gray(void *ctx, uint32_t, uint64_t r0, uint64_t r1)
 {
-    const GrayJob *j = (const GrayJob *)arg;
-    const GrayCtx &c = *j->c;
+    const GrayCtx &c = *(const GrayCtx *)ctx;
     const uint32_t ch = c.channels;
-    for (uint32_t by = j->r0; by < j->r1; by++)
+    for (uint32_t by = (uint32_t)r0; by < (uint32_t)r1; by++)
         for (uint32_t bx = 0; bx < c.g.bw; bx++) {
             uint8_t s[64];
             block_samples(c.coef + ((size_t)by * c.g.bw + bx) * 64, c.qt, s, 8);
@@ -208,7 +171,6 @@ void *run_gray(void *arg)
                     for (uint32_t k = 0; k < ch; k++) row[(size_t)ch * x + k] = s[r * 8 + (x & 7u)];
             }
         }
-    return NULL;
 }
 
 int pixels_host_gray(const int16_t *coef, int width, int height, const uint16_t *qt, uint8_t *out, size_t pitch,
@@ -225,24 +187,7 @@ int pixels_host_gray(const int16_t *coef, int width, int height, const uint16_t 
     c.out = out;
     c.pitch = pitch;
     c.channels = (uint32_t)channels;
-    long ncpu = nthreads ? nthreads : sysconf(_SC_NPROCESSORS_ONLN);
-    if (ncpu < 1) ncpu = 1;
-    if (ncpu > 64) ncpu = 64;
-    const uint32_t nt = (uint32_t)ncpu < c.g.bh ? (uint32_t)ncpu : c.g.bh;
-    GrayJob jobs[64];
-    pthread_t th[64];
-    bool started[64];
-    for (uint32_t t = 0; t < nt; t++) {
-        GrayJob &j = jobs[t];
-        j.c = &c;
-        j.r0 = (uint32_t)((uint64_t)c.g.bh * t / nt);
-        j.r1 = (uint32_t)((uint64_t)c.g.bh * (t + 1) / nt);
-        /* the last run on this thread; a thread that does not start is run here as well */
-        started[t] = t + 1 < nt && pthread_create(&th[t], NULL, run_gray, &j) == 0;
-        if (!started[t]) run_gray(&j);
-    }
-    for (uint32_t t = 0; t < nt; t++)
-        if (started[t]) pthread_join(th[t], NULL);
+    jx_par_run(c.g.bh, jx_thread_count(nthreads), run_gray, &c);
     return JPGX_OK;
 }
 

@@ -367,6 +367,88 @@ def _frame(fn: str, width: int, height: int, sample_ratio: int, flags: int | Non
     return nb, nbc, per_frame, stride
 
 
+# ---- the argument rules of the device entry points, each written once; fn: the public function's name
+def _device_tensor(t, dtype=None, contiguous: bool = False) -> bool:
+    """t is a torch tensor on a GPU (of dtype; contiguous)"""
+    import torch
+    return (isinstance(t, torch.Tensor) and t.is_cuda and (dtype is None or t.dtype == dtype)
+            and (not contiguous or t.is_contiguous()))
+
+
+def _files_batch(fn: str, d_files, lens):
+    """(nf, cap, fstride) of a batch of files in device memory, d_files uint8 [nf][cap] and lens int64 [nf]:
+    bytes per file and bytes between files.  Files that overlap, a stride below cap, are the caller's to
+    refuse: a bad geometry is reported before them."""
+    import torch
+    for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
+        if not _device_tensor(t):
+            raise ValueError(f"{fn}: {name} must be a device tensor")
+        if t.dtype != dt:
+            raise ValueError(f"{fn}: {name} must be {dt}")
+    if d_files.dim() != 2 or lens.dim() != 1 or lens.shape[0] != d_files.shape[0] or d_files.shape[0] == 0:
+        raise ValueError(f"{fn}: d_files [nframes][cap] and lens [nframes]")
+    if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
+        raise ValueError(f"{fn}: each file must be contiguous")
+    nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
+    return nf, cap, int(d_files.stride(0)) if nf > 1 else cap
+
+
+def _qt_stride(fn: str, d_qt, nf: int, size: int) -> int:
+    """uint16 elements between the frames' tables of `size` (128: [2][64], 64: [64]); 0: one for the batch"""
+    if d_qt.numel() not in (size, size * nf):
+        one = "[2][64]" if size == 128 else "[64]"
+        raise ValueError(f"{fn}: d_qt must be {one} or [nframes]{one}")
+    return 0 if d_qt.numel() == size else size
+
+
+def _status_arg(fn: str, status, nf: int):
+    """the pointer a pixel entry point takes for `status`, int32 [nf] or None"""
+    import torch
+    if status is None:
+        return None
+    if (not isinstance(status, torch.Tensor) or status.dtype != torch.int32 or status.numel() != nf
+            or not status.is_contiguous()):
+        raise ValueError(f"{fn}: status must be a contiguous int32 [nframes] tensor")
+    return status.data_ptr()
+
+
+def _pitch_out(fn: str, pitch, out, nf: int, width: int, height: int, bpp: int, bpp_name: str, packed: bool, dev):
+    """(pitch, out) of a pixel entry point: bytes between pixel rows, a multiple of 8 and at least
+    bpp * width (bpp_name in the refusal), by default that many (packed) or that rounded up to 8; out, the
+    caller's buffer of nf * height * pitch bytes or a fresh one on dev"""
+    import torch
+    if pitch is None:
+        pitch = bpp * width if packed else (bpp * width + 7) // 8 * 8
+    pitch = int(pitch)
+    if pitch < bpp * width or pitch % 8:
+        raise ValueError(f"{fn}: pitch must be a multiple of 8 and at least {bpp_name} * width")
+    if out is None:
+        out = torch.empty(nf * height * pitch, dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
+          or out.numel() != nf * height * pitch):
+        raise ValueError(f"{fn}: out must be a contiguous uint8 buffer of nframes * H * pitch bytes")
+    return pitch, out
+
+
+def _workspace(need: int, dev, stream=None):
+    """an entry point's own workspace of `need` bytes, kept until `stream` is past it"""
+    import torch
+    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if stream is not None:
+        ws.record_stream(stream)
+    return ws
+
+
+def _upload_files(files, dev):
+    """host files -> (d_files uint8 [n][cap], lens int64 [n]) on dev; cap: the longest file's length"""
+    import torch
+    cap = max(len(f) for f in files)
+    host = np.zeros((len(files), cap), np.uint8)
+    for k, f in enumerate(files):
+        host[k, :len(f)] = np.frombuffer(f, np.uint8)
+    return torch.from_numpy(host).to(dev), torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
+
+
 def entropy_stats_gpu(d_coef, nb_y: int, nb_c: int, carry=None, stream=None):
     """(dc int32 [nb_y + 2 nb_c], hist uint32 [4][257]) device tensors: the reference's dpcm and
     huffman_encode frequency pass over d_coef (torch int16 tensor, Y|Cb|Cr blocks)."""
@@ -426,7 +508,7 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     file's own, any 1 .. 65535, d_coef holds the coded frames (encode_blocks(any_size=True)); byte for
     byte compat.write_jfif_ex(..., any_size=True)."""
     import torch
-    if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda:
+    if not _device_tensor(d_coef):
         raise ValueError("jfif_gpu: d_coef must be a device tensor")
     if d_coef.dtype != torch.int16 or d_coef.dim() < 2:
         raise ValueError("jfif_gpu: d_coef must be an int16 [nframes][...] tensor")
@@ -442,7 +524,7 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
         out = torch.empty((nf, cap), dtype=torch.uint8, device=dev)
         lens = torch.empty(nf, dtype=torch.int64, device=dev)
         need = int(size_fn(width, height, sample_ratio, restart_rows, nf, cap, jflags))
-        ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        ws = _workspace(need, dev)          # synchronised below: nothing to keep it for
         _check(code_fn(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
                        restart_rows, jflags, out.data_ptr(), cap, cap, lens.data_ptr(),
                        ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
@@ -464,7 +546,7 @@ def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restar
     sampling (pad_edge; the forward path gets the file's ratio, 0 without FLAG_SUBSAMPLE, so that both
     agree on the MCU); decode_jpeg(..., any_size=True) reads it back."""
     import torch
-    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+    if not _device_tensor(rgb):
         raise ValueError("encode_jpeg: rgb must be a device tensor")
     H, W = int(rgb.shape[0]), int(rgb.shape[1])
     sub = sample_ratio if flags & FLAG_SUBSAMPLE else 0
@@ -499,36 +581,8 @@ def jfif_decode_gpu(d_files, lens, width: int, height: int, sample_ratio: int = 
     DESIGN.md 4.8a): the same outputs, faster where intervals are long or few.  any_size:
     jpgx_jfif_decode_gpu_any -- width and height are the files' own, any 1 .. 65535, and nb, nbc are
     the coded frame's (coded_size); statuses and coefficients are compat.read_jfif(any_size=True)'s."""
-    import torch
-    for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"jfif_decode_gpu: {name} must be a device tensor")
-        if t.dtype != dt:
-            raise ValueError(f"jfif_decode_gpu: {name} must be {dt}")
-    if d_files.dim() != 2 or lens.dim() != 1 or lens.shape[0] != d_files.shape[0] or d_files.shape[0] == 0:
-        raise ValueError("jfif_decode_gpu: d_files [nframes][cap] and lens [nframes]")
-    if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
-        raise ValueError("jfif_decode_gpu: each file must be contiguous")
-    nb, nbc, _, _ = _frame("jfif_decode_gpu", width, height, sample_ratio, any_size=any_size)
-    size_fn = lib.jpgx_jfif_decode_gpu_any_workspace_size if any_size else lib.jpgx_jfif_decode_gpu_workspace_size_ex
-    decode_fn = lib.jpgx_jfif_decode_gpu_any if any_size else lib.jpgx_jfif_decode_gpu_ex
-    nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
-    fstride = int(d_files.stride(0)) if nf > 1 else cap
-    if fstride < cap:
-        raise ValueError("jfif_decode_gpu: overlapping files")
-    dev = d_files.device
-    coef = torch.empty((nf, nb + 2 * nbc, 64), dtype=torch.int16, device=dev)
-    qt = torch.empty((nf, 2, 64), dtype=torch.uint16, device=dev)
-    status = torch.empty(nf, dtype=torch.int32, device=dev)
-    dflags = JFIF_DECODE_SUBINTERVAL if subinterval else 0
-    need = int(size_fn(width, height, sample_ratio, nf, fstride, dflags))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    _check(decode_fn(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, sample_ratio,
-                     dflags, coef.data_ptr(), (nb + 2 * nbc) * 64, qt.data_ptr(), status.data_ptr(),
-                     ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu")
-    if stream is not None:
-        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
-    return coef, qt, status
+    return _jfif_decode("jfif_decode_gpu", d_files, lens, width, height, stream, subinterval,
+                        sample_ratio=sample_ratio, any_size=any_size)
 
 
 def _gray_blocks(fn: str, width: int, height: int) -> int:
@@ -545,44 +599,34 @@ def jfif_decode_gpu_gray(d_files, lens, width: int, height: int, stream=None, su
     [nframes][64], status int32 [nframes]), all on the device; status[f], the coefficients and the table
     are compat.read_jfif_gray's for the same bytes, and a three-component file has EJFIF_HEADER.
     Nothing is copied to the host and nothing waits.  subinterval: as jfif_decode_gpu's."""
+    return _jfif_decode("jfif_decode_gpu_gray", d_files, lens, width, height, stream, subinterval, gray=True)
+
+
+def _jfif_decode(fn: str, d_files, lens, width, height, stream, subinterval, sample_ratio: int = 0,
+                 any_size: bool = False, gray: bool = False):
+    """jfif_decode_gpu and, with gray, jfif_decode_gpu_gray: the library's call takes the frame's geometry as
+    (width, height, sample_ratio), a one-component frame's as (width, height)"""
     import torch
-    for name, t, dt in (("d_files", d_files, torch.uint8), ("lens", lens, torch.int64)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ValueError(f"jfif_decode_gpu_gray: {name} must be a device tensor")
-        if t.dtype != dt:
-            raise ValueError(f"jfif_decode_gpu_gray: {name} must be {dt}")
-    if d_files.dim() != 2 or lens.dim() != 1 or lens.shape[0] != d_files.shape[0] or d_files.shape[0] == 0:
-        raise ValueError("jfif_decode_gpu_gray: d_files [nframes][cap] and lens [nframes]")
-    if d_files.stride(1) != 1 or not lens.is_contiguous() or d_files.shape[1] == 0:
-        raise ValueError("jfif_decode_gpu_gray: each file must be contiguous")
-    nb = _gray_blocks("jfif_decode_gpu_gray", width, height)
-    nf, cap = int(d_files.shape[0]), int(d_files.shape[1])
-    fstride = int(d_files.stride(0)) if nf > 1 else cap
+    nf, cap, fstride = _files_batch(fn, d_files, lens)
+    if gray:
+        nblk, geometry = _gray_blocks(fn, width, height), (width, height)
+        size_fn, decode_fn = lib.jpgx_jfif_decode_gpu_gray_workspace_size, lib.jpgx_jfif_decode_gpu_gray
+    else:
+        nb, nbc, _, _ = _frame(fn, width, height, sample_ratio, any_size=any_size)
+        nblk, geometry = nb + 2 * nbc, (width, height, sample_ratio)
+        size_fn = lib.jpgx_jfif_decode_gpu_any_workspace_size if any_size else lib.jpgx_jfif_decode_gpu_workspace_size_ex
+        decode_fn = lib.jpgx_jfif_decode_gpu_any if any_size else lib.jpgx_jfif_decode_gpu_ex
     if fstride < cap:
-        raise ValueError("jfif_decode_gpu_gray: overlapping files")
+        raise ValueError(f"{fn}: overlapping files")
     dev = d_files.device
-    coef = torch.empty((nf, nb, 64), dtype=torch.int16, device=dev)
-    qt = torch.empty((nf, 64), dtype=torch.uint16, device=dev)
+    coef = torch.empty((nf, nblk, 64), dtype=torch.int16, device=dev)
+    qt = torch.empty((nf, 64) if gray else (nf, 2, 64), dtype=torch.uint16, device=dev)
     status = torch.empty(nf, dtype=torch.int32, device=dev)
     dflags = JFIF_DECODE_SUBINTERVAL if subinterval else 0
-    need = int(lib.jpgx_jfif_decode_gpu_gray_workspace_size(width, height, nf, fstride, dflags))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    _check(lib.jpgx_jfif_decode_gpu_gray(d_files.data_ptr(), fstride, lens.data_ptr(), nf, width, height, dflags,
-                                         coef.data_ptr(), nb * 64, qt.data_ptr(), status.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_decode_gpu_gray")
-    if stream is not None:
-        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
+    ws = _workspace(int(size_fn(*geometry, nf, fstride, dflags)), dev, stream)
+    _check(decode_fn(d_files.data_ptr(), fstride, lens.data_ptr(), nf, *geometry, dflags, coef.data_ptr(), nblk * 64,
+                     qt.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_" + fn)
     return coef, qt, status
-
-
-def _upload_files(files, dev):
-    """host files -> (d_files uint8 [n][cap], lens int64 [n]) on dev"""
-    import torch
-    cap = max(len(f) for f in files)
-    host = np.zeros((len(files), cap), np.uint8)
-    for k, f in enumerate(files):
-        host[k, :len(f)] = np.frombuffer(f, np.uint8)
-    return torch.from_numpy(host).to(dev), torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
 
 
 def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False, any_size: bool = False,
@@ -596,27 +640,30 @@ def decode_jpeg_coefficients(data: bytes, device, subinterval: bool = False, any
     width and height the file's).  gray: the file is a one-component one of any size
     (jfif_decode_gpu_gray): coef [nb][64], qt [64], sample_ratio 0, restart_interval in blocks."""
     import torch
-    from . import compat
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("decode_jpeg_coefficients: device must be a GPU")
-    if gray:
-        info = compat.jfif_info_gray(data)
-        d_files, lens = _upload_files([bytes(data)], dev)
-        coef, qt, status = jfif_decode_gpu_gray(d_files, lens, info["width"], info["height"], subinterval=subinterval)
-        _check(int(status[0]), "jpgx_jfif_decode_gpu_gray")
-        return dict(coef=coef[0], qt=qt[0], width=info["width"], height=info["height"], sample_ratio=0,
-                    restart_interval=info["restart_interval"])
-    info = compat.jfif_info(data, any_size=any_size)
-    host = torch.frombuffer(bytearray(data), dtype=torch.uint8)
-    d_files = host.to(dev).reshape(1, -1)
-    lens = torch.tensor([len(data)], dtype=torch.int64, device=dev)
-    coef, qt, status = jfif_decode_gpu(d_files, lens, info["width"], info["height"], info["sample_ratio"],
-                                       subinterval=subinterval, any_size=any_size)
-    _check(int(status[0]), "jpgx_jfif_decode_gpu")
-    out = coef[0].reshape(3, -1, 64) if info["sample_ratio"] == 0 else coef[0]
+    info, geometry, decode, _, what = _decode_path(data, subinterval, any_size, gray)
+    d_files, lens = _upload_files([bytes(data)], dev)
+    coef, qt, status = decode(d_files, lens, *geometry)
+    _check(int(status[0]), what)
+    out = coef[0].reshape(3, -1, 64) if info["sample_ratio"] == 0 and not gray else coef[0]
     return dict(coef=out, qt=qt[0], width=info["width"], height=info["height"],
                 sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
+
+
+def _decode_path(data, subinterval: bool, any_size: bool, gray: bool):
+    """decode_jpeg's and decode_jpeg_coefficients' way for their kind of file: (data's header as a dict; the
+    geometry the next two take after their tensors; the decoder; the pixel call; a nonzero status' name)"""
+    from functools import partial
+    from . import compat
+    info = compat.jfif_info_gray(data) if gray else compat.jfif_info(data, any_size=any_size)
+    if gray:
+        return (info, (info["width"], info["height"]), partial(jfif_decode_gpu_gray, subinterval=subinterval),
+                pixels_gpu_gray, "jpgx_jfif_decode_gpu_gray")
+    return (info, (info["width"], info["height"], info["sample_ratio"]),
+            partial(jfif_decode_gpu, subinterval=subinterval, any_size=any_size), partial(pixels_gpu, any_size=any_size),
+            "jpgx_jfif_decode_gpu")
 
 
 def jfif_qt(quality: int) -> np.ndarray:
@@ -639,44 +686,8 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     and nothing waits.  any_size: jpgx_pixels_gpu_any -- d_coef holds the coded frame's coefficients
     (jfif_decode_gpu(any_size=True)), width and height are the visible frame's, any 1 .. 65535; the
     default pitch is 3 W rounded up to 8, and only bytes [0, 3 W) of the H rows are written."""
-    import torch
-    if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda or d_coef.dtype != torch.int16 or d_coef.dim() < 2:
-        raise ValueError("pixels_gpu: d_coef must be an int16 [nframes][...] device tensor")
-    if not isinstance(d_qt, torch.Tensor) or not d_qt.is_cuda or d_qt.dtype != torch.uint16 or not d_qt.is_contiguous():
-        raise ValueError("pixels_gpu: d_qt must be a contiguous uint16 device tensor")
-    nf = int(d_coef.shape[0])
-    _, _, _, cstride = _frame("pixels_gpu", width, height, sample_ratio, d_coef=d_coef, any_size=any_size)
-    size_fn = lib.jpgx_pixels_gpu_any_workspace_size if any_size else lib.jpgx_pixels_gpu_workspace_size
-    pixels_fn = lib.jpgx_pixels_gpu_any if any_size else lib.jpgx_pixels_gpu
-    if d_qt.numel() == 128:
-        qstride = 0
-    elif d_qt.numel() == 128 * nf:
-        qstride = 128
-    else:
-        raise ValueError("pixels_gpu: d_qt must be [2][64] or [nframes][2][64]")
-    if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.int32
-                               or status.numel() != nf or not status.is_contiguous()):
-        raise ValueError("pixels_gpu: status must be a contiguous int32 [nframes] tensor")
-    if pitch is None:
-        pitch = (3 * width + 7) // 8 * 8 if any_size else 3 * width
-    pitch = int(pitch)
-    if pitch < 3 * width or pitch % 8:
-        raise ValueError("pixels_gpu: pitch must be a multiple of 8 and at least 3 * width")
-    dev = d_coef.device
-    if out is None:
-        out = torch.empty(nf * height * pitch, dtype=torch.uint8, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
-          or out.numel() != nf * height * pitch):
-        raise ValueError("pixels_gpu: out must be a contiguous uint8 buffer of nframes * H * pitch bytes")
-    need = int(size_fn(width, height, sample_ratio, nf))
-    ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    _check(pixels_fn(d_coef.data_ptr(), cstride, nf, width, height, sample_ratio, d_qt.data_ptr(), qstride,
-                               status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
-                               height * pitch, ws.data_ptr() if need else None, need, _stream_ptr(stream)),
-           "jpgx_pixels_gpu")
-    if stream is not None:
-        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
-    return out.view(nf, height, pitch)[:, :, :3 * width].unflatten(2, (width, 3))
+    return _pixels("pixels_gpu", d_coef, width, height, d_qt, status, out, pitch, stream, sample_ratio=sample_ratio,
+                   any_size=any_size)
 
 
 def pixels_gpu_gray(d_coef, width: int, height: int, d_qt, status=None, channels: int = 1, out=None,
@@ -687,40 +698,48 @@ def pixels_gpu_gray(d_coef, width: int, height: int, d_qt, status=None, channels
     (channels 1) or [nframes][H][W][3] (channels 3, R = G = B) on the device: libjpeg's default
     decoder's pixels.  pitch (bytes between pixel rows, a multiple of 8, at least channels * W; default:
     channels * W rounded up to 8) and out as pixels_gpu's.  Nothing is copied to the host and nothing waits."""
+    return _pixels("pixels_gpu_gray", d_coef, width, height, d_qt, status, out, pitch, stream, channels=channels)
+
+
+def _pixels(fn: str, d_coef, width, height, d_qt, status, out, pitch, stream, sample_ratio: int = 0,
+            any_size: bool = False, channels: int | None = None):
+    """pixels_gpu and, with channels, pixels_gpu_gray: a pixel is 3 bytes or `channels`, a frame holds
+    _frame's blocks or _gray_blocks', its tables are 128 elements or 64, and only pixels_gpu on whole MCUs
+    packs its rows by default"""
     import torch
-    if not isinstance(d_coef, torch.Tensor) or not d_coef.is_cuda or d_coef.dtype != torch.int16 or d_coef.dim() < 2:
-        raise ValueError("pixels_gpu_gray: d_coef must be an int16 [nframes][...] device tensor")
-    if not isinstance(d_qt, torch.Tensor) or not d_qt.is_cuda or d_qt.dtype != torch.uint16 or not d_qt.is_contiguous():
-        raise ValueError("pixels_gpu_gray: d_qt must be a contiguous uint16 device tensor")
-    if channels not in (1, 3):
-        raise ValueError("pixels_gpu_gray: channels must be 1 or 3")
+    gray = channels is not None
+    if not _device_tensor(d_coef, torch.int16) or d_coef.dim() < 2:
+        raise ValueError(f"{fn}: d_coef must be an int16 [nframes][...] device tensor")
+    if not _device_tensor(d_qt, torch.uint16, contiguous=True):
+        raise ValueError(f"{fn}: d_qt must be a contiguous uint16 device tensor")
+    if gray and channels not in (1, 3):
+        raise ValueError(f"{fn}: channels must be 1 or 3")
     nf = int(d_coef.shape[0])
-    nb = _gray_blocks("pixels_gpu_gray", width, height)
-    if not d_coef[0].is_contiguous() or d_coef[0].numel() < nb * 64:
-        raise ValueError("pixels_gpu_gray: each frame must be contiguous and hold nb blocks")
-    cstride = int(d_coef.stride(0)) if nf > 1 else int(d_coef[0].numel())
-    if d_qt.numel() == 64:
-        qstride = 0
-    elif d_qt.numel() == 64 * nf:
-        qstride = 64
+    if gray:
+        nb = _gray_blocks(fn, width, height)
+        if not d_coef[0].is_contiguous() or d_coef[0].numel() < nb * 64:
+            raise ValueError(f"{fn}: each frame must be contiguous and hold nb blocks")
+        cstride = int(d_coef.stride(0)) if nf > 1 else int(d_coef[0].numel())
     else:
-        raise ValueError("pixels_gpu_gray: d_qt must be [64] or [nframes][64]")
-    if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.int32
-                               or status.numel() != nf or not status.is_contiguous()):
-        raise ValueError("pixels_gpu_gray: status must be a contiguous int32 [nframes] tensor")
-    pitch = (channels * width + 7) // 8 * 8 if pitch is None else int(pitch)
-    if pitch < channels * width or pitch % 8:
-        raise ValueError("pixels_gpu_gray: pitch must be a multiple of 8 and at least channels * width")
-    if out is None:
-        out = torch.empty(nf * height * pitch, dtype=torch.uint8, device=d_coef.device)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_contiguous()
-          or out.numel() != nf * height * pitch):
-        raise ValueError("pixels_gpu_gray: out must be a contiguous uint8 buffer of nframes * H * pitch bytes")
-    _check(lib.jpgx_pixels_gpu_gray(d_coef.data_ptr(), cstride, nf, width, height, d_qt.data_ptr(), qstride,
-                                    status.data_ptr() if status is not None else None, out.data_ptr(), pitch,
-                                    height * pitch, channels, _stream_ptr(stream)), "jpgx_pixels_gpu_gray")
-    px = out.view(nf, height, pitch)[:, :, :channels * width]
-    return px if channels == 1 else px.unflatten(2, (width, 3))
+        _, _, _, cstride = _frame(fn, width, height, sample_ratio, d_coef=d_coef, any_size=any_size)
+    qstride = _qt_stride(fn, d_qt, nf, 64 if gray else 128)
+    d_status = _status_arg(fn, status, nf)
+    bpp = channels if gray else 3
+    pitch, out = _pitch_out(fn, pitch, out, nf, width, height, bpp, "channels" if gray else "3",
+                            packed=not (gray or any_size), dev=d_coef.device)
+    if gray:
+        rc = lib.jpgx_pixels_gpu_gray(d_coef.data_ptr(), cstride, nf, width, height, d_qt.data_ptr(), qstride, d_status,
+                                      out.data_ptr(), pitch, height * pitch, channels, _stream_ptr(stream))
+    else:
+        size_fn = lib.jpgx_pixels_gpu_any_workspace_size if any_size else lib.jpgx_pixels_gpu_workspace_size
+        pixels_fn = lib.jpgx_pixels_gpu_any if any_size else lib.jpgx_pixels_gpu
+        need = int(size_fn(width, height, sample_ratio, nf))
+        ws = _workspace(need, d_coef.device, stream)
+        rc = pixels_fn(d_coef.data_ptr(), cstride, nf, width, height, sample_ratio, d_qt.data_ptr(), qstride, d_status,
+                       out.data_ptr(), pitch, height * pitch, ws.data_ptr() if need else None, need, _stream_ptr(stream))
+    _check(rc, "jpgx_" + fn)
+    px = out.view(nf, height, pitch)[:, :, :bpp * width]
+    return px if bpp == 1 else px.unflatten(2, (width, 3))
 
 
 def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False, gray: bool = False):
@@ -735,7 +754,6 @@ def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False,
     one-component files of any size (jfif_decode_gpu_gray, pixels_gpu_gray): uint8 [H][W], or
     [n][H][W] for a list; the default refuses such files."""
     import torch
-    from . import compat
     single = isinstance(data, (bytes, bytearray, memoryview))
     files = [bytes(data)] if single else [bytes(d) for d in data]
     if not files:
@@ -743,27 +761,13 @@ def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False,
     dev = torch.device(device)
     if dev.type != "cuda":
         raise ValueError("decode_jpeg: device must be a GPU")
-    if gray:
-        info = compat.jfif_info_gray(files[0])
-        d_files, lens = _upload_files(files, dev)
-        coef, qt, status = jfif_decode_gpu_gray(d_files, lens, info["width"], info["height"], subinterval=subinterval)
-        px = pixels_gpu_gray(coef, info["width"], info["height"], qt, status=status)
-        for rc in status.cpu().tolist():
-            _check(int(rc), "jpgx_jfif_decode_gpu_gray")
-        return px[0] if single else px
-    info = compat.jfif_info(files[0], any_size=any_size)
-    W, H, sr = info["width"], info["height"], info["sample_ratio"]
-    cap = max(len(f) for f in files)
-    host = np.zeros((len(files), cap), np.uint8)
-    for k, f in enumerate(files):
-        host[k, :len(f)] = np.frombuffer(f, np.uint8)
-    d_files = torch.from_numpy(host).to(dev)
-    lens = torch.tensor([len(f) for f in files], dtype=torch.int64, device=dev)
-    coef, qt, status = jfif_decode_gpu(d_files, lens, W, H, sr, subinterval=subinterval, any_size=any_size)
-    rgb = pixels_gpu(coef, W, H, sr, d_qt=qt, status=status, any_size=any_size)
+    _, geometry, decode, pixels, what = _decode_path(files[0], subinterval, any_size, gray)
+    d_files, lens = _upload_files(files, dev)
+    coef, qt, status = decode(d_files, lens, *geometry)
+    px = pixels(coef, *geometry, d_qt=qt, status=status)
     for rc in status.cpu().tolist():
-        _check(int(rc), "jpgx_jfif_decode_gpu")
-    return rgb[0] if single else rgb
+        _check(int(rc), what)
+    return px[0] if single else px
 
 
 def split_sub(out, nb: int, nbc: int):
@@ -825,7 +829,7 @@ def _encode_blocks_any(rgb, W, H, quality, sample_ratio, underflow, flags, devic
         return encode_blocks(pad_edge(np.ascontiguousarray(rgb, np.uint8), sample_ratio), quality, sample_ratio,
                              underflow, flags, device)
     import torch
-    if not isinstance(rgb, torch.Tensor) or not rgb.is_cuda:
+    if not _device_tensor(rgb):
         raise ValueError("encode_blocks: rgb must be a numpy array or a device tensor")
     if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3:
         raise ValueError("encode_blocks: rgb must be (H, W, 3) uint8")
@@ -840,11 +844,9 @@ def _encode_blocks_any(rgb, W, H, quality, sample_ratio, underflow, flags, devic
     need = int(lib.jpgx_workspace_size_any(ctypes.byref(fr), ctypes.byref(p)))
     if not need:                                    # the refusal, by its code
         _check(lib.jpgx_blocks_gpu_any(ctypes.byref(fr), ctypes.byref(p), None, None, None, 0, None), "jpgx_blocks_gpu_any")
-    ws = torch.empty(need, dtype=torch.uint8, device=rgb.device)
+    ws = _workspace(need, rgb.device, stream)
     _check(lib.jpgx_blocks_gpu_any(ctypes.byref(fr), ctypes.byref(p), rgb.data_ptr(), out.data_ptr(),
                                    ws.data_ptr(), need, _stream_ptr(stream)), "jpgx_blocks_gpu_any")
-    if stream is not None:
-        ws.record_stream(stream)        # the workspace is this function's own: keep it until the stream is past it
     return out
 
 

@@ -313,11 +313,40 @@ def jfif_info(data, any_size: bool = False) -> dict:
     """jpgx_jfif_info_of: the header walk of a baseline JFIF file (bytes) -> width, height,
     sample_ratio, restart_interval, scan_offset, nb_y, nb_c.  JpgxError(EJFIF_HEADER) when refused.
     any_size: jpgx_jfif_info_of_any -- any width and height; nb_y and nb_c are the coded frame's."""
+    return _jfif_info(lib.jpgx_jfif_info_of_any if any_size else lib.jpgx_jfif_info_of, data)
+
+
+def _what(lib_fn) -> str:
+    """the name a call's failure is reported under: an _any entry point's is its plain sibling's"""
+    return lib_fn.__name__.replace("_any", "")
+
+
+def _jfif_info(lib_fn, data) -> dict:
+    """jfif_info and jfif_info_gray: one of the library's header walks over data"""
     buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
     info = JfifInfo()
-    fn = lib.jpgx_jfif_info_of_any if any_size else lib.jpgx_jfif_info_of
-    _check(fn(buf.ctypes.data, len(data), ctypes.byref(info)), "jpgx_jfif_info_of")
+    _check(lib_fn(buf.ctypes.data, len(data), ctypes.byref(info)), _what(lib_fn))
     return _info_dict(info)
+
+
+def _read_jfif(lib_fn, data, info: dict, qt_shape, nthreads: int = 1, sub_args=None) -> dict:
+    """The four readers: one of the library's readers over data, a file of `info`, into fresh buffers.
+    sub_args: (sub_bytes, tile_subs) of a twin of the device decoder, which takes them where a reader
+    takes nthreads and counts into `stats`."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    coef = np.empty((info["nb_y"] + 2 * info["nb_c"], 64), np.int16)
+    qt = np.zeros(qt_shape, np.uint16)
+    got, stats = JfifInfo(), JfifSubStats()
+    how, tail = ((nthreads,), ()) if sub_args is None else (sub_args, (ctypes.byref(stats),))
+    _check(lib_fn(buf.ctypes.data, len(buf), *how, coef.ctypes.data, coef.size, qt.ctypes.data, ctypes.byref(got),
+                  *tail), _what(lib_fn))
+    if info["sample_ratio"] == 0 and info["nb_c"]:          # 4:4:4: three planes of nb blocks
+        coef = coef.reshape(3, info["nb_y"], 64)
+    out = dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
+               sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
+    if sub_args is not None:
+        out["stats"] = {n: int(getattr(stats, n)) for n, _ in JfifSubStats._fields_}
+    return out
 
 
 def read_jfif(data, nthreads: int = 1, any_size: bool = False) -> dict:
@@ -327,18 +356,8 @@ def read_jfif(data, nthreads: int = 1, any_size: bool = False) -> dict:
     order).  The restart intervals are decoded on `nthreads` threads (0: one per CPU).
     JpgxError(EJFIF_HEADER / EJFIF_SCAN) when the file is refused.  any_size: jpgx_read_jfif_any --
     a file of any width and height; width and height are the file's, coef the coded frame's."""
-    info = jfif_info(data, any_size)
-    buf = np.frombuffer(bytes(data), np.uint8)
-    nblk = info["nb_y"] + 2 * info["nb_c"]
-    coef = np.empty((nblk, 64), np.int16)
-    qt = np.zeros((2, 64), np.uint16)
-    got = JfifInfo()
-    _check((lib.jpgx_read_jfif_any if any_size else lib.jpgx_read_jfif)(buf.ctypes.data, len(buf), nthreads, coef.ctypes.data, coef.size,
-                              qt.ctypes.data, ctypes.byref(got)), "jpgx_read_jfif")
-    if info["sample_ratio"] == 0:
-        coef = coef.reshape(3, info["nb_y"], 64)
-    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
-                sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"])
+    return _read_jfif(lib.jpgx_read_jfif_any if any_size else lib.jpgx_read_jfif, data, jfif_info(data, any_size),
+                      (2, 64), nthreads)
 
 
 class JfifSubStats(ctypes.Structure):
@@ -352,19 +371,8 @@ def read_jfif_sub(data, sub_bytes: int = 0, tile_subs: int = 0, any_size: bool =
     interval, subsequences of sub_bytes bytes and tiles of tile_subs subsequences
     (0, 0: the kernel's shape).  read_jfif's dict and `stats`, a dict of the twin's counters.
     any_size: jpgx_read_jfif_sub_any, as read_jfif's."""
-    info = jfif_info(data, any_size)
-    buf = np.frombuffer(bytes(data), np.uint8)
-    nblk = info["nb_y"] + 2 * info["nb_c"]
-    coef = np.empty((nblk, 64), np.int16)
-    qt = np.zeros((2, 64), np.uint16)
-    got, stats = JfifInfo(), JfifSubStats()
-    _check((lib.jpgx_read_jfif_sub_any if any_size else lib.jpgx_read_jfif_sub)(buf.ctypes.data, len(buf), sub_bytes, tile_subs, coef.ctypes.data, coef.size,
-                                  qt.ctypes.data, ctypes.byref(got), ctypes.byref(stats)), "jpgx_read_jfif_sub")
-    if info["sample_ratio"] == 0:
-        coef = coef.reshape(3, info["nb_y"], 64)
-    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"],
-                sample_ratio=info["sample_ratio"], restart_interval=info["restart_interval"],
-                stats={n: int(getattr(stats, n)) for n, _ in JfifSubStats._fields_})
+    return _read_jfif(lib.jpgx_read_jfif_sub_any if any_size else lib.jpgx_read_jfif_sub, data, jfif_info(data, any_size),
+                      (2, 64), sub_args=(sub_bytes, tile_subs))
 
 
 def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt: np.ndarray,
@@ -392,39 +400,19 @@ def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt
 def jfif_info_gray(data) -> dict:
     """jpgx_jfif_info_of_gray: jfif_info for a one-component (grayscale) file of any width and height:
     sample_ratio 0, nb_y = ceil(W / 8) * ceil(H / 8), nb_c 0, restart_interval in blocks."""
-    buf = np.frombuffer(bytes(data) or b"\0", np.uint8)
-    info = JfifInfo()
-    _check(lib.jpgx_jfif_info_of_gray(buf.ctypes.data, len(data), ctypes.byref(info)), "jpgx_jfif_info_of_gray")
-    return _info_dict(info)
+    return _jfif_info(lib.jpgx_jfif_info_of_gray, data)
 
 
 def read_jfif_gray(data, nthreads: int = 1) -> dict:
     """jpgx_read_jfif_gray: a one-component baseline file -> dict(coef int16 [nb][64], qt uint16 [64],
     width, height, sample_ratio 0, restart_interval).  JpgxError(EJFIF_HEADER / EJFIF_SCAN) when refused."""
-    info = jfif_info_gray(data)
-    buf = np.frombuffer(bytes(data), np.uint8)
-    coef = np.empty((info["nb_y"], 64), np.int16)
-    qt = np.zeros(64, np.uint16)
-    got = JfifInfo()
-    _check(lib.jpgx_read_jfif_gray(buf.ctypes.data, len(buf), nthreads, coef.ctypes.data, coef.size, qt.ctypes.data,
-                                   ctypes.byref(got)), "jpgx_read_jfif_gray")
-    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"], sample_ratio=0,
-                restart_interval=info["restart_interval"])
+    return _read_jfif(lib.jpgx_read_jfif_gray, data, jfif_info_gray(data), 64, nthreads)
 
 
 def read_jfif_sub_gray(data, sub_bytes: int = 0, tile_subs: int = 0) -> dict:
     """jpgx_read_jfif_sub_gray: read_jfif_gray by the routines of the device decoder that works inside a
     restart interval (read_jfif_sub's shapes and `stats`)."""
-    info = jfif_info_gray(data)
-    buf = np.frombuffer(bytes(data), np.uint8)
-    coef = np.empty((info["nb_y"], 64), np.int16)
-    qt = np.zeros(64, np.uint16)
-    got, stats = JfifInfo(), JfifSubStats()
-    _check(lib.jpgx_read_jfif_sub_gray(buf.ctypes.data, len(buf), sub_bytes, tile_subs, coef.ctypes.data, coef.size,
-                                       qt.ctypes.data, ctypes.byref(got), ctypes.byref(stats)), "jpgx_read_jfif_sub_gray")
-    return dict(coef=coef, qt=qt, width=info["width"], height=info["height"], sample_ratio=0,
-                restart_interval=info["restart_interval"],
-                stats={n: int(getattr(stats, n)) for n, _ in JfifSubStats._fields_})
+    return _read_jfif(lib.jpgx_read_jfif_sub_gray, data, jfif_info_gray(data), 64, sub_args=(sub_bytes, tile_subs))
 
 
 def pixels_host_gray(coef: np.ndarray, width: int, height: int, qt: np.ndarray, channels: int = 1,

@@ -9,7 +9,8 @@
  * JPGX_EJFIF_SCAN, and a status-0 frame's coefficients and tables equal; such a frame then goes
  * through the pixel routine with 1 and 3 channels into buffers of exactly height x channels x width
  * bytes.  The caller states the fixture's geometry, as the device entry point's caller does: a header
- * that parses to another one counts as a header error.
+ * that parses to another one counts as a header error.  Before the files, threads(): the host twins'
+ * thread fan-out (csrc/jx_par.h) on 0, 1, 3, 64 and, in the writer, 200 threads.
  * Exit status 0 and "gray_san: clean" when everything holds. */
 #define _POSIX_C_SOURCE 200809L
 #include <dirent.h>
@@ -117,8 +118,53 @@ static int one_file(const char *path, long *used)
     return 0;
 }
 
+/* the host twins' thread fan-out (csrc/jx_par.h): a 16 x 16 4:4:4 frame, 2 MCU rows, through the
+ * writer, the reader and both pixel routines on 1, 0 (one per CPU), 3 (more threads than rows) and 64
+ * (the most) threads, every output equal to the one-thread one; then the writer's 200 jobs, more than
+ * the runner keeps on its stack, over the 520 one-MCU rows of an 8 x 4160 frame */
+static int threads(void)
+{
+    static const int nt[4] = {1, 0, 3, 64};
+    enum { kCoef = 12 * 64, kCap = 8192 };
+    int16_t coef[kCoef], back[2][kCoef];
+    uint16_t qt[2][2][64];
+    uint8_t *file[2], rgb[2][16 * 48], gray[2][16 * 48], flat[2][16 * 48];    /* flat: one thread's, 1 and 3 channels */
+    size_t len[2] = {0, 0};
+    uint32_t x = 0x6a785f70u;
+    for (int i = 0; i < kCoef; i++) {
+        x = x * 1103515245u + 12345u;
+        coef[i] = (int16_t)((int)(x >> 16 & 63u) - 32);
+    }
+    for (int k = 0; k < 2; k++) CHECK((file[k] = (uint8_t *)malloc(kCap)) != NULL);
+    for (int i = 0; i < 4; i++) {
+        const int k = i != 0;                               /* 0: one thread's, 1: this count's */
+        CHECK(jpgx_write_jfif_ex(coef, 16, 16, 75, 0, 1, nt[i], file[k], kCap, &len[k]) == 0);
+        CHECK(len[k] == len[0] && memcmp(file[k], file[0], len[0]) == 0);
+        CHECK(jpgx_read_jfif(file[0], len[0], nt[i], back[k], kCoef, qt[k], NULL) == 0);
+        CHECK(memcmp(back[k], coef, sizeof coef) == 0 && memcmp(qt[k], qt[0], sizeof qt[0]) == 0);
+        CHECK(jpgx_pixels_host(coef, 16, 16, 0, (const uint16_t (*)[64])qt[0], rgb[k], 48, nt[i]) == 0);
+        CHECK(memcmp(rgb[k], rgb[0], sizeof rgb[0]) == 0);
+        for (int ch = 1; ch <= 3; ch += 2) {
+            memset(gray[k], 0, sizeof gray[k]);
+            CHECK(jpgx_pixels_host_gray(coef, 16, 16, qt[0][0], gray[k], (size_t)ch * 16, ch, nt[i]) == 0);
+            if (!k) memcpy(flat[ch / 2], gray[0], sizeof gray[0]);
+            CHECK(memcmp(gray[k], flat[ch / 2], sizeof gray[0]) == 0);
+        }
+    }
+    int16_t *zero = (int16_t *)calloc((size_t)3 * 520 * 64, sizeof(int16_t));
+    CHECK(zero);
+    CHECK(jpgx_write_jfif_ex(zero, 8, 4160, 50, 0, 1, 1, file[0], kCap, &len[0]) == 0);
+    CHECK(jpgx_write_jfif_ex(zero, 8, 4160, 50, 0, -1, 200, file[1], kCap, &len[1]) == 0);     /* ceil(520 / 800) = 1 row */
+    CHECK(len[1] == len[0] && memcmp(file[1], file[0], len[0]) == 0);
+    free(zero);
+    free(file[0]);
+    free(file[1]);
+    return 0;
+}
+
 int main(void)
 {
+    if (threads()) return 1;
     /* tests/c/gray_san.c -> tests/golden/gray_fixtures/ */
     char dir[4096];
     const char *self = __FILE__, *cut = strstr(self, "c/gray_san.c");

@@ -2,7 +2,8 @@
 emits (SOF0, or SOF1 with 16-bit DQT, DHT, DRI with RSTm markers, one interleaved SOS) and returns the quantised
 zig-zag coefficients [ncomp][nblocks][64] (a list [Y, Cb, Cr] for 4:2:2 / 4:2:0) and the
 DQT tables -- an independent check of the
-writer, written from ITU-T T.81 (Annex C canonical codes, F.2.2 decoding, F.1.2.3 stuffing)."""
+writer, written from ITU-T T.81 (Annex C canonical codes, F.2.2 decoding, F.1.2.3 stuffing).
+A file of any width and height: the coefficients are the coded frame's, the size rounded up to the MCU."""
 import numpy as np
 
 
@@ -106,9 +107,9 @@ def decode(data: bytes):
             break
         i += 2 + ln
     hs, vs = comps[0][1] >> 4, comps[0][1] & 15       # luma sampling (1,1) (2,1) (2,2)
-    bpr = W // 8
-    nb = bpr * (H // 8)
-    cpr, crows = bpr // hs, H // 8 // vs
+    cpr, crows = -(-W // (8 * hs)), -(-H // (8 * vs))  # MCUs of the coded frame: the size rounded up (T.81 A.2.4)
+    bpr = cpr * hs
+    nb = bpr * (crows * vs)
     nbc = cpr * crows
     out = [np.zeros((nb, 64), np.int32)] + [np.zeros((nbc, 64), np.int32) for _ in sel[1:]]
     br = _Bits(b[i:])

@@ -1,10 +1,10 @@
 """An independent decoder of one-component (grayscale) baseline JPEG files (test helper), written from
-ITU-T T.81 on the bit reader and the canonical tables of tests/jfif_decode_any.py.  A scan of one
+ITU-T T.81 on the bit reader and the canonical tables of tests/jfif_decode.py.  A scan of one
 component is not interleaved (T.81 A.2.2): whatever sampling factors SOF states, the MCU is one block,
 the frame has ceil(W / 8) x ceil(H / 8) of them in raster order, and DRI counts blocks."""
 import numpy as np
 
-from jfif_decode_any import _Bits, _decode_sym, _extend, _table, _u16
+from jfif_decode import _Bits, _decode_sym, _extend, _table, _u16
 
 
 def decode(data: bytes):

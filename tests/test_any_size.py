@@ -1,5 +1,5 @@
 """Baseline JFIF files of any width and height, on the host: the _any readers
-against an independent decoder (tests/jfif_decode_any.py), the twin of k_jd_sub against the reader,
+against an independent decoder (tests/jfif_decode.py), the twin of k_jd_sub against the reader,
 jpgx_pixels_host_any against the numpy restatement of the contract (tests/idct_ref_any.py) and against
 Pillow's libjpeg decode, the _any calls against the plain ones at sizes both take, the argument checks
 of the two device entry points (no device is touched) and the sanitizer program tests/c/any_san.c.
@@ -12,7 +12,7 @@ import idct_ref_any as R
 import jpgx
 import jpgx.compat as C
 import pixels_cases as P
-from jfif_decode_any import decode
+from jfif_decode import decode
 
 L = jpgx.lib
 SUB = jpgx.JFIF_DECODE_SUBINTERVAL

@@ -13,21 +13,13 @@ import idct_ref_any as R
 import jpgx
 import jpgx.compat as C
 import pixels_cases as P
+from gpu_files import upload as _upload
 
 gpu = pytest.mark.gpu
 pillow = pytest.mark.skipif(not A.have_pillow(), reason="needs Pillow")
 L = jpgx.lib
 FILL, CFILL = 0x7A, 0x5A5A
 SUB = jpgx.JFIF_DECODE_SUBINTERVAL
-
-
-def _upload(cuda, files):
-    import torch
-    cap = max(len(f) for f in files)
-    host = np.zeros((len(files), cap), np.uint8)
-    for k, f in enumerate(files):
-        host[k, :len(f)] = np.frombuffer(f, np.uint8)
-    return torch.from_numpy(host).to(cuda), torch.tensor([len(f) for f in files], dtype=torch.int64, device=cuda)
 
 
 def _host(data):

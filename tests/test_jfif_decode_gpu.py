@@ -5,12 +5,16 @@ The oracle everywhere is the host decoder on the same bytes, jpgx.compat.read_jf
 against the independent decoder in tests/test_jfif_read.py), for the coefficients, the tables and
 the status alike; every comparison is ==.  (4:2:0 cases use 64x80 where the others use 64x72: a
 4:2:0 MCU is 16 rows high.)"""
+import functools
+
 import numpy as np
 import pytest
 
+import gpu_files
 import jfif_san_cases as S
 import jpgx
 import jpgx.compat as C
+from gpu_files import check_batch as _check_batch, host as _host, roundtrip as _roundtrip
 from jfif_decode import decode
 from jfif_inputs import hand_made, lap as _lap, nblocks as _nblocks, stuffing_heavy
 
@@ -20,51 +24,7 @@ HEADER, SCAN = jpgx.EJFIF_HEADER, jpgx.EJFIF_SCAN
 PIECE, CHUNK = 16, 4096
 
 
-def _host(data):
-    """(status, coef [nblk][64] or None, qt or None) of the host decoder"""
-    try:
-        r = C.read_jfif(data, 1)
-    except jpgx.JpgxError as e:
-        return e.rc, None, None
-    return 0, r["coef"].reshape(-1, 64), r["qt"]
-
-
-def _upload(cuda, files, stride=None):
-    import torch
-    stride = stride or max(len(f) for f in files)
-    buf = np.full((len(files), stride), 0xA5, np.uint8)
-    for k, f in enumerate(files):
-        buf[k, :len(f)] = np.frombuffer(f, np.uint8)
-    return torch.from_numpy(buf).to(cuda), torch.tensor([len(f) for f in files], dtype=torch.int64, device=cuda)
-
-
-def _check_batch(cuda, files, W, H, sr, stride=None):
-    """decodes the files as one batch and compares every frame with the host decoder"""
-    d_files, lens = _upload(cuda, files, stride)
-    coef, qt, status = jpgx.jfif_decode_gpu(d_files, lens, W, H, sr)
-    coef, qt, status = coef.cpu().numpy(), qt.cpu().numpy(), status.cpu().numpy()
-    for k, f in enumerate(files):
-        rc, want, wqt = _host(f)
-        assert status[k] == rc, (k, status[k], rc)
-        if rc == 0:
-            assert np.array_equal(coef[k], want), k
-            assert np.array_equal(qt[k], wqt), k
-    return status
-
-
-def _roundtrip(cuda, coef, W, H, q, sr, rr, optimize=False):
-    """jfif_decode_gpu(*jfif_gpu(coef)): the coder's outputs passed on unchanged"""
-    import torch
-    d = torch.from_numpy(np.ascontiguousarray(coef, np.int16)).to(cuda).reshape(1, -1)
-    out, lens = jpgx.jfif_gpu(d, W, H, q, sr, rr, optimize=optimize)
-    got, qt, status = jpgx.jfif_decode_gpu(out, lens, W, H, sr)
-    n = int(lens[0])
-    data = out[0, :n].cpu().numpy().tobytes()
-    rc, want, wqt = _host(data)
-    assert rc == 0 and int(status[0]) == 0
-    assert np.array_equal(got[0].cpu().numpy(), want)
-    assert np.array_equal(qt[0].cpu().numpy(), wqt)
-    return got[0].cpu().numpy()
+_upload = functools.partial(gpu_files.upload, fill=gpu_files.SLOT_FILL)
 
 
 # ---- round trips ------------------------------------------------------------------------------------

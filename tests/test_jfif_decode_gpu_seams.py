@@ -17,6 +17,7 @@ import pytest
 import gray_cases as G
 import jfif_dec_seams as D
 import jpgx
+from gpu_files import upload
 from jfif_inputs import nblocks
 
 gpu = pytest.mark.gpu
@@ -33,11 +34,7 @@ def _decode(cuda, files, W, H, sr, sub, fill=0xA5, stride=None, before=None):
     import torch
     L, n = jpgx.lib, len(files)
     stride = stride or max(len(f) for f in files) + 3 * D.HALO     # `fill` behind every file, the longest too
-    buf = np.full((n, stride), fill, np.uint8)
-    for k, f in enumerate(files):
-        buf[k, :len(f)] = np.frombuffer(f, np.uint8)
-    d_files = torch.from_numpy(buf).to(cuda)
-    lens = torch.tensor([len(f) for f in files], dtype=torch.int64, device=cuda)
+    d_files, lens = upload(cuda, files, stride, fill)
     if before:
         before(d_files.data_ptr())
     gray = sr is None

@@ -14,6 +14,7 @@ import jfif_san_cases as S
 import jpgx
 import jpgx.compat as C
 import pixels_cases as P
+from gpu_files import upload
 from jfif_decode import decode
 
 gpu = pytest.mark.gpu
@@ -156,11 +157,7 @@ def test_chain_with_a_corrupt_file_in_the_middle(cuda):
     assert (W, H, sr) == (16, 16, 0) and (len(data), S.fnv1a(data)) == S.GPU_FILE[1:]
     pos, val = S.GPU_FLIP
     files = [data, S.flipped(data, pos, val), data]
-    host = np.zeros((3, len(data)), np.uint8)
-    for k, f in enumerate(files):
-        host[k] = np.frombuffer(f, np.uint8)
-    d_files = torch.from_numpy(host).to(cuda)
-    lens = torch.tensor([len(f) for f in files], dtype=torch.int64, device=cuda)
+    d_files, lens = upload(cuda, files)
     out = torch.full((3 * H * 3 * W,), FILL, dtype=torch.uint8, device=cuda)
     coef, qt, status = jpgx.jfif_decode_gpu(d_files, lens, W, H, sr)
     rgb = jpgx.pixels_gpu(coef, W, H, sr, d_qt=qt, status=status, out=out)
@@ -240,14 +237,7 @@ def test_graph_capture_of_decode_and_pixels(cuda, sr):
     sets = [[C.write_jfif_ex(P.oracle_coef(kind, W, H, q, sr) if s == 0 else -P.oracle_coef(kind, W, H, q, sr),
                              W, H, q, sr, restart_rows=1, nthreads=1) for kind in ("splitmix", "tie")] for s in range(2)]
     stride = max(len(f) for fs in sets for f in fs)
-
-    def upload(fs):
-        buf = np.full((2, stride), 0xA5, np.uint8)
-        for k, f in enumerate(fs):
-            buf[k, :len(f)] = np.frombuffer(f, np.uint8)
-        return torch.from_numpy(buf).to(cuda), torch.tensor([len(f) for f in fs], dtype=torch.int64, device=cuda)
-
-    ups = [upload(fs) for fs in sets]
+    ups = [upload(cuda, fs, stride, 0xA5) for fs in sets]
     d_files, lens = ups[0][0].clone(), ups[0][1].clone()
     coef = torch.zeros((2, per), dtype=torch.int16, device=cuda)
     qt = torch.zeros((2, 2, 64), dtype=torch.int16, device=cuda)
