@@ -1,7 +1,7 @@
 """Test helper: the coded bits of every block of a scan, restated from ITU-T T.81 F.1.2 and
 independent of the writers.
 
-walk() is the one per-block walk of the tests (tests/test_jfif_opt.py's symbol_counts counts its
+walk() is the one per-block walk of the tests (tests/jfif_opt_common.py's symbol_counts counts its
 symbols, interval_bits() here adds up their lengths).  The code lengths come from the DHT segments of
 the file under test, so the same helper serves the standard and the per-image tables.  From the bits
 follow each block's bit offset within its restart interval, the interval's bits and the length of its

@@ -1,10 +1,10 @@
 """Per-image Huffman tables (JPGX_JFIF_OPTIMIZE): the table builder jx_jfif_optimal, the host writer
 jpgx_write_jfif_opt and the device coder jpgx_jfif_gpu_ex.
 
-The builder is checked against a restatement of ITU-T T.81 Annex K.2 written here from the standard
-(annex_k2); the host files against that restatement applied to symbol counts this file computes
-itself from the coefficients, and by decoding them; the device against the host writer on one
-thread, == on bytes."""
+The builder is checked against a restatement of ITU-T T.81 Annex K.2 written from the standard
+(annex_k2, tests/jfif_opt_common.py); the host files against that restatement applied to symbol
+counts the tests compute themselves from the coefficients, and by decoding them; the device against
+the host writer on one thread, == on bytes."""
 import ctypes
 import io
 import itertools
@@ -18,78 +18,14 @@ import jpgx
 import jpgx.compat as C
 import san_build
 from conftest import GOLDEN, REPO
-from jfif_bits import category, walk
 from jfif_decode import decode
 from jfif_inputs import CASES, hand_made, stuffing_heavy          # the geometries of tests/test_jfif_gpu.py
 from jfif_inputs import lap as _lap, nblocks as _nblocks
+from jfif_opt_common import (_check_table, _device, _dht_bytes, _flat, _host, _raw, annex_k2, dht_tables, fib_vector,
+                             segments, symbol_counts)   # shared with tests/test_jfif_tables*.py
 
 gpu = pytest.mark.gpu
 OPT = jpgx.JFIF_OPTIMIZE
-
-
-# ---- T.81 Annex K.2, restated -------------------------------------------------------------------
-def annex_k2(counts):
-    """(bits[16], vals, depth of the unlimited tree) for 256 symbol counts: Figures K.1 - K.4 with
-    the reserved point 256 of frequency 1; of equal frequencies the largest index is taken."""
-    freq = [int(c) for c in counts] + [1]
-    codesize, others = [0] * 257, [-1] * 257
-
-    def least(skip):
-        best = -1
-        for i in range(257):
-            if freq[i] and i != skip and (best < 0 or freq[i] <= freq[best]):
-                best = i
-        return best
-
-    while True:
-        v1 = least(-1)
-        v2 = least(v1)
-        if v2 < 0:
-            break
-        freq[v1] += freq[v2]
-        freq[v2] = 0
-        while True:
-            codesize[v1] += 1
-            if others[v1] < 0:
-                break
-            v1 = others[v1]
-        others[v1] = v2
-        while True:
-            codesize[v2] += 1
-            if others[v2] < 0:
-                break
-            v2 = others[v2]
-    depth = max(codesize)
-    bits = [0] * (max(depth, 16) + 1)
-    for i in range(257):
-        if codesize[i]:
-            bits[codesize[i]] += 1
-    i = depth
-    while i > 16:
-        while bits[i] > 0:
-            j = i - 2
-            while bits[j] == 0:
-                j -= 1
-            bits[i] -= 2
-            bits[i - 1] += 1
-            bits[j + 1] += 2
-            bits[j] -= 1
-        i -= 1
-    i = 16
-    while i > 0 and bits[i] == 0:
-        i -= 1
-    if i:
-        bits[i] -= 1
-    vals = [s for _, s in sorted((codesize[s], s) for s in range(256) if codesize[s])]
-    return bits[1:17], vals, depth
-
-
-def fib_vector(n):
-    """1, 2, 3, 5, 8, ...: n distinct counts, each the sum of the two before it"""
-    v = [1, 2]
-    while len(v) < n:
-        v.append(v[-1] + v[-2])
-    return v[:n]
 
 
 def _optimal(counts):
@@ -126,12 +62,6 @@ def _vectors():
 VECTORS = _vectors()
 
 
-def _check_table(counts, bits, vals):
-    assert len(bits) == 16 and sum(bits) == len(vals)              # no length above 16
-    assert sum(b << (16 - l) for l, b in enumerate(bits, 1)) <= (1 << 16) - 1   # Kraft, all ones free
-    assert sorted(vals) == [s for s in range(256) if counts[s]]
-
-
 @pytest.mark.parametrize("name", sorted(VECTORS))
 def test_builder_matches_restatement(name):
     counts = VECTORS[name]
@@ -153,62 +83,6 @@ def test_builder_all_zero_counts():
 
 
 # ---- coefficients, symbol counts and file parsing ------------------------------------------------
-def _host(coef, W, H, q, sr, rr, optimize=True, nthreads=1):
-    """the oracle: the host writer (the device's restart_rows -1 is one MCU row per interval)"""
-    return C.write_jfif_ex(coef, W, H, q, sr, restart_rows=1 if rr == -1 else rr, nthreads=nthreads,
-                           optimize=optimize)
-
-
-def symbol_counts(coef, W, H, sr, rr):
-    """[4][256]: DC luma, AC luma, DC chroma, AC chroma symbols of the scan, in MCU order with the
-    predictors reset at every interval of rr MCU rows (0: never) and the writer's clamps; the walk is
-    tests/jfif_bits.py's"""
-    cnt = np.zeros((4, 256), np.uint64)
-
-    def visit(iv, comp, row, step, diff, acs):
-        t = 0 if comp == 0 else 2
-        cnt[t, category(diff)] += 1
-        for sym, _ in acs:
-            cnt[t + 1, sym] += 1
-
-    walk(coef, W, H, sr, rr, visit)
-    return cnt
-
-
-def segments(data):
-    """[(marker, payload)] of the segments before the scan"""
-    assert data[:2] == b"\xff\xd8"
-    at, out = 2, []
-    while True:
-        assert data[at] == 0xff
-        m, n = data[at + 1], data[at + 2] << 8 | data[at + 3]
-        out.append((m, data[at + 4:at + 2 + n]))
-        at += 2 + n
-        if m == 0xda:
-            return out, at
-
-
-def dht_tables(data):
-    """{class << 4 | id: (bits, vals)} and the segments' bytes in file order"""
-    tabs, order = {}, []
-    for m, p in segments(data)[0]:
-        if m == 0xc4:
-            bits = list(p[1:17])
-            assert len(p) == 17 + sum(bits)                    # one table per segment
-            tabs[p[0]] = (bits, list(p[17:]))
-            order.append(p[0])
-    assert order == [0x00, 0x10, 0x01, 0x11]
-    return tabs
-
-
-def _dht_bytes(data):
-    return b"".join(bytes([m]) + p for m, p in segments(data)[0] if m == 0xc4)
-
-
-def _flat(planes):
-    return np.concatenate([np.asarray(x).reshape(-1, 64) for x in planes])
-
-
 @pytest.fixture(scope="module")
 def jfd():
     subprocess.run(["make", "-s", "-C", os.path.join(REPO, "tests", "c"), "jfd"], check=True)
@@ -335,29 +209,6 @@ def test_builder_and_writer_under_asan_ubsan():
 
 
 # ---- GPU: byte equality with the host writer -----------------------------------------------------
-def _device(cuda, coef, W, H, q, sr, rr, cap=None, optimize=True):
-    import torch
-    d = torch.from_numpy(np.ascontiguousarray(coef, np.int16)).to(cuda).reshape(1, -1)
-    out, lens = jpgx.jfif_gpu(d, W, H, q, sr, rr, cap=cap, optimize=optimize)
-    n = int(lens[0])
-    assert 0 < n <= out.shape[1]
-    return out[0, :n].cpu().numpy().tobytes()
-
-
-def _raw(d_coef, fstride, nf, W, H, q, sr, rr, flags, out, ostride, cap, lens, ws=None):
-    """jpgx_jfif_gpu_ex itself on torch tensors (a workspace of the size the library asks for)"""
-    import torch
-    need = jpgx.lib.jpgx_jfif_gpu_workspace_size_ex(W, H, sr, rr, nf, cap, flags)
-    assert need > 0
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=out.device)
-    assert ws.numel() >= need
-    rc = jpgx.lib.jpgx_jfif_gpu_ex(d_coef.data_ptr(), fstride, nf, W, H, q, sr, rr, flags, out.data_ptr(), ostride,
-                                   cap, lens.data_ptr(), ws.data_ptr(), ws.numel(), None)
-    torch.cuda.synchronize()
-    return rc
-
-
 @gpu
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_bytes_equal_host_writer(cuda, name):
