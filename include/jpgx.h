@@ -446,6 +446,54 @@ int jpgx_pixels_gpu_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t
                          const int32_t *d_status, uint8_t *d_out, size_t out_pitch,
                          size_t out_frame_stride, int channels, void *stream);
 
+/* ---- the encode side of the one-component family ---------------------------
+ * The reference knows only RGB: this contract is the project's own (parity unpinned).  A one-channel
+ * image of width x height, 1 .. 65535 each, is coded as jx_frame_make_gray's frame (csrc/jx_frame.h):
+ * bw x bh = ceil(width / 8) x ceil(height / 8) blocks in raster order with standard tiling (no x0 = -8
+ * quirk), no chroma, never rounded up to a larger MCU.  Pixels beyond the image follow the edge rule of
+ * the any-size family: the last column repeated to the right, the last row downwards.  The sample is
+ * (double)g - 128; a block's coefficients are the reference's dct_block in its exact operation order,
+ * quantise_lum with the scaled luminance table applied transposed, C round() and zig-zag -- what
+ * cpuref_dct_block, cpuref_quantise_block (with cpuref_scale_table(cpuref_q_lum, q)) and
+ * cpuref_zigzag_block compute.  Output: int16 Y [nb][64] per frame, what jpgx_jfif_decode_gpu_gray
+ * returns and jpgx_pixels_gpu_gray takes.
+ *
+ * jpgx_blocks_gpu_gray: one launch of k_gray (csrc/jpgx_gray.hip) over the batch.  d_gray: uint8
+ * [height][width] top-down, rows in_pitch >= width bytes apart, frames in_frame_stride bytes apart (any
+ * value: the input is only read, so frames may overlap or, with 0, be one frame);
+ * any pitch and any alignment; nothing is read outside bytes [0, width) of rows [0, height) of a frame.
+ * d_out: 16-byte aligned, frames out_frame_stride int16 elements apart, a multiple of 64 and at least
+ * nb * 64; only a frame's nb * 64 elements are written.  flags: 0 or JPGX_FLAG_FORCE_EXACT (every
+ * coefficient through the exact path; the same output).  No workspace; asynchronous on `stream`,
+ * capturable, no state but the per-quality tables built once per device.  All checks happen before the
+ * first device call, the first that applies: JPGX_EQUALITY (quality outside 1 .. 97), JPGX_EGEOMETRY (a
+ * side outside 1 .. 65535), JPGX_EARG (null d_gray or d_out, unknown flags, in_pitch < width, nframes
+ * outside 1 .. 65535, d_out not 16-byte aligned, an out_frame_stride that is not whole blocks or is too small, a batch of 2^32
+ * blocks or more).
+ *
+ * jpgx_jfif_gpu_gray_workspace_size / jpgx_jfif_gpu_gray: jpgx_jfif_gpu_any's contract without
+ * sample_ratio, for one-component files: d_coef holds Y [nb][64] per frame (coef_frame_stride a
+ * multiple of 64 and at least nb * 64); frame f's file is jpgx_write_jfif_gray's (jpgx_compat.h) for
+ * the same arguments byte for byte, restart_rows -1 meaning one block row here.  restart_rows counts
+ * block rows, DRI counts blocks: rows x bw must fit 16 bits, 0 is refused.  jfif_flags 0 or
+ * JPGX_JFIF_OPTIMIZE (the frame's own two luminance tables).  The same kernels as the colour coder walk
+ * the one-component frame (hs = vs = lum = bpm = 1, cbw = bw, cbh = bh, nbc = 0).  JPGX_EARG for a side
+ * outside 1 .. 65535, the interval, the flags, the pointers and the strides; JPGX_EQUALITY;
+ * JPGX_EWORKSPACE; the capacity report in d_len[f] (bit 63 and a capacity that suffices) and everything
+ * else are jpgx_jfif_gpu_ex's.  jpgx_jfif_bound(8 bw, 8 bh) bounds a frame's file. */
+int jpgx_blocks_gpu_gray(const uint8_t *d_gray, size_t in_pitch, size_t in_frame_stride, size_t nframes,
+                         int width, int height, int quality, unsigned flags, int16_t *d_out,
+                         size_t out_frame_stride, void *stream);
+size_t jpgx_jfif_gpu_gray_workspace_size(int width, int height, int restart_rows, size_t nframes,
+                                         size_t out_cap, unsigned jfif_flags);
+int jpgx_jfif_gpu_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                       int quality, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
+                       size_t out_frame_stride, size_t out_cap, uint64_t *d_len,
+                       void *d_workspace, size_t workspace_bytes, void *stream);
+/* k_gray's fp32 scales and guard band limits of `quality`, [v * 8 + u] for coefficient (row v, column
+ * u): as jpgx_guard_band, from the sample bound [-128, 127].  JPGX_EQUALITY, JPGX_EARG (null). */
+int jpgx_guard_band_gray(int quality, float scale[64], float lim[64]);
+
 /* The two tables exactly as the JFIF writers put them into DQT for `quality` (the divisors the
  * forward path applied, zig-zag order): jpgx_blocks_gpu's output can be turned into pixels without
  * writing a file.  JPGX_EQUALITY outside 1..97, JPGX_EARG for a null qt. */

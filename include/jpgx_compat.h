@@ -199,6 +199,23 @@ int jpgx_write_jfif_any(const int16_t *coef, int width, int height, int quality,
                         int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out,
                         size_t cap, size_t *len);
 
+/* jpgx_write_jfif_opt for a one-component (grayscale) file of any width and height, 1 .. 65535 each
+ * (include/jpgx.h: the encode side of the one-component family): coef holds Y [nb][64],
+ * nb = ceil(width / 8) * ceil(height / 8) blocks in raster order -- what jpgx_blocks_gpu_gray writes
+ * and jpgx_read_jfif_gray returns.  The file: SOI, jpgx_write_jfif's APP0, one DQT (table 0,
+ * jpgx_jfif_qt(quality)[0]), SOF0 with Nf = 1 (component 1, sampling 0x11, Tq 0; SOF1 and a 16-bit table
+ * for q <= 23), DHT DC 0x00 and AC 0x10 only -- the K.3 luminance tables or, with JPGX_JFIF_OPTIMIZE,
+ * the image's own by Annex K.2, counted over these two tables alone -- DRI when there are intervals,
+ * SOS with Ns = 1, the scan, EOI.  restart_rows counts block rows (0 none, -1 auto as in
+ * jpgx_write_jfif_ex) and DRI counts blocks: rows x ceil(width / 8) must fit 16 bits.  Luminance never
+ * reaches the coder's clamps (|AC| <= 1020, |DC difference| <= 2040 at q 97), so reading the file back
+ * returns coef for every input.  The threading contract is jpgx_write_jfif_opt's: the bytes do not
+ * depend on nthreads for restart_rows >= 0.  jpgx_jfif_bound(8 bw, 8 bh) bounds the file.  JPGX_EARG for
+ * a side outside 1 .. 65535, the interval, unknown flags and null pointers, JPGX_EQUALITY, JPGX_ENOMEM,
+ * and JPGX_EARG with *len = the size needed when cap is too small, as jpgx_write_jfif_opt. */
+int jpgx_write_jfif_gray(const int16_t *coef, int width, int height, int quality, int restart_rows,
+                         int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap, size_t *len);
+
 /* The edge rule of the encode side's _any entry points, on the host: out, coded_height rows of
  * 3 coded_width bytes, is the width x height image rgb (rows `pitch` >= 3 width bytes apart) with its
  * last column repeated to the right and its last row repeated downwards -- numpy's

@@ -33,6 +33,11 @@
  *               frame's code tables, DHT segments and their lengths in the workspace
  * k_jf_len, k_jf_pack and k_jf_frame are templates over where tables and header come from: the
  * launch's by-value arguments (the standard path, the same code as before) or the frame's workspace.
+ *
+ * One-component (grayscale) files (jpgx_jfif_gpu_gray) are the same kernels over the
+ * one-component frame (jx_frame_make_gray_coded: an MCU is a block), with the one-component header
+ * (jx_jfif_header_gray) and, optimised, two tables per frame: k_jf_tables on a grid of 2 and
+ * k_jf_frame<JfHdrOptGray>, the one instantiation that is new.
  */
 #include <stdint.h>
 #include <string.h>
@@ -40,6 +45,7 @@
 #include "jpgx_internal.h"
 #include "jx_hip.h"
 #include "jx_jfif_enc.h"
+#include "jx_jfif_gray.h"
 
 namespace {
 
@@ -98,6 +104,32 @@ struct JfHdrOpt {
         i -= npre;
         const uint32_t *n = dhtlen + 4 * (size_t)f;
         for (uint32_t k = 0; k < 4; k++) {
+            if (i < n[k]) return dht[((size_t)f * 4 + k) * kDhtSlot + i];
+            i -= n[k];
+        }
+        return suf[i];
+    }
+};
+
+/* the same for a one-component file (jpgx_jfif_gpu_gray): two DHT segments, DC and AC luminance, in
+ * slots 0 and 1 of the frame's four; k_jf_frame's one new instantiation, every other kernel's text is
+ * the colour coder's */
+struct JfHdrOptGray {
+    uint8_t pre[kHdrPre], suf[kHdrSuf];
+    uint32_t npre, nsuf;
+    const uint8_t *dht;                 /* [nframes][4][kDhtSlot] */
+    const uint32_t *dhtlen;             /* [nframes][4] */
+    __device__ __forceinline__ uint32_t length(const JfArgs &, uint32_t f) const
+    {
+        const uint32_t *n = dhtlen + 4 * (size_t)f;
+        return npre + n[0] + n[1] + nsuf;
+    }
+    __device__ __forceinline__ uint8_t byte(uint32_t f, uint32_t i) const
+    {
+        if (i < npre) return pre[i];
+        i -= npre;
+        const uint32_t *n = dhtlen + 4 * (size_t)f;
+        for (uint32_t k = 0; k < 2; k++) {
             if (i < n[k]) return dht[((size_t)f * 4 + k) * kDhtSlot + i];
             i -= n[k];
         }
@@ -656,14 +688,20 @@ __global__ __launch_bounds__(kT) void k_jf_tables(const JfOpt o)
     if (t == 0) o.dhtlen[(size_t)f * 4 + tb] = min(2u + seg, (uint32_t)kDhtSlot);
 }
 
+/* which frame an entry point codes: whole MCUs only, the coded frame of a width x height file of any
+ * size, or a one-component file's blocks (sample_ratio unused; an MCU is a block, an MCU row a block row) */
+enum JfKind { kWhole, kAny, kGray };
+
 /* geometry and argument checks shared by the size query and the call; a.hdrlen stays 0.  The
  * device codes with restart intervals only: restart_rows 0 is refused, -1 is one MCU row */
-int jf_geometry(bool any, int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
+int jf_geometry(JfKind kind, int width, int height, int sample_ratio, int restart_rows, size_t nframes, JfArgs &a)
 {
     if (restart_rows == 0 || restart_rows < -1 || !jx_frames_ok(nframes)) return JPGX_EARG;
-    jx_frame_any fa;                                       /* any: the coded frame of a width x height file */
-    const int rc = jx_frame_rc_coder(any ? jx_frame_make_any(width, height, sample_ratio, &fa)
-                                         : jx_frame_make(width, height, sample_ratio, &a.g));
+    jx_frame_any fa;
+    const bool any = kind == kAny;
+    const int rc = jx_frame_rc_coder(kind == kGray ? jx_frame_make_gray_coded(width, height, &a.g)
+                                     : any         ? jx_frame_make_any(width, height, sample_ratio, &fa)
+                                                   : jx_frame_make(width, height, sample_ratio, &a.g));
     if (rc) return rc;
     if (any) a.g = fa.c;
     a.rpi = restart_rows > 0 ? (uint32_t)restart_rows : 1u;
@@ -701,12 +739,12 @@ JfLayout jf_layout(const JfArgs &a, size_t nframes, size_t out_cap, unsigned jfi
     return l;
 }
 
-size_t jf_workspace_size(bool any, int width, int height, int sample_ratio, int restart_rows, size_t nframes,
+size_t jf_workspace_size(JfKind kind, int width, int height, int sample_ratio, int restart_rows, size_t nframes,
                          size_t out_cap, unsigned jfif_flags)
 {
     JfArgs a;
     if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return 0;
-    if (jf_geometry(any, width, height, sample_ratio, restart_rows, nframes, a)) return 0;
+    if (jf_geometry(kind, width, height, sample_ratio, restart_rows, nframes, a)) return 0;
     return jf_layout(a, nframes, out_cap, jfif_flags).total;
 }
 
@@ -723,13 +761,19 @@ size_t jpgx_jfif_gpu_workspace_size(int width, int height, int sample_ratio, int
 size_t jpgx_jfif_gpu_workspace_size_ex(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
                                        size_t out_cap, unsigned jfif_flags)
 {
-    return jf_workspace_size(false, width, height, sample_ratio, restart_rows, nframes, out_cap, jfif_flags);
+    return jf_workspace_size(kWhole, width, height, sample_ratio, restart_rows, nframes, out_cap, jfif_flags);
 }
 
 size_t jpgx_jfif_gpu_any_workspace_size(int width, int height, int sample_ratio, int restart_rows, size_t nframes,
                                         size_t out_cap, unsigned jfif_flags)
 {
-    return jf_workspace_size(true, width, height, sample_ratio, restart_rows, nframes, out_cap, jfif_flags);
+    return jf_workspace_size(kAny, width, height, sample_ratio, restart_rows, nframes, out_cap, jfif_flags);
+}
+
+size_t jpgx_jfif_gpu_gray_workspace_size(int width, int height, int restart_rows, size_t nframes, size_t out_cap,
+                                         unsigned jfif_flags)
+{
+    return jf_workspace_size(kGray, width, height, 0, restart_rows, nframes, out_cap, jfif_flags);
 }
 
 int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
@@ -744,10 +788,11 @@ int jpgx_jfif_gpu(const int16_t *d_coef, size_t coef_frame_stride, size_t nframe
 
 namespace {
 
-/* jpgx_jfif_gpu_ex, and with `any` jpgx_jfif_gpu_any: the same kernels over the coded frame of a
+/* jpgx_jfif_gpu_ex, and with kAny jpgx_jfif_gpu_any: the same kernels over the coded frame of a
  * width x height file; the header states the file's own size, the restart interval counts the coded
- * frame's MCUs */
-int jf_code(bool any, const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+ * frame's MCUs.  With kGray jpgx_jfif_gpu_gray: the same kernels over the one-component frame, with the
+ * one-component header and, optimised, two tables per frame instead of four */
+int jf_code(JfKind kind, const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
             int quality, int sample_ratio, int restart_rows, unsigned jfif_flags, uint8_t *d_out,
             size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
             size_t workspace_bytes, void *stream)
@@ -758,14 +803,17 @@ int jf_code(bool any, const int16_t *d_coef, size_t coef_frame_stride, size_t nf
     if (!d_coef || !d_out || !d_len || !d_workspace || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_out & 15) ||
         ((uintptr_t)d_len & 7) || ((uintptr_t)d_workspace & 15))
         return JPGX_EARG;
-    int rc = jf_geometry(any, width, height, sample_ratio, restart_rows, nframes, a);
+    const bool gray = kind == kGray;
+    int rc = jf_geometry(kind, width, height, sample_ratio, restart_rows, nframes, a);
     if (rc) return rc;
     if (!jx_coef_batch_ok(coef_frame_stride, a.g.nblk) || out_frame_stride < out_cap) return JPGX_EARG;
     JfHdr hdr;
     memset(&hdr, 0, sizeof hdr);
     size_t dht_at = 0;
-    const size_t hl = jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.g.cbw, NULL, NULL, hdr.b,
-                                          sizeof hdr.b, &dht_at);
+    const size_t hl = gray ? jx_jfif_header_gray(width, height, quality, a.rpi * a.g.cbw, NULL, NULL, hdr.b,
+                                                 sizeof hdr.b, &dht_at)
+                           : jx_jfif_header_tabs(width, height, quality, sample_ratio, a.rpi * a.g.cbw, NULL, NULL,
+                                                 hdr.b, sizeof hdr.b, &dht_at);
     if (!hl) return JPGX_EQUALITY;
     if (hl > sizeof hdr.b) return JPGX_EARG;
     const JfLayout l = jf_layout(a, nframes, out_cap, jfif_flags);
@@ -799,7 +847,7 @@ int jf_code(bool any, const int16_t *d_coef, size_t coef_frame_stride, size_t nf
         /* the standard header around its DHT segments: what every frame's header shares */
         JfHdrOpt ho;
         memset(&ho, 0, sizeof ho);
-        const size_t suf_at = dht_at + JX_JFIF_DHT_STD;
+        const size_t suf_at = dht_at + (gray ? JX_JFIF_DHT_STD_GRAY : JX_JFIF_DHT_STD);
         if (dht_at > sizeof ho.pre || suf_at > hl || hl - suf_at > sizeof ho.suf) return JPGX_EARG;
         memcpy(ho.pre, hdr.b, dht_at);
         memcpy(ho.suf, hdr.b + suf_at, hl - suf_at);
@@ -815,11 +863,19 @@ int jf_code(bool any, const int16_t *d_coef, size_t coef_frame_stride, size_t nf
         const JfTabsOf tof{o.tabs};
         hipLaunchKernelGGL(k_jf_zero, per_frame, dim3(kT), 0, s, o);
         hipLaunchKernelGGL(k_jf_count, per_interval, dim3(kT), 0, s, a, o);
-        hipLaunchKernelGGL(k_jf_tables, dim3(4, (unsigned)nframes), dim3(kT), 0, s, o);
+        hipLaunchKernelGGL(k_jf_tables, dim3(gray ? 2 : 4, (unsigned)nframes), dim3(kT), 0, s, o);
         hipLaunchKernelGGL(k_jf_len<JfTabsOf>, per_interval, dim3(kT), 0, s, a, tof);
         hipLaunchKernelGGL(k_jf_place, per_frame, dim3(kT), 0, s, a);
         hipLaunchKernelGGL(k_jf_pack<JfTabsOf>, per_interval, dim3(kT), 0, s, a, tof);
-        hipLaunchKernelGGL(k_jf_frame<JfHdrOpt>, per_frame, dim3(kT), 0, s, a, ho);
+        if (gray) {                                        /* the same bytes around two segments */
+            JfHdrOptGray hg;
+            memcpy(hg.pre, ho.pre, sizeof hg.pre);
+            memcpy(hg.suf, ho.suf, sizeof hg.suf);
+            hg.npre = ho.npre, hg.nsuf = ho.nsuf, hg.dht = ho.dht, hg.dhtlen = ho.dhtlen;
+            hipLaunchKernelGGL(k_jf_frame<JfHdrOptGray>, per_frame, dim3(kT), 0, s, a, hg);
+        } else {
+            hipLaunchKernelGGL(k_jf_frame<JfHdrOpt>, per_frame, dim3(kT), 0, s, a, ho);
+        }
         hipLaunchKernelGGL(k_jf_stuff, per_interval, dim3(kT), 0, s, a);
         return jx_hip_rc(hipGetLastError());
     }
@@ -840,7 +896,7 @@ int jpgx_jfif_gpu_ex(const int16_t *d_coef, size_t coef_frame_stride, size_t nfr
                      size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
                      size_t workspace_bytes, void *stream)
 {
-    return jf_code(false, d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
+    return jf_code(kWhole, d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
                    jfif_flags, d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
 }
 
@@ -849,8 +905,16 @@ int jpgx_jfif_gpu_any(const int16_t *d_coef, size_t coef_frame_stride, size_t nf
                       size_t out_frame_stride, size_t out_cap, uint64_t *d_len, void *d_workspace,
                       size_t workspace_bytes, void *stream)
 {
-    return jf_code(true, d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
+    return jf_code(kAny, d_coef, coef_frame_stride, nframes, width, height, quality, sample_ratio, restart_rows,
                    jfif_flags, d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
+}
+
+int jpgx_jfif_gpu_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                       int quality, int restart_rows, unsigned jfif_flags, uint8_t *d_out, size_t out_frame_stride,
+                       size_t out_cap, uint64_t *d_len, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    return jf_code(kGray, d_coef, coef_frame_stride, nframes, width, height, quality, 0, restart_rows, jfif_flags,
+                   d_out, out_frame_stride, out_cap, d_len, d_workspace, workspace_bytes, stream);
 }
 
 }  /* extern "C" */

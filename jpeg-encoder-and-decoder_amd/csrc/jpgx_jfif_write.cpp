@@ -1,6 +1,6 @@
 /*
  * jpgx_jfif_write.cpp -- the host JFIF writer's scan: jpgx_write_jfif,
- * jpgx_write_jfif_sub, jpgx_write_jfif_ex, jpgx_write_jfif_opt, jpgx_write_jfif_any, jpgx_jfif_bound
+ * jpgx_write_jfif_sub, jpgx_write_jfif_ex, jpgx_write_jfif_opt, jpgx_write_jfif_any, jpgx_write_jfif_gray, jpgx_jfif_bound
  * (include/jpgx_compat.h).  What a block's symbols are, the clamps, the scan's geometry and its
  * block order are jx_jfif_enc.h's, the routines the device coder (jpgx_jfif.hip) runs; this file
  * adds the bit writer with its 0xFF stuffing, the restart-row policy and the threads.  Tables and
@@ -16,6 +16,7 @@
 #include "jpgx_internal.h"
 #include "jx_consts.h"
 #include "jx_jfif_enc.h"
+#include "jx_jfif_gray.h"
 #include "jx_par.h"
 
 namespace {
@@ -207,18 +208,26 @@ void job_main(void *jobs, uint32_t t, uint64_t i0, uint64_t i1)
     else walk_intervals(j->S, (size_t)i0, (size_t)i1, CodeSink{j->S, &j->w, NULL, NULL});
 }
 
-/* jpgx_write_jfif_opt, and with `any` jpgx_write_jfif_any: the scan of the coded frame of a
+/* which frame a writer codes: whole MCUs only, the coded frame of a file of any size, or a
+ * one-component file's blocks */
+enum Kind { kWhole, kAny, kGray };
+
+/* jpgx_write_jfif_opt, and with kAny jpgx_write_jfif_any: the scan of the coded frame of a
  * width x height file; the header states the file's own size, the restart interval counts the coded
- * frame's MCUs */
-int write_jfif(bool any, const int16_t *coef, int width, int height, int quality, int sample_ratio,
+ * frame's MCUs.  With kGray jpgx_write_jfif_gray: the one-component frame (sample_ratio unused), whose MCU
+ * is a block; two tables, the luminance ones, are used, counted and written. */
+int write_jfif(Kind kind, const int16_t *coef, int width, int height, int quality, int sample_ratio,
                int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap, size_t *len)
 {
     if (jfif_flags & ~JPGX_JFIF_OPTIMIZE) return JPGX_EARG;
     if (!coef || !out || restart_rows < -1 || nthreads < 0) return JPGX_EARG;
     Scan S;
     jx_frame_any fa;
-    int rc = jx_frame_rc_coder(any ? jx_frame_make_any(width, height, sample_ratio, &fa)
-                                   : jx_frame_make(width, height, sample_ratio, &S.g));
+    const bool any = kind == kAny, gray = kind == kGray;
+    const int ntab = gray ? 2 : 4;
+    int rc = jx_frame_rc_coder(gray  ? jx_frame_make_gray_coded(width, height, &S.g)
+                               : any ? jx_frame_make_any(width, height, sample_ratio, &fa)
+                                     : jx_frame_make(width, height, sample_ratio, &S.g));
     if (rc) return rc;
     if (any) S.g = fa.c;
     if (quality < 1 || quality > JX_MAXQ) return JPGX_EQUALITY;
@@ -257,10 +266,10 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
         for (long t = 0; t < T; t++) jobs[t].cnt = cnt + 4 * t;
         jx_par_run(S.nintervals, (uint64_t)T, job_main, jobs);
         for (long t = 1; t < T; t++)
-            for (int k = 0; k < 4; k++)
+            for (int k = 0; k < ntab; k++)
                 for (int s = 0; s < 256; s++) cnt[k][s] += cnt[4 * t + k][s];
         memset(ovals, 0, sizeof ovals);
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < ntab; k++) {
             jx_jfif_optimal(cnt[k], obits[k], ovals[k]);
             jx_jfif_build_codes(obits[k], ovals[k], S.cl[k]);
         }
@@ -275,8 +284,11 @@ int write_jfif(bool any, const int16_t *coef, int width, int height, int quality
     size_t n = 0;
     int overflow = 0;
     if (!rc) {
-        n = jx_jfif_header_tabs(width, height, quality, sample_ratio, (unsigned)(rr * S.g.cbw),
-                                (const uint8_t (*)[16])bits, (const uint8_t (*)[256])vals, out, cap, NULL);
+        const unsigned ri = (unsigned)(rr * S.g.cbw);
+        n = gray ? jx_jfif_header_gray(width, height, quality, ri, (const uint8_t (*)[16])bits,
+                                       (const uint8_t (*)[256])vals, out, cap, NULL)
+                 : jx_jfif_header_tabs(width, height, quality, sample_ratio, ri, (const uint8_t (*)[16])bits,
+                                       (const uint8_t (*)[256])vals, out, cap, NULL);
         if (!n) rc = JPGX_EQUALITY;
         if (n > cap) overflow = 1;
     }
@@ -343,7 +355,7 @@ int jpgx_write_jfif_opt(const int16_t *coef, int width, int height, int quality,
                         int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
                         size_t *len)
 {
-    return write_jfif(false, coef, width, height, quality, sample_ratio, restart_rows, nthreads, jfif_flags, out,
+    return write_jfif(kWhole, coef, width, height, quality, sample_ratio, restart_rows, nthreads, jfif_flags, out,
                       cap, len);
 }
 
@@ -351,8 +363,14 @@ int jpgx_write_jfif_any(const int16_t *coef, int width, int height, int quality,
                         int restart_rows, int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap,
                         size_t *len)
 {
-    return write_jfif(true, coef, width, height, quality, sample_ratio, restart_rows, nthreads, jfif_flags, out,
+    return write_jfif(kAny, coef, width, height, quality, sample_ratio, restart_rows, nthreads, jfif_flags, out,
                       cap, len);
+}
+
+int jpgx_write_jfif_gray(const int16_t *coef, int width, int height, int quality, int restart_rows,
+                         int nthreads, unsigned jfif_flags, uint8_t *out, size_t cap, size_t *len)
+{
+    return write_jfif(kGray, coef, width, height, quality, 0, restart_rows, nthreads, jfif_flags, out, cap, len);
 }
 
 }  /* extern "C" */

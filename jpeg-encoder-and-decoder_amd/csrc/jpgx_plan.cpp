@@ -20,6 +20,7 @@
 
 #include "jpgx_internal.h"
 #include "jx_consts.h"
+#include "jx_gray.h"
 #include "xform_math.h"
 
 /* pristine base tables, src/quantise.c:8-25 (row index = first subscript) */
@@ -788,4 +789,54 @@ extern "C" long long jx_selftest_mx420(long long nblocks, unsigned long long see
                                        long long *flagged, double *ratio)
 {
     return mx_selftest(2, nblocks, seed, quality, flagged, ratio);
+}
+
+/* ---- the one-channel forward path: k_gray (csrc/jpgx_gray.hip, csrc/jx_gray.h) ----
+ * The sample is byte - 128, an exact integer in [-128, 127]: the bound starts there with no error and
+ * runs through the kernel's own sequence, jx_fdct8 on rows and on columns.  Scales and divisors are the
+ * luminance ones of the colour path (same indexing: [v * 8 + u], divisor Qs[u][v]).  The kernel's
+ * restatement on the host, for the tests, is csrc/jpgx_gray_host.cpp. */
+
+namespace {
+
+void coef_bounds_gray(Bnd F[8][8])
+{
+    const Bnd p{-128.0, 127.0, 0.0};
+    Bnd px[8], row[8];
+    for (int x = 0; x < 8; x++) px[x] = p;
+    jx_fdct8<BoundOps>(px, row);   /* every pixel row has the same bound */
+    for (int u = 0; u < 8; u++) {
+        Bnd col[8], out[8];
+        for (int y = 0; y < 8; y++) col[y] = row[u];
+        jx_fdct8<BoundOps>(col, out);
+        for (int v = 0; v < 8; v++) F[v][u] = out[v];
+    }
+}
+
+}  // namespace
+
+extern "C" int jx_plan_tables_gray(int quality, float w[64], float lim[64], int16_t q[64])
+{
+    int qs[2][8][8];
+    int16_t qq[2][64];
+    const int rc = plan_divisors(quality, qs, qq);
+    if (rc) return rc;
+    memcpy(q, qq[0], sizeof qq[0]);
+    Bnd F[8][8];
+    coef_bounds_gray(F);
+    const long double a0 = 1.0L / sqrtl(2.0L);
+    for (int v = 0; v < 8; v++)
+        for (int u = 0; u < 8; u++) {
+            const long double au = u == 0 ? a0 : 1.0L, av = v == 0 ? a0 : 1.0L;
+            const long double ws = 0.25L * au * av * dct_kfactor(u) * dct_kfactor(v) / (long double)qs[0][u][v];
+            plan_band(ws, F[v][u], &w[v * 8 + u], &lim[v * 8 + u]);
+        }
+    return JPGX_OK;
+}
+
+extern "C" int jpgx_guard_band_gray(int quality, float scale[64], float lim[64])
+{
+    int16_t q[64];
+    if (!scale || !lim) return JPGX_EARG;
+    return jx_plan_tables_gray(quality, scale, lim, q);
 }

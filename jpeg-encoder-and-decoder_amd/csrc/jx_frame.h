@@ -125,6 +125,21 @@ JXF_FN int jx_frame_make_gray(int width, int height, jx_frame_gray *g)
     return 0;
 }
 
+/* The same frame as the JFIF coder walks it (the encode side's _gray entry points): one block per MCU,
+ * hs = vs = lum = bpm = 1, an MCU row is a block row (cbw = bw, cbh = bh), no chroma (nbc = 0, nblk = nb);
+ * jx_frame_block(f, my, mx, 0) is block my * bw + mx.  JXF_RANGE is all it refuses. */
+JXF_FN int jx_frame_make_gray_coded(int width, int height, jx_frame *f)
+{
+    jx_frame_gray g;
+    if (jx_frame_make_gray(width, height, &g)) return JXF_RANGE;
+    f->hs = f->vs = f->lum = f->bpm = 1u;
+    f->bw = f->cbw = g.bw;
+    f->bh = f->cbh = g.bh;
+    f->nb = f->nblk = g.nb;
+    f->nbc = 0u;
+    return 0;
+}
+
 /* The codes the entry points refuse with are part of the ABI and differ; each is one mapping of
  * the reason:            SAMPLE         RANGE           MULT8           MCU
  *   the JFIF coder       EARG           EARG            EARG            EGEOMETRY

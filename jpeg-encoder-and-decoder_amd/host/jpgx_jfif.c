@@ -28,6 +28,7 @@
 #include "../csrc/jx_consts.h"
 #include "../csrc/jpgx_internal.h"
 #include "../csrc/jx_frame.h"
+#include "../csrc/jx_jfif_gray.h"
 
 /* ITU-T T.81 Annex K.3, Tables K.3-K.6: code-length counts and symbol values */
 static const uint8_t kDcLumBits[16] = {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0};
@@ -177,6 +178,20 @@ int jpgx_jfif_qt(int quality, uint16_t qt[2][64])
     return JPGX_OK;
 }
 
+/* SOI and the APP0 segment every file of this writer begins with (JFIF 1.01, aspect 1:1, no thumbnail) */
+static void put_soi_app0(Out *o)
+{
+    put_u16(o, 0xffd8);                                    /* SOI */
+    put_u16(o, 0xffe0);                                    /* APP0 JFIF 1.01 */
+    put_u16(o, 16);
+    put_byte(o, 'J'); put_byte(o, 'F'); put_byte(o, 'I'); put_byte(o, 'F'); put_byte(o, 0);
+    put_u16(o, 0x0101);
+    put_byte(o, 0);
+    put_u16(o, 1);
+    put_u16(o, 1);
+    put_byte(o, 0); put_byte(o, 0);
+}
+
 /* SOI, APP0, DQT x 2, SOF, DHT x 4, DRI (ri != 0), SOS: see csrc/jpgx_internal.h */
 size_t jx_jfif_header(int width, int height, int quality, int sample_ratio, unsigned ri,
                       uint8_t *out, size_t cap)
@@ -193,15 +208,7 @@ size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio,
     uint32_t hs, vs;                                       /* Y sampling */
     jx_frame_sampling(sample_ratio, &hs, &vs);
     Out o = {out, 0, cap, 0};
-    put_u16(&o, 0xffd8);                                   /* SOI */
-    put_u16(&o, 0xffe0);                                   /* APP0 JFIF 1.01 */
-    put_u16(&o, 16);
-    put_byte(&o, 'J'); put_byte(&o, 'F'); put_byte(&o, 'I'); put_byte(&o, 'F'); put_byte(&o, 0);
-    put_u16(&o, 0x0101);
-    put_byte(&o, 0);
-    put_u16(&o, 1);
-    put_u16(&o, 1);
-    put_byte(&o, 0); put_byte(&o, 0);
+    put_soi_app0(&o);
     /* DQT: the divisors applied.  For q <= 23 some exceed 255 (q = 1: 6050); baseline allows
      * only 8-bit tables, so then both tables are written with 16-bit precision (Pq = 1) and
      * the frame is extended sequential (SOF1, same Huffman coding), as libjpeg does. */
@@ -253,6 +260,55 @@ size_t jx_jfif_header_tabs(int width, int height, int quality, int sample_ratio,
         put_byte(&o, (uint8_t)(c + 1));
         put_byte(&o, (uint8_t)(c ? 0x11 : 0x00));
     }
+    put_byte(&o, 0);
+    put_byte(&o, 63);
+    put_byte(&o, 0);
+    return o.n;
+}
+
+/* The header of a one-component file (csrc/jx_jfif_gray.h): SOI, the colour writer's APP0, one DQT
+ * (table 0: jpgx_jfif_qt(quality)[0]; 16-bit and SOF1 where an entry exceeds 255, as above), SOF with
+ * Nf = 1 (component 1, sampling 0x11, Tq 0), DHT DC 0x00 and AC 0x10, DRI (ri != 0, in blocks), SOS with
+ * Ns = 1, Td / Ta 0 / 0, Ss 0, Se 63 */
+size_t jx_jfif_header_gray(int width, int height, int quality, unsigned ri, const uint8_t bits[2][16],
+                           const uint8_t vals[2][256], uint8_t *out, size_t cap, size_t *dht_at)
+{
+    uint16_t zz[2][64];
+    if (jpgx_jfif_qt(quality, zz)) return 0;
+    Out o = {out, 0, cap, 0};
+    put_soi_app0(&o);
+    int wide = 0;
+    for (int k = 0; k < 64; k++)
+        if (zz[0][k] > 255) wide = 1;
+    put_u16(&o, 0xffdb);                                   /* DQT 0 */
+    put_u16(&o, (unsigned)(2 + 1 + 64 * (wide ? 2 : 1)));
+    put_byte(&o, (uint8_t)(wide << 4));
+    for (int k = 0; k < 64; k++) {
+        if (wide) put_u16(&o, (unsigned)zz[0][k]);
+        else put_byte(&o, (uint8_t)zz[0][k]);
+    }
+    put_u16(&o, wide ? 0xffc1 : 0xffc0);                   /* SOF1 / SOF0 */
+    put_u16(&o, 8 + 3);
+    put_byte(&o, 8);
+    put_u16(&o, (unsigned)height);
+    put_u16(&o, (unsigned)width);
+    put_byte(&o, 1);
+    put_byte(&o, 1);
+    put_byte(&o, 0x11);
+    put_byte(&o, 0);
+    if (dht_at) *dht_at = o.n;
+    put_dht(&o, 0x00, bits ? bits[0] : kDcLumBits, bits ? vals[0] : kDcVals);
+    put_dht(&o, 0x10, bits ? bits[1] : kAcLumBits, bits ? vals[1] : kAcLumVals);
+    if (ri) {                                              /* DRI (T.81 B.2.4.4) */
+        put_u16(&o, 0xffdd);
+        put_u16(&o, 4);
+        put_u16(&o, ri);
+    }
+    put_u16(&o, 0xffda);                                   /* SOS */
+    put_u16(&o, 6 + 2);
+    put_byte(&o, 1);
+    put_byte(&o, 1);
+    put_byte(&o, 0x00);
     put_byte(&o, 0);
     put_byte(&o, 63);
     put_byte(&o, 0);

@@ -18,7 +18,10 @@ The way there takes images of any size too: encode_blocks, jfif_gpu and encode_j
 (jpgx_blocks_gpu_any, jpgx_jfif_gpu_any) transform and code the image's coded frame, the image with its
 last column and row repeated up to the MCU (pad_edge), and the file states the image's own size.
 One-component (grayscale) files go through jfif_decode_gpu_gray and pixels_gpu_gray (the library's
-_gray entry points), or through decode_jpeg / decode_jpeg_coefficients with gray=True.
+_gray entry points), or through decode_jpeg / decode_jpeg_coefficients with gray=True.  The way there:
+encode_blocks_gray (jpgx_blocks_gpu_gray: a one-channel image of any size and any row pitch to Y
+[nb][64]), jfif_gpu_gray (jpgx_jfif_gpu_gray: those coefficients to one-component files), or
+encode_jpeg with gray=True; the contract is the project's own (include/jpgx.h).
 """
 from __future__ import annotations
 
@@ -65,6 +68,7 @@ EXPORTS = [
     "jpgx_pixels_gpu_any_workspace_size", "jpgx_pixels_gpu_any",
     "jpgx_jfif_decode_gpu_gray_workspace_size", "jpgx_jfif_decode_gpu_gray", "jpgx_pixels_gpu_gray",
     "jpgx_workspace_size_any", "jpgx_blocks_gpu_any", "jpgx_jfif_gpu_any_workspace_size", "jpgx_jfif_gpu_any",
+    "jpgx_blocks_gpu_gray", "jpgx_jfif_gpu_gray_workspace_size", "jpgx_jfif_gpu_gray", "jpgx_guard_band_gray",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -77,7 +81,7 @@ COMPAT_EXPORTS = [
     "jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub", "jpgx_pixels_host",
     "jpgx_jfif_info_of_any", "jpgx_read_jfif_any", "jpgx_read_jfif_sub_any", "jpgx_pixels_host_any",
     "jpgx_jfif_info_of_gray", "jpgx_read_jfif_gray", "jpgx_read_jfif_sub_gray", "jpgx_pixels_host_gray",
-    "jpgx_write_jfif_any", "jpgx_pad_edge", "jpgx_encode_rgb_to_jpeg_any",
+    "jpgx_write_jfif_any", "jpgx_pad_edge", "jpgx_encode_rgb_to_jpeg_any", "jpgx_write_jfif_gray",
 ]
 
 
@@ -177,6 +181,11 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_gpu_any_workspace_size.restype = sz
     L.jpgx_jfif_gpu_any.argtypes = L.jpgx_jfif_gpu_ex.argtypes
     L.jpgx_pad_edge.argtypes = [vp, i, i, sz, i, i, vp]
+    L.jpgx_blocks_gpu_gray.argtypes = [vp, sz, sz, sz, i, i, i, ctypes.c_uint, vp, sz, vp]
+    L.jpgx_jfif_gpu_gray_workspace_size.argtypes = [i, i, i, sz, sz, ctypes.c_uint]
+    L.jpgx_jfif_gpu_gray_workspace_size.restype = sz
+    L.jpgx_jfif_gpu_gray.argtypes = [vp, sz, sz, i, i, i, i, ctypes.c_uint, vp, sz, sz, vp, vp, sz, vp]
+    L.jpgx_guard_band_gray.argtypes = [i, vp, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -256,6 +265,14 @@ def guard_band(quality: int) -> tuple[np.ndarray, np.ndarray]:
     w = np.zeros((3, 64), np.float32)
     lim = np.zeros((3, 64), np.float32)
     _check(lib.jpgx_guard_band(quality, w.ctypes.data, lim.ctypes.data), "jpgx_guard_band")
+    return w, lim
+
+
+def guard_band_gray(quality: int) -> tuple[np.ndarray, np.ndarray]:
+    """jpgx_guard_band_gray: (scale, lim) float32 [64] of the one-channel forward path, [v * 8 + u]."""
+    w = np.zeros(64, np.float32)
+    lim = np.zeros(64, np.float32)
+    _check(lib.jpgx_guard_band_gray(quality, w.ctypes.data, lim.ctypes.data), "jpgx_guard_band_gray")
     return w, lim
 
 
@@ -359,12 +376,19 @@ def _frame(fn: str, width: int, height: int, sample_ratio: int, flags: int | Non
     per_frame = (nb + 2 * nbc) * 64
     if d_coef is None:
         return nb, nbc, per_frame, None
+    return nb, nbc, per_frame, _coef_stride(fn, d_coef, per_frame, "nb + 2 nbc", whole_blocks)
+
+
+def _coef_stride(fn: str, d_coef, per_frame: int, blocks: str, whole_blocks: bool = False) -> int:
+    """int16 elements between the frames of d_coef ([nframes][...]), each of which must be contiguous and
+    hold per_frame elements (`blocks` in the refusal), and with whole_blocks be laid out as the JFIF coder
+    needs it"""
     if not d_coef[0].is_contiguous() or d_coef[0].numel() < per_frame:
-        raise ValueError(f"{fn}: each frame must be contiguous and hold nb + 2 nbc blocks")
+        raise ValueError(f"{fn}: each frame must be contiguous and hold {blocks} blocks")
     stride = int(d_coef.stride(0)) if d_coef.shape[0] > 1 else int(d_coef[0].numel())
     if whole_blocks and (d_coef.data_ptr() % 16 or stride % 64):
         raise ValueError(f"{fn}: 16-byte aligned frames, a stride of whole blocks")
-    return nb, nbc, per_frame, stride
+    return stride
 
 
 # ---- the argument rules of the device entry points, each written once; fn: the public function's name
@@ -507,15 +531,41 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     compat.write_jfif_ex(..., optimize=True).  any_size: jpgx_jfif_gpu_any -- width and height are the
     file's own, any 1 .. 65535, d_coef holds the coded frames (encode_blocks(any_size=True)); byte for
     byte compat.write_jfif_ex(..., any_size=True)."""
+    return _jfif_gpu("jfif_gpu", d_coef, width, height, quality, restart_rows, cap, stream, optimize,
+                     sample_ratio=sample_ratio, any_size=any_size)
+
+
+def jfif_gpu_gray(d_coef, width: int, height: int, quality: int, restart_rows: int = -1, cap: int | None = None,
+                  stream=None, optimize: bool = False):
+    """jfif_gpu for one-component (grayscale) files (jpgx_jfif_gpu_gray): d_coef int16 [nframes][>= nb][64]
+    as encode_blocks_gray writes it, nb = ceil(W / 8) * ceil(H / 8), width and height any 1 .. 65535 ->
+    (out uint8 [nframes][cap], lens int64 [nframes]); frame f's file is byte for byte
+    compat.write_jfif_gray(coef, ..., restart_rows, nthreads=1) (restart_rows counts block rows; -1: one).
+    cap, the retry on capacity, stream and optimize as jfif_gpu's."""
+    return _jfif_gpu("jfif_gpu_gray", d_coef, width, height, quality, restart_rows, cap, stream, optimize, gray=True)
+
+
+def _jfif_gpu(fn: str, d_coef, width, height, quality, restart_rows, cap, stream, optimize, sample_ratio: int = 0,
+              any_size: bool = False, gray: bool = False):
+    """jfif_gpu and, with gray, jfif_gpu_gray: the library's call takes the frame's geometry as (width, height,
+    quality, sample_ratio), a one-component frame's as (width, height, quality); a frame holds _frame's blocks
+    or _gray_blocks'"""
     import torch
     if not _device_tensor(d_coef):
-        raise ValueError("jfif_gpu: d_coef must be a device tensor")
+        raise ValueError(f"{fn}: d_coef must be a device tensor")
     if d_coef.dtype != torch.int16 or d_coef.dim() < 2:
-        raise ValueError("jfif_gpu: d_coef must be an int16 [nframes][...] tensor")
-    _, _, per_frame, fstride = _frame("jfif_gpu", width, height, sample_ratio, d_coef=d_coef, whole_blocks=True,
-                                      any_size=any_size)
-    size_fn = lib.jpgx_jfif_gpu_any_workspace_size if any_size else lib.jpgx_jfif_gpu_workspace_size_ex
-    code_fn = lib.jpgx_jfif_gpu_any if any_size else lib.jpgx_jfif_gpu_ex
+        raise ValueError(f"{fn}: d_coef must be an int16 [nframes][...] tensor")
+    if gray:
+        per_frame = _gray_blocks(fn, width, height) * 64
+        fstride = _coef_stride(fn, d_coef, per_frame, "nb", whole_blocks=True)
+        size_fn, code_fn = lib.jpgx_jfif_gpu_gray_workspace_size, lib.jpgx_jfif_gpu_gray
+        size_geometry, geometry = (width, height), (width, height, quality)
+    else:
+        _, _, per_frame, fstride = _frame(fn, width, height, sample_ratio, d_coef=d_coef, whole_blocks=True,
+                                          any_size=any_size)
+        size_fn = lib.jpgx_jfif_gpu_any_workspace_size if any_size else lib.jpgx_jfif_gpu_workspace_size_ex
+        code_fn = lib.jpgx_jfif_gpu_any if any_size else lib.jpgx_jfif_gpu_ex
+        size_geometry, geometry = (width, height, sample_ratio), (width, height, quality, sample_ratio)
     nf = d_coef.shape[0]
     dev = d_coef.device
     cap = int(cap) if cap else max(1 << 20, per_frame // 2)
@@ -523,11 +573,10 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
     for attempt in range(2):
         out = torch.empty((nf, cap), dtype=torch.uint8, device=dev)
         lens = torch.empty(nf, dtype=torch.int64, device=dev)
-        need = int(size_fn(width, height, sample_ratio, restart_rows, nf, cap, jflags))
+        need = int(size_fn(*size_geometry, restart_rows, nf, cap, jflags))
         ws = _workspace(need, dev)          # synchronised below: nothing to keep it for
-        _check(code_fn(d_coef.data_ptr(), fstride, nf, width, height, quality, sample_ratio,
-                       restart_rows, jflags, out.data_ptr(), cap, cap, lens.data_ptr(),
-                       ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_jfif_gpu")
+        _check(code_fn(d_coef.data_ptr(), fstride, nf, *geometry, restart_rows, jflags, out.data_ptr(), cap, cap,
+                       lens.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(stream)), "jpgx_" + fn)
         if stream is not None:
             stream.synchronize()
         host = lens.cpu()
@@ -538,21 +587,33 @@ def jfif_gpu(d_coef, width: int, height: int, quality: int, sample_ratio: int = 
 
 
 def encode_jpeg(rgb, quality: int, sample_ratio: int = 0, flags: int = 0, restart_rows: int = -1,
-                optimize: bool = False, any_size: bool = False) -> bytes:
+                optimize: bool = False, any_size: bool = False, gray: bool = False) -> bytes:
     """One device image (H, W, 3 uint8 torch tensor on a GPU) -> its JFIF file: encode_blocks, then
     jfif_gpu, then a device-to-host copy of the file's bytes.  With FLAG_SUBSAMPLE and sample_ratio
     1 / 2 the file is 4:2:2 / 4:2:0, otherwise 4:4:4.  optimize: per-image Huffman tables (jfif_gpu).  any_size: an image of
     any width and height, 1 .. 65535 each: the file states H x W and codes the coded frame of its own
     sampling (pad_edge; the forward path gets the file's ratio, 0 without FLAG_SUBSAMPLE, so that both
-    agree on the MCU); decode_jpeg(..., any_size=True) reads it back."""
+    agree on the MCU); decode_jpeg(..., any_size=True) reads it back.  gray: the image is one channel,
+    (H, W) uint8 of any size, and the file a one-component one (encode_blocks_gray, jfif_gpu_gray; flags:
+    0 or FLAG_FORCE_EXACT, sample_ratio unused); decode_jpeg(..., gray=True) reads it back.  The default
+    refuses a 2-D tensor."""
     import torch
     if not _device_tensor(rgb):
         raise ValueError("encode_jpeg: rgb must be a device tensor")
-    H, W = int(rgb.shape[0]), int(rgb.shape[1])
-    sub = sample_ratio if flags & FLAG_SUBSAMPLE else 0
-    coef = encode_blocks(rgb, quality, sub if any_size else sample_ratio,
-                         flags=flags if sub else flags & ~FLAG_SUBSAMPLE, any_size=any_size)
-    out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows, optimize=optimize, any_size=any_size)
+    if gray:
+        if rgb.dim() != 2:
+            raise ValueError("encode_jpeg: gray=True takes an (H, W) uint8 tensor")
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        coef = encode_blocks_gray(rgb, quality, flags=flags)
+        out, lens = jfif_gpu_gray(coef.reshape(1, -1), W, H, quality, restart_rows, optimize=optimize)
+    else:
+        if rgb.dim() != 3:
+            raise ValueError("encode_jpeg: rgb must be (H, W, 3) uint8; a one-channel image takes gray=True")
+        H, W = int(rgb.shape[0]), int(rgb.shape[1])
+        sub = sample_ratio if flags & FLAG_SUBSAMPLE else 0
+        coef = encode_blocks(rgb, quality, sub if any_size else sample_ratio,
+                             flags=flags if sub else flags & ~FLAG_SUBSAMPLE, any_size=any_size)
+        out, lens = jfif_gpu(coef.reshape(1, -1), W, H, quality, sub, restart_rows, optimize=optimize, any_size=any_size)
     n = int(lens[0])
     if n < 0:
         raise JpgxError(EARG, "jpgx_jfif_gpu (capacity)")
@@ -716,10 +777,7 @@ def _pixels(fn: str, d_coef, width, height, d_qt, status, out, pitch, stream, sa
         raise ValueError(f"{fn}: channels must be 1 or 3")
     nf = int(d_coef.shape[0])
     if gray:
-        nb = _gray_blocks(fn, width, height)
-        if not d_coef[0].is_contiguous() or d_coef[0].numel() < nb * 64:
-            raise ValueError(f"{fn}: each frame must be contiguous and hold nb blocks")
-        cstride = int(d_coef.stride(0)) if nf > 1 else int(d_coef[0].numel())
+        cstride = _coef_stride(fn, d_coef, _gray_blocks(fn, width, height) * 64, "nb")
     else:
         _, _, _, cstride = _frame(fn, width, height, sample_ratio, d_coef=d_coef, any_size=any_size)
     qstride = _qt_stride(fn, d_qt, nf, 64 if gray else 128)
@@ -848,6 +906,39 @@ def _encode_blocks_any(rgb, W, H, quality, sample_ratio, underflow, flags, devic
     _check(lib.jpgx_blocks_gpu_any(ctypes.byref(fr), ctypes.byref(p), rgb.data_ptr(), out.data_ptr(),
                                    ws.data_ptr(), need, _stream_ptr(stream)), "jpgx_blocks_gpu_any")
     return out
+
+
+def encode_blocks_gray(gray, quality: int, flags: int = 0, stream=None):
+    """One-channel images on a GPU -> their coefficients (jpgx_blocks_gpu_gray, one launch of k_gray):
+    gray uint8 [H][W] or [n][H][W], W and H any 1 .. 65535, of any strides as long as the pixels of a row
+    are adjacent and the rows top-down (a slice of a wider tensor is read where it is, whatever its pitch and
+    alignment; frames may overlap or be one frame expanded, the input is only read) ->
+    int16 [nb][64] or [n][nb][64], nb = ceil(W / 8) * ceil(H / 8) blocks in raster order: the frame of
+    jfif_decode_gpu_gray and pixels_gpu_gray, the pixels beyond the image by the edge rule.  flags: 0 or
+    FLAG_FORCE_EXACT.  Nothing is copied to the host and nothing waits."""
+    import torch
+    if not _device_tensor(gray):
+        raise ValueError("encode_blocks_gray: gray must be a device tensor")
+    if gray.dtype != torch.uint8 or gray.dim() not in (2, 3):
+        raise ValueError("encode_blocks_gray: gray must be (H, W) or (n, H, W) uint8")
+    batch = gray if gray.dim() == 3 else gray.unsqueeze(0)
+    nf, H, W = (int(x) for x in batch.shape)
+    nb = _gray_blocks("encode_blocks_gray", W, H)
+    if nf == 0:
+        raise ValueError("encode_blocks_gray: no frames")
+    if W > 1 and batch.stride(2) != 1:
+        raise ValueError("encode_blocks_gray: the pixels of a row must be adjacent")
+    pitch = int(batch.stride(1)) if H > 1 else W
+    fstride = int(batch.stride(0)) if nf > 1 else pitch * H
+    if pitch < W:
+        raise ValueError("encode_blocks_gray: rows top-down with a pitch >= W")
+    out = torch.empty((nf, nb, 64), dtype=torch.int16, device=gray.device)
+    _check(lib.jpgx_blocks_gpu_gray(batch.data_ptr(), pitch, fstride, nf, W, H, quality, flags, out.data_ptr(),
+                                    nb * 64, _stream_ptr(stream)), "jpgx_blocks_gpu_gray")
+    if stream is not None:
+        gray.record_stream(stream)
+        out.record_stream(stream)
+    return out if gray.dim() == 3 else out[0]
 
 
 def encode_blocks_multi(rgb: np.ndarray, quality: int, ngpus: int, sample_ratio: int = 0,

@@ -101,6 +101,8 @@ def _setup(L):
                                           ctypes.c_uint, i]
     L.jpgx_encode_rgb_to_jpeg_any.argtypes = L.jpgx_encode_rgb_to_jpeg.argtypes
     L.jpgx_write_jfif_any.argtypes = L.jpgx_write_jfif_opt.argtypes
+    L.jpgx_write_jfif_gray.argtypes = [vp, i, i, i, i, i, ctypes.c_uint, vp, ctypes.c_size_t,
+                                       ctypes.POINTER(ctypes.c_size_t)]
 
 
     L.jpgx_jfif_info_of.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(JfifInfo)]
@@ -287,6 +289,29 @@ def write_jfif_ex(coef: np.ndarray, width: int, height: int, quality: int, sampl
         cap = n.value
     _check(rc, "jpgx_write_jfif_ex")
     raise JpgxError(rc, "jpgx_write_jfif_ex")
+
+
+def write_jfif_gray(coef: np.ndarray, width: int, height: int, quality: int, restart_rows: int = 0,
+                    nthreads: int = 1, optimize: bool = False, cap: int | None = None) -> bytes:
+    """jpgx_write_jfif_gray: int16 Y [nb][64], nb = ceil(width / 8) * ceil(height / 8), -> the bytes of a
+    one-component baseline file of width x height, any 1 .. 65535 (read_jfif_gray reads it back).
+    restart_rows counts block rows (-1 auto, 0 none); nthreads, optimize and cap as write_jfif_ex's."""
+    coef = np.ascontiguousarray(coef, np.int16)
+    if 0 < width < 65536 and 0 < height < 65536 and coef.size < ((width + 7) // 8) * ((height + 7) // 8) * 64:
+        raise ValueError("write_jfif_gray: coef must hold ceil(width / 8) * ceil(height / 8) blocks")
+    n = ctypes.c_size_t()
+    cap = cap or max(1 << 20, coef.size // 2)
+    for _ in range(2):
+        buf = np.empty(cap, np.uint8)
+        rc = lib.jpgx_write_jfif_gray(coef.ctypes.data, width, height, quality, restart_rows, nthreads,
+                                      1 if optimize else 0, buf.ctypes.data, cap, ctypes.byref(n))
+        if rc == 0:
+            return buf[:n.value].tobytes()
+        if rc != -4 or n.value <= cap:                      # JPGX_EARG with the size needed
+            break
+        cap = n.value
+    _check(rc, "jpgx_write_jfif_gray")
+    raise JpgxError(rc, "jpgx_write_jfif_gray")
 
 
 def write_jfif_sub(coef: np.ndarray, width: int, height: int, quality: int,

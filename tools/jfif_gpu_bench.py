@@ -94,8 +94,25 @@ taken in turn, several passes, in one process:
                   own and named by --kernel-stats=FILE.csv (rocprofv3 --kernel-trace --stats); absent without one
   bytes_equal     every frame's coefficients == jpgx_blocks_gpu's for the image padded by torch's replicate rule,
                   and frame 0's file == jpgx_write_jfif_any's on the host; repeat_equal: the same after the timed calls
+With --encode-gray the run times the encode side of the one-component family (jpgx_blocks_gpu_gray = k_gray,
+jpgx_jfif_gpu_gray) on 8 one-channel frames of 3840 x 2160 and of 3839 x 2159 (the inputs' top left,
+rows 3839 bytes apart) at q 90 and writes profiles/jfif_gpu_enc_gray.json.  The inputs are --gray's (noise, and flat
+8 x 8 tiles plus +-6 of noise).  Per input:
+  gray_xform_us, rgb_xform_us     jpgx_blocks_gpu_gray on the 3840 x 2160 frames and jpgx_blocks_gpu on the same frames
+                  as R = G = B, taken in turn, several passes, in one process (events around 10 calls; all passes,
+                  sorted); gray_over_rgb: the medians' ratio, which must be below 1 (the gate; exit status 1 otherwise)
+  gray_fraction_of_8TBps          3 B per pixel (1 read, 2 written) over gray_xform_us's minimum
+  flagged_share   {quality: flagged coefficients / coefficients} at q 50, 90, 97: k_gray's fp32 sequence and band on
+                  the host (jx_selftest_gray_blocks) over the first 20,000 blocks of frame 0; blocks_with_a_flag likewise
+and per size ("3840x2160", "3839x2159"):
+  xform_us        jpgx_blocks_gpu_gray per batch (events, as above; all rounds, sorted); fraction_of_8TBps
+  coder_us, coder_opt_us          jpgx_jfif_gpu_gray per batch, standard and JPGX_JFIF_OPTIMIZE, one block row per interval
+  host_route_s    the coefficients copied to pinned host memory + jpgx_write_jfif_gray, restart_rows 1, 16 threads,
+                  frame after frame; best of 2
+  bytes_equal     frame 0's coefficients == k_gray's restatement on the host (jx_gray_host_blocks), and frame 0's
+                  files, standard and optimised, == jpgx_write_jfif_gray's; repeat_equal: the same after the timed calls
 Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels [--any-size
-[--parent-lib=PATH]] | --gray [--gray-files=DIR] | --encode-any [--kernel-stats=FILE.csv]] [OUT.json]"""
+[--parent-lib=PATH]] | --gray [--gray-files=DIR] | --encode-any [--kernel-stats=FILE.csv] | --encode-gray] [OUT.json]"""
 import json
 import os
 import sys
@@ -924,9 +941,151 @@ def main_gray(dst):
     sys.exit(0 if ok else 1)
 
 
+def measure_enc_gray(name, images, dev):
+    import ctypes
+    stream = torch.cuda.current_stream().cuda_stream
+    L = jpgx.lib
+    L.jx_gray_host_blocks.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_void_p]
+    L.jx_selftest_gray_blocks.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                          ctypes.POINTER(ctypes.c_longlong), ctypes.c_void_p]
+    L.jx_selftest_gray_blocks.restype = ctypes.c_longlong
+    res = {"input": name}
+    ok = again = True
+    full = {}
+    for VW, VH in ((W, H), (W - 1, H - 1)):
+        bw, bh = (VW + 7) // 8, (VH + 7) // 8
+        nb = bw * bh
+        per = nb * 64
+        host_img = np.ascontiguousarray(images[:, :VH, :VW])
+        d = torch.from_numpy(host_img).to(dev)
+        coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+
+        def fwd(d=d, coef=coef, VW=VW, VH=VH, per=per):        # bound now: the gate below calls the first size's
+            rc = L.jpgx_blocks_gpu_gray(d.data_ptr(), VW, VW * VH, F, VW, VH, Q, 0, coef.data_ptr(), per, stream)
+            assert rc == 0, rc
+
+        want0 = np.empty((nb, 64), np.int16)
+        rc = L.jx_gray_host_blocks(host_img[0].ctypes.data, VW, VH, VW, Q, 0, want0.ctypes.data)
+        assert rc == 0, rc
+        coef.fill_(0x5A5A)
+        fwd()
+        torch.cuda.synchronize()
+        ok = ok and bool(np.array_equal(coef[0].cpu().numpy().reshape(nb, 64), want0))
+        part = {"blocks_per_frame": nb, "xform_us": timed(fwd)}
+        part["fraction_of_8TBps"] = 3 * F * VW * VH / (part["xform_us"][0] * 1e-6) / 8e12
+
+        _, lens0 = jpgx.jfif_gpu_gray(coef, VW, VH, Q, 1, cap=1 << 20)
+        cap = (int(lens0.max()) + 4095) // 4096 * 4096
+        out = torch.empty((F, cap), dtype=torch.uint8, device=dev)
+        lens = torch.empty(F, dtype=torch.int64, device=dev)
+        files0 = {}
+        for key, flags in (("coder_us", 0), ("coder_opt_us", jpgx.JFIF_OPTIMIZE)):
+            wsb = int(L.jpgx_jfif_gpu_gray_workspace_size(VW, VH, 1, F, cap, flags))
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+
+            def coder():
+                rc = L.jpgx_jfif_gpu_gray(coef.data_ptr(), per, F, VW, VH, Q, 1, flags, out.data_ptr(), cap, cap,
+                                          lens.data_ptr(), ws.data_ptr(), wsb, stream)
+                assert rc == 0, rc
+
+            def file0():
+                return out[0, :int(lens[0])].cpu().numpy().tobytes()
+
+            host = C.write_jfif_gray(want0, VW, VH, Q, restart_rows=1, nthreads=HOST_THREADS, optimize=bool(flags), cap=cap)
+            coder()
+            torch.cuda.synchronize()
+            ok = ok and file0() == host
+            part[key] = timed(coder)
+            again = again and file0() == host
+            files0[key] = len(host)
+        part["file_bytes_frame0"], part["file_bytes_frame0_opt"] = files0["coder_us"], files0["coder_opt_us"]
+        part["opt_over_std"] = median(part["coder_opt_us"]) / median(part["coder_us"])
+        # the host route: D2H of the coefficients into pinned memory + the host writer, frame after frame
+        pinned = torch.empty((F, per), dtype=torch.int16).pin_memory()
+        buf = np.empty(cap, np.uint8)
+        n = ctypes.c_size_t()
+        host_s = []
+        for _ in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pinned.copy_(coef)
+            torch.cuda.synchronize()
+            for f in range(F):
+                rc = L.jpgx_write_jfif_gray(pinned.data_ptr() + f * per * 2, VW, VH, Q, 1, HOST_THREADS, 0,
+                                            buf.ctypes.data, cap, ctypes.byref(n))
+                assert rc == 0, rc
+            host_s.append(time.perf_counter() - t0)
+        part["host_route_s"], part["host_threads"] = min(host_s), HOST_THREADS
+        part["speedup"] = min(host_s) / (median(part["coder_us"]) * 1e-6)
+        fwd()
+        torch.cuda.synchronize()
+        again = again and bool(np.array_equal(coef[0].cpu().numpy().reshape(nb, 64), want0))
+        res["%dx%d" % (VW, VH)] = part
+        if (VW, VH) == (W, H):
+            full = {"d": d, "coef": coef, "fwd": fwd}
+        del out, pinned
+
+    # the gate: the same frames as R = G = B through jpgx_blocks_gpu, the two taken in turn
+    per3 = 3 * (W // 8) * (H // 8) * 64
+    d_rgb = full["d"].unsqueeze(3).expand(F, H, W, 3).contiguous()
+    coef3 = torch.empty((F, per3), dtype=torch.int16, device=dev)
+    fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per3)
+    p = jpgx.default_params(W, H, Q, 0)
+    xws = torch.empty(max(jpgx.workspace_size(fr), 16), dtype=torch.uint8, device=dev)
+
+    def rgb_xform():
+        jpgx.blocks_gpu(fr, p, d_rgb, coef3, xws)
+
+    calls = (("gray_xform_us", full["fwd"]), ("rgb_xform_us", rgb_xform))
+    ts = {k: [] for k, _ in calls}
+    for _ in range(7):
+        for k, fn in calls:
+            ts[k] += timed(fn, rounds=1, settle=0.2)
+    ts = {k: sorted(v) for k, v in ts.items()}
+    res.update(ts)
+    res["gray_over_rgb"] = median(ts["gray_xform_us"]) / median(ts["rgb_xform_us"])
+    res["gray_fraction_of_8TBps"] = 3 * F * W * H / (ts["gray_xform_us"][0] * 1e-6) / 8e12
+    res["rgb_fraction_of_8TBps"] = 9 * F * W * H / (ts["rgb_xform_us"][0] * 1e-6) / 8e12
+    res["gate_gray_below_rgb"] = bool(res["gray_over_rgb"] < 1.0)
+
+    # the flagged share: the kernel's fp32 sequence and band on the host, over frame 0's first blocks
+    nsample = 20000
+    blocks = np.ascontiguousarray(images[0, :H // 8 * 8, :W].reshape(H // 8, 8, W // 8, 8).transpose(0, 2, 1, 3)
+                                  .reshape(-1, 64)[:nsample])
+    res["flagged_share"], res["blocks_with_a_flag"] = {}, {}
+    for q in (50, 90, 97):
+        flagged = ctypes.c_longlong()
+        mask = np.zeros(len(blocks), np.uint64)
+        bad = L.jx_selftest_gray_blocks(blocks.ctypes.data, len(blocks), q, ctypes.byref(flagged), mask.ctypes.data)
+        ok = ok and bad == 0
+        res["flagged_share"][str(q)] = flagged.value / (64.0 * len(blocks))
+        res["blocks_with_a_flag"][str(q)] = float((mask != 0).mean())
+    res["bytes_equal"], res["repeat_equal"] = bool(ok), bool(again)
+    return res
+
+
+def main_enc_gray(dst):
+    assert torch.cuda.is_available(), "needs a GPU"
+    dev = torch.device("cuda:0")
+    res = {"what": "tools/jfif_gpu_bench.py --encode-gray", "width": W, "height": H, "frames": F, "quality": Q,
+           "restart_rows": 1, "device": torch.cuda.get_device_name(0), "version": jpgx.version(), "runs": []}
+    for name, _, images in gray_inputs():
+        res["runs"].append(measure_enc_gray(name, images, dev))
+        print(json.dumps(res["runs"][-1]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
+    with open(dst, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    ok = all(r["bytes_equal"] and r["repeat_equal"] for r in res["runs"])
+    gate = all(r["gate_gray_below_rgb"] for r in res["runs"])
+    print("bytes equal:", ok, " gate (gray below rgb):", gate)
+    sys.exit(0 if ok and gate else 1)
+
+
 def main():
     global PARENT, GRAY_FILES, KERNEL_STATS
-    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size", "--gray", "--encode-any")
+    modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size", "--gray", "--encode-any", "--encode-gray")
     for a in sys.argv[1:]:
         if a.startswith("--parent-lib="):
             # an older build has only the plain entry points: bind the one call that is timed
@@ -938,7 +1097,10 @@ def main():
         if a.startswith("--kernel-stats="):
             KERNEL_STATS = os.path.abspath(a.split("=", 1)[1])
     args = [a for a in sys.argv[1:] if a not in modes and not a.startswith(("--parent-lib=", "--gray-files=", "--kernel-stats="))]
-    optimize, decoding, pixels, sub, any_size, gray, enc_any = (m in sys.argv[1:] for m in modes)
+    optimize, decoding, pixels, sub, any_size, gray, enc_any, enc_gray = (m in sys.argv[1:] for m in modes)
+    if enc_gray:
+        assert not (optimize or decoding or pixels or gray or enc_any), "--encode-gray stands alone"
+        return main_enc_gray(args[0] if args else os.path.join(REPO, "profiles", "jfif_gpu_enc_gray.json"))
     assert not enc_any or not (optimize or decoding or pixels or gray), "--encode-any stands alone"
     if gray:
         assert not (optimize or decoding or pixels), "--gray stands alone"
