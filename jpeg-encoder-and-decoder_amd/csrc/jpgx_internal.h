@@ -65,19 +65,11 @@ struct jx_limtab {
 #define JX_MAXQ 97
 
 /* k_mxs, k_mxs422, k_mxs420 (csrc/jpgx_mx.hip): the colour conversion + row DCT of each pixel row
- * is an f16 MFMA product with B split into JX_MX_PARTS f16 parts (hi exact, lo parts scaled by
- * 2^JX_MX_LOEXP).  Per quality, plan column n = 8c + u holds the scales and guard band of
- * coefficients (c, u, v = 0..7). */
-#ifndef JX_MX_PARTS
-#define JX_MX_PARTS 2       /* 2: hi + one lo part (band 1.28x that of 3 parts, 16 MFMAs per
-                               8 blocks instead of 24: jpgx_plan.cpp's bound covers either) */
-#endif
-/* scale of the lo f16 parts of B (exponent): 0 stores them at the hi parts' scale, so R = acc_h +
- * acc_l is one add (round 4); 12 stores them x 2^12 (R = fma(acc_l, 2^-12, acc_h), rounds 2-3).
- * Either way R = fl(acc_h + acc_l) bit for bit. */
-#ifndef JX_MX_LOEXP
-#define JX_MX_LOEXP 0
-#endif
+ * is an f16 MFMA product with B split into two f16 parts: hi (its products exact) and lo, stored
+ * at the hi part's scale, so R = acc_h + acc_l is one add.  Per quality, plan column n = 8c + u
+ * holds the scales and guard band of coefficients (c, u, v = 0..7).  (Earlier rounds built a third
+ * part and a lo part stored x 2^12; DESIGN.md 4.3 records what they measured.) */
+#define JX_MX_PARTS 2       /* sizes the operand arrays of the plan / kernel interface */
 struct jx_mxtab {
     float w[24][8];         /* 1/4 a(u) a(v) k(v) / Q[u][v] (row transform uses exact cosines) */
     float lsq[24][8];       /* a float <= lim^2 of the rigorous band (flag: d*d - lsq >= 0);

@@ -74,7 +74,7 @@ typedef uint32_t mx_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t mx_u2 __attribute__((ext_vector_type(2)));
 
 constexpr float kMagic = 12582912.0f;   /* 1.5 * 2^23: x + kMagic rounds x to an integer     */
-constexpr int kParts = JX_MX_PARTS;     /* f16 parts of B: hi (exact products) + lo [+ lo2]  */
+constexpr int kParts = JX_MX_PARTS;     /* f16 parts of B: hi (exact products) + lo           */
 constexpr unsigned kSlot = 1536;        /* one step's pixels: [y][8 blocks x 24 B]           */
 constexpr int kWPE = 4;                 /* waves per SIMD the register allocation targets    */
 
@@ -251,27 +251,17 @@ typedef __attribute__((address_space(3))) void *mx_lp;
 typedef const __attribute__((address_space(1))) void *mx_gp;
 
 /*
- * The pixels of the step starting at block b0 (position P) into `slot` ([y][24 jb + k]).
- * Simple steps: two LDS-DMA instructions of 16-byte pieces (piece p = lane, and 64 + lane for
- * lanes < 32: row p / 12, bytes 16 (p % 12); the LDS destination of an LDS-DMA is base + 16 lane
- * for 12- and 16-byte pieces alike, so the slot is filled contiguously).  Other steps (a row's
- * last block, row or frame crossings, the launch's last step): lane l loads pixel row y = l & 7
+ * The pixels of the general step starting at block b0 into `slot` ([y][24 jb + k]), through
+ * registers (simple steps take the LDS-DMA of mxs_issue).  A general step holds a row's last block,
+ * a row or frame crossing or the launch's end: lane l loads pixel row y = l & 7
  * of block jb = l >> 3 with the reference's addressing -- blockToCoords (preprocess.c:199-211)
  * gives x0 = -8 for the last block of a block-row, i.e. pixel row 8r + y - 1, columns W-8..W-1,
  * and at frame block-row 0, y = 0 those are the bytes in front of the planes (g.u) -- and
  * writes it to the slot itself; it waits for every outstanding VMEM operation (rare), so the
  * caller's vmcnt accounting, which counts two DMA operations per step, stays conservative.
  */
-__device__ __forceinline__ void mx_issue(const MxG &g, const MxCur &P, unsigned b0, bool simple,
-                                         uint32_t off0, uint32_t off1, uint8_t *slot)
+__device__ __forceinline__ void mx_fill_general(const MxG &g, unsigned b0, uint8_t *slot)
 {
-    if (simple) {
-        const uint8_t *base = P.src;
-        __builtin_amdgcn_global_load_lds((mx_gp)(base + off0), (mx_lp)slot, 16, 0, 0);
-        if (mx_lane() < 32)
-            __builtin_amdgcn_global_load_lds((mx_gp)(base + off1), (mx_lp)(slot + 1024u), 16, 0, 0);
-        return;
-    }
     const unsigned lane = mx_lane(), y = lane & 7u, jb = lane >> 3;
     unsigned b = b0 + jb;
     b = b < g.total ? b : g.total - 1u;
@@ -627,8 +617,7 @@ __device__ __forceinline__ uint32_t mx_flags(const float (&F)[8], const float (&
 }
 
 /* R rows 0..7 of one column from the lo (rows 0..3) and hi (rows 4..7) tiles: the lo B part is
- * encoded at the hi part's scale (JX_MX_LOEXP = 0), so R = fl(acc_h + acc_l) */
-static_assert(JX_MX_LOEXP == 0, "the kernels take R = acc_h + acc_l");
+ * encoded at the hi part's scale, so R = fl(acc_h + acc_l) */
 __device__ __forceinline__ void mx_combine(mx_f4 hl, mx_f4 ll, mx_f4 hh, mx_f4 lh, float (&R)[8])
 {
     R[0] = ll.x + hl.x, R[1] = ll.y + hl.y, R[2] = ll.z + hl.z, R[3] = ll.w + hl.w;
@@ -854,8 +843,6 @@ struct alignas(16) MxsImg {
     uint8_t scan_t[8][8];               /* zig-zag position of (v, u) at [u][v] */
     MxExTab ex;                         /* the exact pass's tables                      */
 };
-constexpr unsigned kMxsPieces = sizeof(MxsImg) / 16;
-static_assert(sizeof(MxsImg) % 16 == 0 && kMxsPieces <= 768, "three 16-byte pieces per thread");
 static_assert(sizeof(MxsLds) * kMxsWPG + sizeof(MxsImg) <= 40 * 1024, "4 workgroups of 4 waves per CU");
 __device__ MxsImg g_mxs_img[2][JX_MAXQ + 1];     /* [force][quality] */
 
@@ -939,6 +926,58 @@ __device__ __forceinline__ void mxs_issue(const MxsCur &P, const MxG &g, uint8_t
     }
 }
 
+/* ---- scaffolding the kernels share (outside a step's matrix sequence).  k_mxs422 keeps its own
+ * image loop and Y selectors: with the shared ones its ISA differs from the measured one by two
+ * instructions and its median in the same-machine A/B lay outside the noise
+ * (profiles/mx_fold_ab.txt) ------------------------------------------------------------------- */
+
+/* The workgroup image `src` into LDS at `dst`, by the workgroup's WPG waves: LDS-DMA of 16-byte
+ * pieces, piece p of thread t lands at 16 p */
+template <unsigned WPG, class Img>
+__device__ __forceinline__ void mx_image_dma(const Img &src, Img &dst, unsigned wave)
+{
+    static_assert(sizeof(Img) % 16 == 0, "16-byte pieces");
+    constexpr unsigned kPieces = sizeof(Img) / 16, kT = 64u * WPG;
+    const uint8_t *img = (const uint8_t *)&src;
+#pragma unroll
+    for (unsigned i = 0; i < (kPieces + kT - 1u) / kT; i++) {
+        const unsigned piece = kT * i + threadIdx.x;
+        if (kT * i + 64u * wave < kPieces && piece < kPieces)
+            mxs_dma<16>(img + 16u * piece, (uint8_t *)&dst + 16u * (kT * i + 64u * wave));
+    }
+}
+
+/* The Y A operand of lane (m = lane & 15, q = lane >> 4): C row m is pixel row m & 3 of the half
+ * (rows `pitch` bytes apart) of block m >> 2, its bytes 8 q .. 8 q + 7 at slot offset off; the
+ * selectors turn them into k = 8 q .. 8 q + 7 (mx_aop).  Lanes 48..63 (the bias / zero rows
+ * k = 24..31) use no pixel byte: they read lanes 32..47's addresses, an LDS broadcast (round 6:
+ * their own addresses made every A read 2-way in the upper half of the wave) */
+struct MxYop {
+    uint32_t off, s0, s1, s2;
+};
+__device__ __forceinline__ MxYop mx_yop(unsigned lane, unsigned pitch)
+{
+    const unsigned m = lane & 15u, q = lane >> 4;
+    return MxYop{pitch * (m & 3u) + 24u * (m >> 2) + 8u * (q < 3 ? q : 2u), q < 3 ? kSelLo : kSelOne,
+                 q < 3 ? kSelHi : kSelZero, q < 3 ? kSelLo : kSelZero};
+}
+
+/* k_mxs422's / k_mxs420's B operands of lane l from the image's [part * T + which]: which 0 holds
+ * the two Y sets merged (lane l keeps set (l & 15) / 8's), so B[p][0] / B[p][1] get it or zeros;
+ * the T - 1 chroma K steps follow */
+template <unsigned T>
+__device__ __forceinline__ void mx_load_b(mx_u4 (&B)[kParts][T + 1], const mx_u4 (&img)[kParts * T][64], unsigned l)
+{
+#pragma unroll
+    for (int p = 0; p < kParts; p++) {
+        const mx_u4 by = img[T * p][l], zero = {};
+        B[p][0] = (l & 15u) < 8 ? by : zero;
+        B[p][1] = (l & 15u) < 8 ? zero : by;
+#pragma unroll
+        for (unsigned w = 2; w < T + 1; w++) B[p][w] = img[T * p + w - 1][l];
+    }
+}
+
 __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args a)
 {
     __shared__ __attribute__((aligned(16))) MxsLds s_lds[kMxsWPG];
@@ -967,16 +1006,7 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
     mx_u4 B[3];                                  /* older than every DMA of the wave */
 #pragma unroll
     for (int w = 0; w < 3; w++) B[w] = g_mxs_B[w][lane];
-    /* the image into LDS (LDS-DMA: piece p of thread t lands at 16 p) */
-    {
-        const uint8_t *img = (const uint8_t *)&g_mxs_img[g.force ? 1 : 0][g.quality];
-#pragma unroll
-        for (unsigned i = 0; i < (kMxsPieces + 64u * kMxsWPG - 1u) / (64u * kMxsWPG); i++) {
-            const unsigned piece = 64u * kMxsWPG * i + threadIdx.x;
-            if (64u * kMxsWPG * i + 64u * wave < kMxsPieces && piece < kMxsPieces)
-                mxs_dma<16>(img + 16u * piece, (uint8_t *)&s_img + 16u * (64u * kMxsWPG * i + 64u * wave));
-        }
-    }
+    mx_image_dma<kMxsWPG>(g_mxs_img[g.force ? 1 : 0][g.quality], s_img, wave);
     /* this wave's steps' DMA */
     const unsigned wv = blockIdx.x * kMxsWPG + wave;
     const uint32_t off0 = (uint32_t)((lane / 12u) * (unsigned)g.pitch + 16u * (lane % 12u));
@@ -991,14 +1021,8 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
     }
 
     /* lane constants */
-    const unsigned m = lane & 15u, q = lane >> 4;
-    /* lanes 48..63 (the bias / zero rows k = 24..31) use no pixel byte: they read lanes 32..47's
-     * addresses, an LDS broadcast (round 6: their own addresses made every A read 2-way in the
-     * upper half of the wave) */
-    const uint32_t aoff = 192u * (m & 3u) + 24u * (m >> 2) + 8u * (q < 3 ? q : 2u);
-    const uint32_t s0 = q < 3 ? kSelLo : kSelOne;
-    const uint32_t s1 = q < 3 ? kSelHi : kSelZero;
-    const uint32_t s2 = q < 3 ? kSelLo : kSelZero;
+    const MxYop yop = mx_yop(lane, 192u);
+    const uint32_t aoff = yop.off, s0 = yop.s0, s1 = yop.s1, s2 = yop.s2;
     const uint32_t so0 = lane * 16u, so1 = so0 + g.nb * 128u, so2 = so1 + g.nb * 128u;
     const uint32_t ro = mx_ro(lane);                          /* mxs_piece(lane >> 3, lane & 7) */
     const uint32_t rr = (ro ^ (lane & 32u)) + 1024u + ((lane & 32u) << 5);   /* Cr: slots 8..11, 20..23 */
@@ -1033,9 +1057,7 @@ __global__ __launch_bounds__(64 * kMxsWPG, kWPE) void k_mxs(const jx_xform_args 
     /* one step from `sp` (its DMA has landed): transform, inline exact pass, three stores */
     const auto body = [&](const MxsCur &S, uint8_t *sp) __attribute__((always_inline)) {
         if (!S.simple) {
-            MxCur P;
-            mx_seek(P, g, S.b);
-            mx_issue(g, P, S.b, false, off0, off1, sp);      /* register path; waits vmcnt(0) */
+            mx_fill_general(g, S.b, sp);                /* register path; waits vmcnt(0) */
         }
         mx_wave_sync();
         const mx_u2 d00 = *(const mx_u2 *)(sp + aoff);
@@ -1383,26 +1405,14 @@ __global__ __launch_bounds__(64 * kMxs422WPG, kWPE) void k_mxs422(const jx_xform
     }
     /* the B operands; reloaded after an exact pass, so that their registers are free during it */
     mx_u4 B[kParts][4];
-    const auto load_b = [&](unsigned l) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < kParts; p++) {
-            const mx_u4 by = s_img.B[3 * p][l], zero = {};
-            B[p][0] = (l & 15u) < 8 ? by : zero;
-            B[p][1] = (l & 15u) < 8 ? zero : by;
-            B[p][2] = s_img.B[3 * p + 1][l];
-            B[p][3] = s_img.B[3 * p + 2][l];
-        }
-    };
-    load_b(lane);
+    mx_load_b<3>(B, s_img.B, lane);
     const float limc0 = s_img.limc[0][j], limc2 = s_img.limc[1][j];
     const MxTab &tb = s_img.tab;
     const MxExLds xt{s_img.ex, s_img.scan_t};
 
     const auto body = [&](const MxsCur &S, uint8_t *sp) __attribute__((always_inline)) {
         if (!S.simple) {
-            MxCur P;
-            mx_seek(P, g, S.b);
-            mx_issue(g, P, S.b, false, off0, off1, sp);      /* register path; waits vmcnt(0) */
+            mx_fill_general(g, S.b, sp);                /* register path; waits vmcnt(0) */
         }
         const uint32_t qmask = S.simple ? 0u : mx422_true_rows(L, g, S.b);
         mx_wave_sync();
@@ -1420,12 +1430,6 @@ __global__ __launch_bounds__(64 * kMxs422WPG, kWPE) void k_mxs422(const jx_xform
             o[2] = mx_mma(Ah1, B[0][w0 + 1], m[2]);
             o[1] = mx_mma(Al1, B[1][w0 + 1], m[1]);
             o[3] = mx_mma(Ah1, B[1][w0 + 1], m[3]);
-            if (kParts == 3) {
-                o[1] = mx_mma(Al0, B[kParts - 1][w0], o[1]);
-                o[3] = mx_mma(Ah0, B[kParts - 1][w0], o[3]);
-                o[1] = mx_mma(Al1, B[kParts - 1][w0 + 1], o[1]);
-                o[3] = mx_mma(Ah1, B[kParts - 1][w0 + 1], o[3]);
-            }
         };
         /* every LDS read of the step's A operands before its first MFMA; each column reads its
          * scales after its tiles (the Y column after a fence on the chroma products) */
@@ -1478,7 +1482,7 @@ __global__ __launch_bounds__(64 * kMxs422WPG, kWPE) void k_mxs422(const jx_xform
                 if (2u * (lane >> 4) >= nvalid) fl &= ~0xff00u;
             }
             mx422_exact_inline(L, sp, qmask, fl, xt);
-            load_b(mx_lane());
+            mx_load_b<3>(B, s_img.B, mx_lane());
         }
         /* always two store instructions (the vmcnt accounting counts on it) */
         if (S.simple) {
@@ -1560,7 +1564,17 @@ struct Mx420Chunk {
     int16_t *ydst, *cdst;               /* Y block (2my, 2mx), chroma block mi (Cb) of frame f */
 };
 
-__device__ __forceinline__ void mx420_ptrs(Mx420Chunk &C, const MxG &g, const Mx420G &h)
+/* Position of the launch-global MCU m: frame, MCU in frame, row, column */
+__device__ __forceinline__ void mx420_mcu(const Mx420G &h, unsigned m, unsigned &f, unsigned &mi,
+                                          unsigned &my, unsigned &mx)
+{
+    f = mx_udiv(m, h.dnmcu);
+    mi = m - f * h.nmcu;
+    my = mx_udiv(mi, h.dmpr);
+    mx = mi - my * h.mpr;
+}
+
+__device__ __forceinline__ void mx420_ptrs(Mx420Chunk &C, const MxG &g)
 {
     C.src = g.rgb + (long long)C.f * g.fstride + 16ll * C.my * g.pitch + 48ll * C.mx;
     C.ydst = g.out + (long long)C.f * g.ofstride + 64ll * (2ull * C.my * g.bpr + 2u * C.mx);
@@ -1570,21 +1584,8 @@ __device__ __forceinline__ void mx420_ptrs(Mx420Chunk &C, const MxG &g, const Mx
 __device__ __forceinline__ void mx420_at(Mx420Chunk &C, const MxG &g, const Mx420G &h, unsigned m0)
 {
     C.m0 = m0;
-    C.f = mx_udiv(m0, h.dnmcu);
-    C.mi = m0 - C.f * h.nmcu;
-    C.my = mx_udiv(C.mi, h.dmpr);
-    C.mx = C.mi - C.my * h.mpr;
-    mx420_ptrs(C, g, h);
-}
-
-/* Position of the launch-global MCU m: frame, MCU in frame, row, column */
-__device__ __forceinline__ void mx420_mcu(const Mx420G &h, unsigned m, unsigned &f, unsigned &mi,
-                                          unsigned &my, unsigned &mx)
-{
-    f = mx_udiv(m, h.dnmcu);
-    mi = m - f * h.nmcu;
-    my = mx_udiv(mi, h.dmpr);
-    mx = mi - my * h.mpr;
+    mx420_mcu(h, m0, C.f, C.mi, C.my, C.mx);
+    mx420_ptrs(C, g);
 }
 
 /* A general step's pixels (row / frame crossings, a row's last MCU, the launch's end): lane l
@@ -1756,8 +1757,6 @@ struct alignas(16) MxsImg420 {
     uint8_t scan_t[8][8];
     MxExTab ex;
 };
-constexpr unsigned kMxs420Pieces = sizeof(MxsImg420) / 16;
-static_assert(sizeof(MxsImg420) % 16 == 0 && kMxs420Pieces <= 1024, "four 16-byte pieces per thread");
 static_assert(sizeof(Mxs420Lds) % 16 == 0 && sizeof(Mxs420Lds) * kMxs420WPG + sizeof(MxsImg420) <= 40 * 1024,
               "4 workgroups of 4 waves per CU");
 __device__ MxsImg420 g_mxs420_img[2][JX_MAXQ + 1];
@@ -1794,15 +1793,7 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     Mxs420Lds &L = s_lds[wave];
-    {
-        const uint8_t *img = (const uint8_t *)&g_mxs420_img[g.force ? 1 : 0][g.quality];
-#pragma unroll
-        for (unsigned i = 0; i < (kMxs420Pieces + 64u * kMxs420WPG - 1u) / (64u * kMxs420WPG); i++) {
-            const unsigned piece = 64u * kMxs420WPG * i + threadIdx.x;
-            if (64u * kMxs420WPG * i + 64u * wave < kMxs420Pieces && piece < kMxs420Pieces)
-                mxs_dma<16>(img + 16u * piece, (uint8_t *)&s_img + 16u * (64u * kMxs420WPG * i + 64u * wave));
-        }
-    }
+    mx_image_dma<kMxs420WPG>(g_mxs420_img[g.force ? 1 : 0][g.quality], s_img, wave);
     /* two pairs: MCUs m0 .. m0 + 3 and m0 + 4 .. m0 + 7; simple = one MCU row of one frame, no
      * row-last MCU, in range (per pair) */
     const unsigned m0 = 8u * (blockIdx.x * kMxs420WPG + wave);
@@ -1839,10 +1830,8 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
 
     /* lane constants */
     const unsigned m = lane & 15u, q = lane >> 4;
-    const uint32_t aoff = 96u * (m & 3u) + 24u * (m >> 2) + 8u * (q < 3 ? q : 2u);
-    const uint32_t s0 = q < 3 ? kSelLo : kSelOne;
-    const uint32_t s1 = q < 3 ? kSelHi : kSelZero;
-    const uint32_t s2 = q < 3 ? kSelLo : kSelZero;
+    const MxYop yop = mx_yop(lane, 96u);
+    const uint32_t aoff = yop.off, s0 = yop.s0, s1 = yop.s1, s2 = yop.s2;
     const uint32_t cof0 = 192u * (m & 7u) + 48u * (m >> 3) + 8u * q;
     const uint32_t cof1 = cof0 + (q < 2 ? 32u : 80u);
     const uint32_t soy = (lane & 31u) * 16u + (lane >> 5) * g.bpr * 128u;
@@ -1871,17 +1860,7 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
     }
     /* the B operands; reloaded after an exact pass, so that their registers are free during it */
     mx_u4 B[kParts][5];
-    const auto load_b = [&](unsigned l) __attribute__((always_inline)) {
-#pragma unroll
-        for (int p = 0; p < kParts; p++) {
-            const mx_u4 by = s_img.B[4 * p][l], zero = {};
-            B[p][0] = (l & 15u) < 8 ? by : zero;
-            B[p][1] = (l & 15u) < 8 ? zero : by;
-#pragma unroll
-            for (int w = 2; w < 5; w++) B[p][w] = s_img.B[4 * p + w - 1][l];
-        }
-    };
-    load_b(lane);
+    mx_load_b<4>(B, s_img.B, lane);
     const float limc0 = s_img.limc[0][j], limc2 = s_img.limc[1][j];
     const MxTab &tb = s_img.tab;
     const MxExLds xt{s_img.ex, s_img.scan_t};
@@ -1947,12 +1926,6 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
             accY[2] = mx_mma(Ah1, B[0][1], midY[2]);
             accY[1] = mx_mma(Al1, B[1][1], midY[1]);
             accY[3] = mx_mma(Ah1, B[1][1], midY[3]);
-            if (kParts == 3) {
-                accY[1] = mx_mma(Al0, B[kParts - 1][0], accY[1]);
-                accY[3] = mx_mma(Ah0, B[kParts - 1][0], accY[3]);
-                accY[1] = mx_mma(Al1, B[kParts - 1][1], accY[1]);
-                accY[3] = mx_mma(Ah1, B[kParts - 1][1], accY[3]);
-            }
         }
         __builtin_amdgcn_sched_barrier(0);
         mx_fence_all(accY);
@@ -1969,11 +1942,6 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
             midC[3] = mx_mma(C1, B[1][3], midC[1]);
             accC[0] = mx_mma(C2, B[0][4], midC[2]);
             accC[1] = mx_mma(C2, B[1][4], midC[3]);
-            if (kParts == 3) {
-                accC[1] = mx_mma(C0, B[kParts - 1][2], accC[1]);
-                accC[1] = mx_mma(C1, B[kParts - 1][3], accC[1]);
-                accC[1] = mx_mma(C2, B[kParts - 1][4], accC[1]);
-            }
         }
         __builtin_amdgcn_sched_barrier(0);
         mx_fence_all(accC);
@@ -2007,7 +1975,7 @@ __global__ __launch_bounds__(64 * kMxs420WPG, kWPE) void k_mxs420(const jx_xform
                 if (mp + mx420_pm(gq) >= h.tm) fl &= ~0xff00u;
             }
             mx420_exact_inline(L, sp, fl, mp, simp, L.ring[pp ? 2 : 0], L.ring[pp ? 0 : 1], g, h, xt);
-            if (k < 3) load_b(mx_lane());
+            if (k < 3) mx_load_b<4>(B, s_img.B, mx_lane());
         }
         /* stores: the Y store; on the second step also the pair's chroma */
         if (simp) {

@@ -388,8 +388,8 @@ extern "C" long long jx_selftest_pk(long long nblocks, unsigned long long seed)
 
 /* ---- k_mxs / k_mxs422 / k_mxs420: colour conversion + row DCT as f16 MFMA products --------
  *
- * The kernels multiply a row of pixel bytes b_k by a matrix B[k][n], split into JX_MX_PARTS f16
- * parts.  Three matrices ("mode"), one code path below:
+ * The kernels multiply a row of pixel bytes b_k by a matrix B[k][n], split into two f16 parts
+ * (JX_MX_PARTS: hi and lo).  Three matrices ("mode"), one code path below:
  *   mode 0 (k_mxs, and the Y of every kernel): a pixel row of a block, 24 bytes (k = 3x + p, plane
  *     p of pixel x), B[k][n] = a[c][p] cos((2x+1)u pi/16), n = 8c + u, c = Y, Cb, Cr, with a bias
  *     row (input 1.0) carrying the level shift, -8 * 128 for Y at u = 0 (preprocess.c:160-162,
@@ -404,8 +404,7 @@ extern "C" long long jx_selftest_pk(long long nblocks, unsigned long long seed)
  *     w = 1/2 or 1/4, c = Cb, Cr, n = 8 c' + u (c' = 0 Cb, 1 Cr); its bias row is all zero.  Two /
  *     three K = 32 products per part (k = 0..31, 32..63 [, 64..95]).
  * The split: Bh = B rounded to a multiple of 2^-11 (|B| < 1: 11 bits; bias: its f16), Bl = the f16
- * of B - Bh [, Bm = the f16 of B - Bh - Bl], the lo parts stored x 2^JX_MX_LOEXP (0: at the hi
- * part's scale, R = acc_h + acc_l is one add).
+ * of B - Bh, stored at the hi part's scale: R = acc_h + acc_l is one add.
  * Encoding (the kernel's A is one v_perm per two bytes): A holds the byte zero-extended to 16
  * bits, i.e. the f16 subnormal b 2^-24 (exact), the bias lanes 1.0; B's byte rows are stored
  * x 2^15 and the bias row x 2^-9, so every product is b B 2^-9 (exact in fp32) and the MFMA's
@@ -414,8 +413,8 @@ extern "C" long long jx_selftest_pk(long long nblocks, unsigned long long seed)
  * scales with them, and the quantiser's w x 2^9 (jpgx_mx.hip kRScale) gives the very fp32 F w.
  * acc_h = sum_k b_k Bh_k is EXACT whatever the order of the MFMA's additions: every product
  * and every partial sum is a multiple of 2^-11 below 2^13 in magnitude (24 bits).  acc_l =
- * sum_k b_k (Bl_k [+ Bm_k]) is below 1 in magnitude; each of its additions is charged one ulp
- * (32 products per MFMA plus the accumulator: 33, 65 or 97 per lo part).  R = fl(acc_h + acc_l)
+ * sum_k b_k Bl_k is below 1 in magnitude; each of its additions is charged one ulp
+ * (32 products per MFMA plus the accumulator: 33, 65 or 97 by mode).  R = fl(acc_h + acc_l)
  * then enters the column pass (jx_fdct8, FOps, two blocks per v_pk_* pair) as usual.
  *
  * Operand layout (v_mfma_f32_16x16x32_f16: lane l holds A[row l & 15][k = 8 (l >> 4) + e] and
@@ -485,12 +484,9 @@ static long double mx_enc(long double v, bool bias, uint16_t *bits)
 /* one mode's split matrix: true-scale values and f16 bit patterns, rows 0..nk (nk = the bias row) */
 struct MxSplit {
     int mode, nk, ncol;
-    long double h[97][24], l[97][24], m[97][24];      /* m = 0 unless JX_MX_PARTS == 3 */
-    uint16_t bh[97][24], bl[97][24], bm[97][24];
-    uint16_t bits(int part, int k, int n) const
-    {
-        return k > nk ? 0 : (part == 0 ? bh[k][n] : (part == 1 ? bl[k][n] : bm[k][n]));
-    }
+    long double h[97][24], l[97][24];
+    uint16_t bh[97][24], bl[97][24];
+    uint16_t bits(int part, int k, int n) const { return k > nk ? 0 : (part == 0 ? bh[k][n] : bl[k][n]); }
 };
 typedef std::unique_ptr<MxSplit> MxSplitPtr;        /* heap, per call: reentrant across threads */
 
@@ -507,14 +503,7 @@ static int mx_split(int mode, MxSplit &S)
             const long double hv = mx_enc(bias ? B : rintl(ldexpl(B, 11)) / 2048.0L, bias, &S.bh[k][n]);
             if (ldexpl(hv, 11) != rintl(ldexpl(hv, 11))) return JPGX_EARG;
             S.h[k][n] = hv;
-            /* the lo parts are stored scaled by 2^JX_MX_LOEXP (exact scaling: the kernels take R =
-             * acc_h + 2^-LOEXP acc_l).  S.l / S.m hold the unscaled values. */
-            const long double ls = mx_enc(ldexpl(B - hv, JX_MX_LOEXP), bias, &S.bl[k][n]);
-            S.l[k][n] = ldexpl(ls, -JX_MX_LOEXP);
-            if (JX_MX_PARTS == 3) {
-                const long double ms = mx_enc(ldexpl(B - hv, JX_MX_LOEXP) - ls, bias, &S.bm[k][n]);
-                S.m[k][n] = ldexpl(ms, -JX_MX_LOEXP);
-            }
+            S.l[k][n] = mx_enc(B - hv, bias, &S.bl[k][n]);
         }
     for (int n = 0; n < S.ncol; n++) {          /* acc_h exactness: partial sums < 2^13 */
         long double sh = fabsl(S.h[S.nk][n]);
@@ -524,8 +513,9 @@ static int mx_split(int mode, MxSplit &S)
     return JPGX_OK;
 }
 
+/* the split as the tests and pins read it: two parts, the lo part at the hi part's scale (2^0) */
 extern "C" int jx_mx_parts(void) { return JX_MX_PARTS; }
-extern "C" int jx_mx_loexp(void) { return JX_MX_LOEXP; }
+extern "C" int jx_mx_loexp(void) { return 0; }
 
 /* k_mxs's operands, 3 * part + which; lane l holds B[k = 8 (l >> 4) + e][plan column of l & 15].
  * which 0 = columns j = 8c + u for c = Y, Cb; 1 = Cr at u = j for j < 8, zero columns j >= 8;
@@ -556,7 +546,7 @@ extern "C" int jx_mx_operands(uint16_t ops[3 * JX_MX_PARTS][64][8])
  * 0..7 and its lo part in columns 8..15 -- lane for lane ops[3 * 0 + 1] where l % 16 < 8 and
  * ops[3 * 1 + 2] elsewhere (the set-1 tile is the same matrix shifted by eight columns).  One
  * product A Bc gives acc_h in columns 0..7 and acc_l in columns 8..15 of the same set's Cr. */
-static_assert(JX_MX_PARTS == 2, "k_mxs's Cr tile holds one hi and one lo part");
+static_assert(JX_MX_PARTS == 2, "the Cr tile's halves are the split's two parts");
 extern "C" int jx_mxs_device_operands(uint16_t out[3][64][8])
 {
     std::unique_ptr<uint16_t[][64][8]> ops(new uint16_t[3 * JX_MX_PARTS][64][8]);
@@ -603,23 +593,23 @@ static Bnd mx_row_bound(const MxSplit &S, int n)
 {
     const int nk = S.nk;
     long double loh = S.h[nk][n], hih = S.h[nk][n];
-    long double lol = S.l[nk][n] + S.m[nk][n], hil = lol;
-    long double sl = fabsl(S.l[nk][n]) + fabsl(S.m[nk][n]);
-    long double rep = fabsl(mx_exact(S.mode, nk, n) - S.h[nk][n] - S.l[nk][n] - S.m[nk][n]);
+    long double lol = S.l[nk][n], hil = lol;
+    long double sl = fabsl(S.l[nk][n]);
+    long double rep = fabsl(mx_exact(S.mode, nk, n) - S.h[nk][n] - S.l[nk][n]);
     for (int k = 0; k < nk; k++) {             /* bytes 0..255 */
-        const long double bh = S.h[k][n], bo = S.l[k][n] + S.m[k][n];
+        const long double bh = S.h[k][n], bo = S.l[k][n];
         loh += std::min(0.0L, 255.0L * bh);
         hih += std::max(0.0L, 255.0L * bh);
         lol += std::min(0.0L, 255.0L * bo);
         hil += std::max(0.0L, 255.0L * bo);
-        sl += 255.0L * (fabsl(S.l[k][n]) + fabsl(S.m[k][n]));
-        rep += 255.0L * fabsl(mx_exact(S.mode, k, n) - S.h[k][n] - S.l[k][n] - S.m[k][n]);
+        sl += 255.0L * fabsl(S.l[k][n]);
+        rep += 255.0L * fabsl(mx_exact(S.mode, k, n) - S.h[k][n] - S.l[k][n]);
     }
-    /* acc_l: per lo part mx_products MFMAs of 32 products (mode 0: 25 weights, 7 zeros; k_mxs's Cr
+    /* acc_l: mx_products MFMAs of 32 products (mode 0: 25 weights, 7 zeros; k_mxs's Cr
      * tile's second, K-concatenated MFMA adds exact zeros in every column) plus the accumulator
      * input; every addition charged one ulp of the magnitude bound, twice over for an unknown
      * summation tree and rounding mode */
-    const double nadd = 2.0 * ((32.0 * mx_products(S.mode) + 1.0) * (JX_MX_PARTS - 1));
+    const double nadd = 2.0 * (32.0 * mx_products(S.mode) + 1.0);
     const double el = (double)(nadd * sl * 0x1p-23L + rep);
     return BoundOps::add(Bnd{(double)loh, (double)hih, 0.0},
                          Bnd{(double)lol - el, (double)hil + el, el});
@@ -736,12 +726,11 @@ static long long mx_selftest(int mode, long long nblocks, unsigned long long see
             float R[8];
             for (int y = 0; y < 8; y++) {
                 long double ah = S.h[S.nk][n];
-                float al = (float)(S.l[S.nk][n] + S.m[S.nk][n]);
+                float al = (float)S.l[S.nk][n];
                 for (int k = 0; k < S.nk; k++) {
                     const int sv = px[y][k];
                     ah += sv * S.h[k][n];
                     al = al + (float)(sv * S.l[k][n]);
-                    if (JX_MX_PARTS == 3) al = al + (float)(sv * S.m[k][n]);
                 }
                 R[y] = (float)ah + al;
             }
