@@ -12,12 +12,15 @@
  * Reads never leave [row start, row start + 3 W) of a row 0 .. H - 1: a chunk whose aligned dwords
  * would (a row's first chunk when the row starts off a dword, its last one or two), a chunk that
  * holds repeated columns, and the chunk that straddles the two rows of a pair when 3 cw is no
- * multiple of 16, are put together byte by byte instead -- about three chunks of a row.  A lane takes
- * the same chunk of kPadPairs row pairs and issues all their loads before the first store.  No LDS.
+ * multiple of 16, are put together byte by byte instead -- about three chunks of a row.  That rule is
+ * csrc/jx_pad.h's, one text for this kernel and for its host restatement (csrc/jpgx_pad_host.cpp), which
+ * runs it with every load checked.  A lane takes the same chunk of kPadPairs row pairs and issues all
+ * their loads before the first store.  No LDS.
  */
 #include <stdint.h>
 
 #include "jx_hip.h"
+#include "jx_pad.h"
 
 namespace {
 
@@ -35,20 +38,18 @@ struct PadArgs {
     uint32_t nframes;
 };
 
-/* byte xb of a coded row whose source row begins at `row`: beyond 3 W the last pixel's channel */
-__device__ __forceinline__ uint32_t pad_byte(const uint8_t *row, uint32_t xb, uint32_t w3)
-{
-    return row[xb < w3 ? xb : w3 - 3u + xb % 3u];
-}
+/* the device's loads, as they are */
+struct PadMem {
+    __device__ __forceinline__ uint32_t u32(const uint8_t *p) const { return *(const uint32_t *)p; }
+    __device__ __forceinline__ uint32_t u8(const uint8_t *p) const { return *p; }
+};
 
 __global__ __launch_bounds__(kPadT) void k_pad_edge(const PadArgs a)
 {
     const uint32_t c = blockIdx.x * kPadT + threadIdx.x;        /* chunk of the row pair */
     if (c >= a.pitch / 8u) return;
-    const uint32_t o = 16u * c;                                 /* its byte in the pair */
-    const uint32_t r = o >= a.pitch ? 1u : 0u;
-    const uint32_t xb = o - r * a.pitch;                        /* its first byte's place in row 2 pair + r */
-    const bool whole = xb + 16u <= a.w3;                        /* 16 image bytes of one row */
+    const JxPadChunk ck = jx_pad_chunk(c, a.pitch, a.w3);
+    const PadMem mem;
     const uint32_t pair0 = blockIdx.y * kPadPairs;
     for (uint32_t f = blockIdx.z; f < a.nframes; f += gridDim.z) {
         const uint8_t *src = a.src + (size_t)f * a.in_fstride;
@@ -60,19 +61,7 @@ __global__ __launch_bounds__(kPadT) void k_pad_edge(const PadArgs a)
             const uint32_t pair = pair0 + j;
             fast[j] = false;
             if (pair >= a.npairs) continue;
-            const uint32_t y = min(2u * pair + r, a.h - 1u);
-            const uint8_t *p = src + (size_t)y * a.in_pitch + xb;
-            sh[j] = (uint32_t)((uintptr_t)p & 3u);
-            /* the aligned dwords [p - sh, p - sh + 16), and [.., + 20) when sh != 0, inside the row */
-            fast[j] = whole && xb >= sh[j] && (sh[j] == 0u || xb - sh[j] + 20u <= a.w3);
-            if (fast[j]) {
-                const uint32_t *q = (const uint32_t *)(p - sh[j]);
-                d[j][0] = q[0];
-                d[j][1] = q[1];
-                d[j][2] = q[2];
-                d[j][3] = q[3];
-                d[j][4] = sh[j] ? q[4] : 0u;
-            }
+            jx_pad_load(mem, src, a.in_pitch, a.w3, a.h, ck, pair, d[j], sh[j], fast[j]);
         }
         uint32_t slow = 0;                                      /* bit j: pair0 + j is left to the bytes */
 #pragma unroll
@@ -84,27 +73,16 @@ __global__ __launch_bounds__(kPadT) void k_pad_edge(const PadArgs a)
                 continue;
             }
             uint32_t w[4];
-#pragma unroll
-            for (int k = 0; k < 4; k++) w[k] = __builtin_amdgcn_alignbyte(d[j][k + 1], d[j][k], sh[j]);
-            *(u32x4 *)(dst + (size_t)pair * 2u * a.pitch + o) = u32x4{w[0], w[1], w[2], w[3]};
+            JX_PAD_FUNNEL(w, d[j], sh[j]);
+            *(u32x4 *)(dst + (size_t)pair * 2u * a.pitch + ck.o) = u32x4{w[0], w[1], w[2], w[3]};
         }
         /* the few chunks at a row's ends: rolled up, so that they cost the others no registers */
 #pragma unroll 1
         for (; slow; slow &= slow - 1u) {
             const uint32_t pair = pair0 + (uint32_t)__builtin_ctz(slow);
             uint32_t w[4] = {0, 0, 0, 0};
-#pragma unroll 1
-            for (uint32_t k = 0; k < 16u; k++) {
-                const uint32_t ob = o + k;                      /* below 2 pitch: c < pitch / 8 */
-                const uint32_t rr = ob >= a.pitch ? 1u : 0u;
-                const uint32_t y = min(2u * pair + rr, a.h - 1u);
-                const uint32_t b = pad_byte(src + (size_t)y * a.in_pitch, ob - rr * a.pitch, a.w3) << (8u * (k & 3u));
-                w[0] |= k < 4u ? b : 0u;
-                w[1] |= k >= 4u && k < 8u ? b : 0u;
-                w[2] |= k >= 8u && k < 12u ? b : 0u;
-                w[3] |= k >= 12u ? b : 0u;
-            }
-            *(u32x4 *)(dst + (size_t)pair * 2u * a.pitch + o) = u32x4{w[0], w[1], w[2], w[3]};
+            JX_PAD_BYTES(w, mem, src, a.in_pitch, a.w3, a.h, a.pitch, ck.o, pair);
+            *(u32x4 *)(dst + (size_t)pair * 2u * a.pitch + ck.o) = u32x4{w[0], w[1], w[2], w[3]};
         }
     }
 }

@@ -18,7 +18,7 @@ import ctypes
 
 import numpy as np
 
-from . import JpgxError, coded_size, lib
+from . import EARG, JpgxError, coded_size, lib
 
 c_int_p = ctypes.POINTER(ctypes.c_int)
 
@@ -456,6 +456,36 @@ def pixels_host_gray(coef: np.ndarray, width: int, height: int, qt: np.ndarray, 
                                      channels, nthreads), "jpgx_pixels_host_gray")
     px = buf[:height, :channels * width]
     return px if channels == 1 else px.reshape(height, width, 3)
+
+
+PAD_STATS = 17      # JX_PAD_NSTAT (csrc/jx_pad.h)
+
+
+def pad_host(buf: np.ndarray, base_off: int, width: int, height: int, in_pitch: int, in_frame_stride: int,
+             nframes: int, coded_width: int, coded_height: int, trace: bool = True, library=None):
+    """jx_pad_host (csrc/jpgx_pad_host.cpp, test-only): k_pad_edge's chunk rule (csrc/jx_pad.h) on the host
+    over the frames of `buf`, uint8 [len]; pixel (0, 0) of frame f is buf[base_off + f * in_frame_stride].
+    -> (bad, coded uint8 [nframes][coded_height][coded_width][3], touched uint8 [len] or None, stats uint64
+    [PAD_STATS]).  trace: every load is checked against buf and recorded in `touched` (1: byte loads, 2:
+    dword loads); bad counts the refused ones.  stats: fast chunks by the row start's residue [0:4], slow
+    chunks by reason [4:8] (a row's first chunk off a dword, repeated columns or a row's short end, the
+    fifth dword past the row, the straddling chunk), chunks with an index >= 256 [8], and by residue the
+    chunks that met the fifth dword's bound exactly [9:13] and missed it by one byte [13:17]."""
+    L = library or lib
+    fn = L.jx_pad_host
+    vp, i, z = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
+    fn.argtypes = [vp, z, z, i, i, z, z, i, i, i, vp, vp, vp]
+    fn.restype = ctypes.c_longlong
+    if buf.dtype != np.uint8 or buf.ndim != 1 or not buf.flags.c_contiguous:
+        raise ValueError("pad_host: buf must be a contiguous uint8 vector")
+    out = np.zeros((nframes, coded_height, coded_width, 3), np.uint8)
+    touched = np.zeros(len(buf), np.uint8) if trace else None
+    stats = np.zeros(PAD_STATS, np.uint64)
+    bad = fn(buf.ctypes.data, len(buf), base_off, width, height, in_pitch, in_frame_stride, nframes, coded_width,
+             coded_height, out.ctypes.data, touched.ctypes.data if trace else None, stats.ctypes.data)
+    if bad < 0:
+        raise JpgxError(EARG, "jx_pad_host")
+    return int(bad), out, touched, stats
 
 
 def encode_bmp_to_jpeg_ex(src: str, dst: str, quality: int, sample_ratio: int, flags: int,

@@ -10,6 +10,8 @@ filter in either direction.  The output is rows [0, H) and columns [0, W).
 
     coded(W, H, sample_ratio) -> (coded W, coded H)
     pixels(coef, W, H, sample_ratio, qt) -> uint8 [H][W][3]      coef: the coded frame's blocks
+
+m24: pass 1's products from the 24-bit multiplier's model (tests/idct_ref.py), not the contract.
 """
 import numpy as np
 
@@ -51,7 +53,7 @@ def upsample(p, W, H, vs):
     return (3 * s[:, i] + s[:, j] + add.astype(I32)) >> I32(shift)
 
 
-def pixels(coef, W, H, sample_ratio, qt):
+def pixels(coef, W, H, sample_ratio, qt, m24=False):
     coef = np.asarray(coef, np.int16).reshape(-1, 64)
     qt = np.asarray(qt, np.uint16).reshape(2, 64)
     hs, vs = sampling(sample_ratio)
@@ -60,10 +62,10 @@ def pixels(coef, W, H, sample_ratio, qt):
     cbw, cbh = bw // hs, bh // vs
     nb, nbc = bw * bh, cbw * cbh
     assert coef.shape[0] == nb + 2 * nbc
-    y = samples(coef[:nb], qt[0], bw, bh)[:H, :W]
+    y = samples(coef[:nb], qt[0], bw, bh, m24)[:H, :W]
     wc, hc = -(-W // hs), -(-H // vs)
-    cb = samples(coef[nb:nb + nbc], qt[1], cbw, cbh)[:hc, :wc]
-    cr = samples(coef[nb + nbc:], qt[1], cbw, cbh)[:hc, :wc]
+    cb = samples(coef[nb:nb + nbc], qt[1], cbw, cbh, m24)[:hc, :wc]
+    cr = samples(coef[nb + nbc:], qt[1], cbw, cbh, m24)[:hc, :wc]
     if sample_ratio:
         cb, cr = upsample(cb, W, H, vs), upsample(cr, W, H, vs)
     cb, cr = cb - 128, cr - 128

@@ -1,7 +1,9 @@
 """The pixel half of the decoder on the host: jpgx_pixels_host against the numpy
 restatement of the contract (tests/idct_ref.py) and against Pillow's libjpeg decode, jpgx_jfif_qt,
 jpgx_pixels_gpu's argument checks (no device is touched) and the sanitizer program
-tests/c/pixels_san.c.  The arithmetic is integer: every comparison is ==."""
+tests/c/pixels_san.c; the model of the device's 24-bit multiplier (idct_ref.mul24) and the guards of the
+frames that pin the kernels' choice of multiplier (tests/pixels_cases.py; the device side is
+tests/test_pixels_mul_gpu.py).  The arithmetic is integer: every comparison is ==."""
 import io
 import shutil
 
@@ -63,6 +65,92 @@ def test_hostile_values(sr):
             assert np.array_equal(got, want), (W, H, k)
             seen.update(np.unique(got).tolist())
         assert len(seen) > 64                            # the outputs are not all clamped to 0 / 255
+
+
+# ---- the multiplier choice: a model of the 24-bit multiplier, and frames on which it shows ------------------
+def test_mul24_is_the_24_bit_multiplier():
+    m = lambda a, c: int(idct_ref.mul24(np.array([a], np.int64).astype(np.int32), np.int32(c))[0])   # noqa: E731
+    assert m(3, -7) == -21 and m(-1, -1) == 1 and m(0x7FFFFF, 2) == 0xFFFFFE
+    assert m(0x800000, 1) == -0x800000                      # bit 23 is the sign
+    assert m(0x1000000, 5) == 0 and m(0x1000003, 5) == 15   # bits 24 .. 31 are not read
+    assert m(-0x800001, 1) == 0x7FFFFF
+    assert m(0x7FFFFF, 0x7FFFFF) == (0x7FFFFF * 0x7FFFFF) % (1 << 32) - (1 << 32)      # the product's low 32 bits
+    rng = np.random.default_rng(24)
+    a = rng.integers(-(1 << 23), 1 << 23, 4096).astype(np.int32)
+    c = rng.integers(-(1 << 23), 1 << 23, 4096).astype(np.int32)
+    with np.errstate(over="ignore"):
+        assert np.array_equal(idct_ref.mul24(a, c), a * c)          # in range: the 32-bit multiplier's
+
+
+def test_the_model_is_the_contract_where_the_kernels_may_use_it():
+    """random full-range blocks under uniform 63 and 64: every number that is multiplied is inside 24 bits"""
+    blocks = np.random.default_rng(63).integers(-32768, 32768, (500, 64)).astype(np.int16)
+    for t in (1, 63, 64):
+        qt = np.full(64, t, np.uint16)
+        assert np.array_equal(idct_ref.samples(blocks, qt, 20, 25, m24=True), idct_ref.samples(blocks, qt, 20, 25)), t
+    # and it is not vacuous: under 255 most samples differ
+    qt = np.full(64, 255, np.uint16)
+    assert (idct_ref.samples(blocks, qt, 20, 25, m24=True) != idct_ref.samples(blocks, qt, 20, 25)).mean() > 0.5
+
+
+def test_63_and_64_cannot_tell_the_multipliers_apart():
+    for sr in (0, 1, 2):
+        case = P.cannot_tell_case(sr)
+        assert len(case["names"]) == 8
+        for k, name in enumerate(case["names"]):
+            assert not P.tells(case, k), (sr, name)
+            assert np.array_equal(P.host_pixels(case, k), P.model_pixels("plain", case["coefs"][k], 48, 32, sr, case["qts"][k], False))
+
+
+MUL = P.multiplier_cases()
+
+
+@pytest.mark.parametrize("name", [m[0] for m in MUL])
+def test_multiplier_cases_tell_and_the_host_is_the_contract(name):
+    """every frame's guard, and the host twin == the restatement on it"""
+    case, channels = next(m[1:] for m in MUL if m[0] == name)
+    assert len(case["names"]) == len(case["coefs"]) == len(case["qts"]) == len(case["regions"]) >= 5
+    for k, what in enumerate(case["names"]):
+        y0, y1, x0, x1 = case["regions"][k]
+        assert y0 < y1 <= case["H"] and x0 < x1 <= case["W"], what
+        assert P.tells(case, k), (name, what)
+        want = P.model_pixels(case["kind"], case["coefs"][k], case["W"], case["H"], case["sr"], case["qts"][k], False,
+                              channels or 1)
+        assert np.array_equal(P.host_pixels(case, k, channels), want), (name, what)
+
+
+def test_multiplier_cases_cover_what_they_are_for():
+    from idct_ref import ZZ
+    for sr in (0, 1, 2):
+        names = P.threshold_case(sr)[1]
+        assert any(n.startswith("luma 63, chroma 65") for n in names) and any(n.startswith("luma 65, chroma 63") for n in names)
+        assert sum(n.endswith("random") for n in names) >= 5            # from 96 up
+    for sr in (0, 1, 2):
+        for ch in (0, 1, 2):
+            case = P.vote_lane_case(sr, ch)
+            first = P.planes_of(case["W"], case["H"], sr, "plain")[ch][0]
+            lanes = set()
+            for k in range(64):
+                c = case["coefs"][k].astype(np.int32)
+                big = np.argwhere(np.abs(c) > P.BACKGROUND)
+                assert len(big) == 1                                    # one large value, in one channel
+                blk, pos = int(big[0][0]) - first, int(big[0][1])
+                assert 0 <= blk < 8 and (ZZ[pos] >> 3) % 4 != 0         # natural rows 0 and 4 are never multiplied
+                lanes.add((blk, pos >> 3))
+            assert len(lanes) == 64                                     # no load lane is left out
+    for W, H, sr, kind, per_row in ((264, 8, 0, "plain", (33, 33, 33)), (528, 16, 1, "plain", (66, 33, 33)),
+                                    (523, 13, 2, "any", (66, 33, 33)), (264, 8, 0, "gray", (33,))):
+        case = P.vote_run_case(W, H, sr, kind)
+        planes = P.planes_of(W, H, sr, kind)
+        assert tuple(p[1] for p in planes) == per_row
+        runs = set()
+        for k in range(len(case["names"])):
+            big = np.argwhere(np.abs(case["coefs"][k].astype(np.int32)) > P.BACKGROUND)
+            assert len(big) == 1
+            ch = max(i for i, p in enumerate(planes) if p[0] <= big[0][0])
+            runs.add((ch, (int(big[0][0]) - planes[ch][0]) % planes[ch][1] // 8))
+        assert runs == {(ch, r) for ch, p in enumerate(planes) for r in range(-(-p[1] // 8))}
+        assert any("block 32 " in n for n in case["names"])             # the tail's single live block
 
 
 def test_host_argument_checks():
