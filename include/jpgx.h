@@ -446,6 +446,40 @@ int jpgx_pixels_gpu_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t
                          const int32_t *d_status, uint8_t *d_out, size_t out_pitch,
                          size_t out_frame_stride, int channels, void *stream);
 
+/* ---- 1/2, 1/4 and 1/8 of the size ------------------------------------------------
+ * libjpeg-turbo's default decoder with scale_num / scale_denom = 1 / scale_denom: reduced-size inverse
+ * DCTs produce the small image from the coefficients directly.  The output is ow x oh =
+ * ceil(width / scale_denom) x ceil(height / scale_denom) (jpgx_scaled_size; JPGX_EARG for null
+ * pointers, a side outside 1 .. 65535 or a scale_denom other than 1, 2, 4, 8).  A luma block becomes
+ * m x m = 8 / scale_denom samples; a chroma block m x m too, for 4:2:0 2m x 2m, which is the luma's
+ * size; 4:2:2's chroma goes through the h2v1 triangle filter clamped at its real extent
+ * ceil(width * m / 16), and is replicated where that is 2 or less and at 1/8.  Equal byte for byte to
+ * jpgx_pixels_host_scaled / jpgx_pixels_host_gray_scaled (jpgx_compat.h).
+ *
+ * jpgx_pixels_gpu_scaled: jpgx_pixels_gpu_any's arguments with scale_denom after sample_ratio;
+ * jpgx_pixels_gpu_gray_scaled: jpgx_pixels_gpu_gray's with scale_denom after height.  width and height
+ * are the file's, the coefficients the coded frame's.  scale_denom 1 is the sibling's call, launch for
+ * launch.  Otherwise the sibling's contract holds with ow x oh in the place of width x height:
+ * out_pitch at least bytes per pixel * ow and a multiple of 8, out_frame_stride at least out_pitch * oh
+ * and a multiple of 8; only bytes [0, bytes per pixel * ow) of rows [0, oh) are written; a frame with
+ * d_status[f] != 0 is skipped and untouched.  The checks and their order are the sibling's, with
+ * JPGX_EARG for a scale_denom other than 1, 2, 4, 8 among the first (the pointer and alignment checks).
+ * Workspace (jpgx_pixels_gpu_scaled_workspace_size; 0 for bad arguments): the two chroma sample planes
+ * at their reduced size for 4:2:2 at 1/2 and 1/4 and for 4:2:0, 16-byte aligned; none for 4:4:4, for
+ * 4:2:2 at 1/8 and for one-component frames. */
+int jpgx_scaled_size(int width, int height, int scale_denom, int *out_width, int *out_height);
+size_t jpgx_pixels_gpu_scaled_workspace_size(int width, int height, int sample_ratio, int scale_denom,
+                                             size_t nframes);
+int jpgx_pixels_gpu_scaled(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes,
+                           int width, int height, int sample_ratio, int scale_denom,
+                           const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                           uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
+                           void *d_workspace, size_t workspace_bytes, void *stream);
+int jpgx_pixels_gpu_gray_scaled(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes,
+                                int width, int height, int scale_denom, const uint16_t *d_qt,
+                                size_t qt_frame_stride, const int32_t *d_status, uint8_t *d_out,
+                                size_t out_pitch, size_t out_frame_stride, int channels, void *stream);
+
 /* ---- the encode side of the one-component family ---------------------------
  * The reference knows only RGB: this contract is the project's own (parity unpinned).  A one-channel
  * image of width x height, 1 .. 65535 each, is coded as jx_frame_make_gray's frame (csrc/jx_frame.h):

@@ -335,6 +335,20 @@ int jpgx_read_jfif_sub_gray(const uint8_t *file, size_t len, uint32_t sub_bytes,
 int jpgx_pixels_host_gray(const int16_t *coef, int width, int height, const uint16_t qt[64],
                           uint8_t *out, size_t pitch, int channels, int nthreads);
 
+/* The host twins of jpgx_pixels_gpu_scaled and jpgx_pixels_gpu_gray_scaled (include/jpgx.h; DESIGN.md
+ * 4.9b): libjpeg-turbo's default decoder's pixels with scale_num / scale_denom = 1 / scale_denom, from
+ * the same source (csrc/jx_idct.h).  jpgx_pixels_host_any's and jpgx_pixels_host_gray's arguments and
+ * contracts with scale_denom, 1, 2, 4 or 8, after sample_ratio (after height for the one-component
+ * frame): the coefficients are the coded frame's, width and height the file's, and bytes
+ * [0, bytes per pixel * ow) of rows [0, oh) are written, ow x oh = ceil(width / scale_denom) x
+ * ceil(height / scale_denom).  scale_denom 1 is the sibling's call.  JPGX_EARG: the sibling's cases with
+ * the pitch measured against ow, and any other scale_denom. */
+int jpgx_pixels_host_scaled(const int16_t *coef, int width, int height, int sample_ratio, int scale_denom,
+                            const uint16_t qt[2][64], uint8_t *rgb, size_t pitch, int nthreads);
+int jpgx_pixels_host_gray_scaled(const int16_t *coef, int width, int height, int scale_denom,
+                                 const uint16_t qt[64], uint8_t *out, size_t pitch, int channels,
+                                 int nthreads);
+
 /* encode_bmp_to_jpeg with flags: JPGX_FLAG_SUBSAMPLE and sample_ratio 1/2 write a truly
  * subsampled JFIF (extension); otherwise exactly jpgx_encode_bmp_to_jpeg.  GPU `device`. */
 int jpgx_encode_bmp_to_jpeg_ex(const char *input, const char *output, int quality,

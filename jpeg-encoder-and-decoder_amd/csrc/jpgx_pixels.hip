@@ -34,6 +34,10 @@
  * px_transform<1> on the same runs and the same LDS image, then 1 byte per pixel through a staging
  * buffer of its own (px_store_gray1) or 3 equal bytes through px_store<1> with Cb = Cr = 128, for
  * which jxi_rgb returns the sample three times.  No workspace.
+ *
+ * jpgx_pixels_gpu_scaled / jpgx_pixels_gpu_gray_scaled (1/2, 1/4, 1/8 of the size) launch
+ * k_pxs, k_pxs_chroma and k_pxs_dc, which stand below the kernels above and share their runs, their LDS
+ * image and their lane constants; scale_denom 1 is the _any / _gray call.
  */
 #include <stdint.h>
 #include <string.h>
@@ -487,6 +491,313 @@ __global__ __launch_bounds__(kWave) void k_px_gray(const PxArgsGray a)
     }
 }
 
+/* ---- 1/2, 1/4 and 1/8 of the size ------------------------------------------------
+ *   k_pxs<N, MODE>     a luma block to N x N samples, N = 4 or 2, on the runs and the LDS image above:
+ *                      one-component frames (1 or 3 bytes per pixel) and 4:4:4 fused, 4:2:x with the
+ *                      chroma samples read from the workspace (as they are, replicated 2 x 1 or through
+ *                      the triangle filter: a.up)
+ *   k_pxs_chroma<N>    Cb and Cr to N x N samples per block in the workspace (8 x 8: k_px_chroma)
+ *   k_pxs_dc<MODE>     1/8 of the size: lane = block, one DC per channel, one pixel per lane */
+struct PxArgsScaled : PxArgs {
+    uint32_t ow, oh;                    /* the output */
+    uint32_t wc;                        /* a chroma row's real samples: the triangle filter clamps there */
+    uint32_t pc;                        /* bytes between a chroma plane's rows in the workspace */
+    uint32_t up;                        /* the chroma samples of a pixel row: 0 as they are, 1 replicated 2 x 1,
+                                           2 through the h2v1 triangle filter */
+    unsigned long long plane;           /* bytes of a chroma plane */
+};
+
+/* px_transform at N = 4 or 2: lane (b, row j < N) gets s[ch][0..N-1], the other lanes zeros.  Pass 1
+ * takes the 24-bit multiplier under px_transform's rule (every input inside +-2^21 then), pass 2 always */
+template <int NCH, int N>
+__device__ __forceinline__ void pxs_transform(const int16_t *const (&src)[NCH], const int (&tab)[NCH], uint32_t n,
+                                              const Lane &L, uint32_t *img, uint32_t (&s)[NCH][N])
+{
+    const bool live = L.b < n;
+    V4 in[NCH];
+    if (live) {
+#pragma unroll
+        for (int ch = 0; ch < NCH; ch++) in[ch].v = *(const uint4 *)(src[ch] + (size_t)threadIdx.x * 8);
+#pragma unroll
+        for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                img[ch * 512 + L.at[i]] = jxi_dequant((int16_t)in[ch].h[i], L.q[tab[ch]].h[i]);
+    }
+    bool small = L.fast;
+    if (!small) {
+        uint32_t big = 0;
+        if (live) {
+#pragma unroll
+            for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+                for (int i = 0; i < 8; i++) big |= jxi_dequant((int16_t)in[ch].h[i], L.q[tab[ch]].h[i]) + 0x8000u;
+        }
+        small = __all(big < 0x10000u);
+    }
+    __syncthreads();
+    /* pass 1: lane = (block, column j), rows 0 .. N - 1 in place */
+    const uint32_t col = px_at(L.b, 0, L.j);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        uint32_t v[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) v[r] = img[ch * 512 + (col ^ (8u * r))];
+        if (small) jxi_idctn<N, 1>(v, 1);
+        else jxi_idctn<N, 0>(v, 1);
+#pragma unroll
+        for (int r = 0; r < N; r++) img[ch * 512 + (col ^ (8u * r))] = v[r];
+    }
+    __syncthreads();
+    /* pass 2: lane = (block, row j < N) */
+    const uint32_t row = px_at(L.b, L.j & (uint32_t)(N - 1), 0);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ch++) {
+        const uint4 lo = *(const uint4 *)(img + ch * 512 + row), hi = *(const uint4 *)(img + ch * 512 + (row ^ 4u));
+        uint32_t v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        jxi_idctn<N, 1>(v, 2);
+#pragma unroll
+        for (int c = 0; c < N; c++) s[ch][c] = L.j < (uint32_t)N ? jxi_range(v[c]) : 0u;
+    }
+    __syncthreads();                    /* the image is free: the staging buffer lies in it */
+}
+
+/* lane (b, row j < N) has the NB = bytes per pixel x N bytes of its piece of pixel row j of the run; a
+ * row of the run is 8 NB bytes, NB pieces of 8 bytes, and N rows are at most 48 pieces: lane t stores
+ * piece t % NB of row t / NB.  rows, nbytes and the row's last partial piece: as px_store<1>'s */
+template <int NB, int N>
+__device__ __forceinline__ void pxs_store(const uint32_t (&px)[NB], const Lane &L, uint8_t *stage, uint8_t *out,
+                                          size_t pitch, uint32_t rows, uint32_t nbytes)
+{
+    constexpr uint32_t kRow = 8u * NB + 16u;    /* bytes between the staged rows */
+    if (L.j < (uint32_t)N) {
+        uint8_t *dst = stage + L.j * kRow + L.b * (uint32_t)NB;
+        if constexpr (NB % 4 == 0) {
+#pragma unroll
+            for (int k = 0; k < NB / 4; k++)
+                ((uint32_t *)dst)[k] = px[4 * k] | px[4 * k + 1] << 8 | px[4 * k + 2] << 16 | px[4 * k + 3] << 24;
+        } else {
+#pragma unroll
+            for (int k = 0; k < NB / 2; k++) ((uint16_t *)dst)[k] = (uint16_t)(px[2 * k] | px[2 * k + 1] << 8);
+        }
+    }
+    __syncthreads();
+    {
+        const uint32_t r = threadIdx.x / (uint32_t)NB, c = threadIdx.x % (uint32_t)NB;
+        if (r < rows && c * 8u + 8u <= nbytes)      /* rows <= N, nbytes <= 8 NB */
+            *(uint2 *)(out + (size_t)r * pitch + c * 8u) = *(const uint2 *)(stage + r * kRow + c * 8u);
+    }
+    if (nbytes & 7u) {                  /* the same for the whole wave: lane r finishes row r */
+        const uint32_t r = threadIdx.x, at = nbytes & ~7u;
+        if (r < rows) {
+            const uint2 w = *(const uint2 *)(stage + r * kRow + at);
+            uint8_t *tail = out + (size_t)r * pitch + at;           /* 8-byte aligned */
+            uint32_t v = w.x;
+            if (nbytes & 4u) {
+                *(uint32_t *)tail = v;
+                tail += 4;
+                v = w.y;
+            }
+            if (nbytes & 2u) {
+                *(uint16_t *)tail = (uint16_t)v;
+                tail += 2;
+                v >>= 16;
+            }
+            if (nbytes & 1u) *tail = (uint8_t)v;
+        }
+    }
+    __syncthreads();                    /* the staging buffer is free for the next run's image */
+}
+
+enum { PXS_GRAY1, PXS_GRAY3, PXS_444, PXS_PLANES };
+
+/* The grid has the block rows that hold a visible output row: by * N < oh; run * 8 N < ow for every run
+ * of a row, as in the any-size kernels.  PXS_PLANES: the chroma plane's rows are the output's rows; its
+ * samples are N per block (a.up 0: 4:2:0, the plane has the luma's size) or N / 2 with their two clamped
+ * neighbours (4:2:2); every index is below a.wc <= a.pc or, for a.up 0, below bw N = a.pc */
+template <int N, int MODE>
+__global__ __launch_bounds__(kWave) void k_pxs(const PxArgsScaled a)
+{
+    constexpr int NCH = MODE == PXS_444 ? 3 : 1, BPP = MODE == PXS_GRAY1 ? 1 : 3;
+    __shared__ __attribute__((aligned(16))) uint32_t img[NCH * 512];
+    const uint32_t f = blockIdx.z, by = blockIdx.y;
+    if (px_skip(a, f)) return;          /* the same for the whole workgroup */
+    Lane L;
+    if constexpr (MODE == PXS_GRAY1 || MODE == PXS_GRAY3) px_lane_gray(a, f, L);
+    else px_lane(a, f, L);
+    const uint32_t nruns = (a.g.bw + 7u) / 8u;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride;
+    uint8_t *out = a.rgb + (size_t)f * a.ostride + (size_t)by * N * a.pitch;
+    const uint32_t y0 = by * N, rows = y0 < a.oh ? min((uint32_t)N, a.oh - y0) : 0u;
+    const uint8_t *crow = nullptr;      /* this lane's row of the Cb plane */
+    if constexpr (MODE == PXS_PLANES)
+        crow = a.planes + (size_t)f * 2u * a.plane + (size_t)(y0 + (L.j & (uint32_t)(N - 1))) * a.pc;
+    for (uint32_t run = blockIdx.x * kRunsPerWave; run < min(nruns, (blockIdx.x + 1u) * kRunsPerWave); run++) {
+        const uint32_t n = min(8u, a.g.bw - run * 8u);
+        const size_t blk = (size_t)by * a.g.bw + (size_t)run * 8u;
+        uint32_t s[NCH][N], px[BPP * N];
+        if constexpr (NCH == 3) {
+            const int16_t *const src[3] = {frame + blk * 64, frame + ((size_t)a.g.nb + blk) * 64,
+                                           frame + (2 * (size_t)a.g.nb + blk) * 64};
+            const int tab[3] = {0, 1, 1};
+            pxs_transform<3, N>(src, tab, n, L, img, s);
+        } else {
+            const int16_t *const src[1] = {frame + blk * 64};
+            const int tab1[1] = {0};
+            pxs_transform<1, N>(src, tab1, n, L, img, s);
+        }
+        if constexpr (MODE == PXS_GRAY1) {
+#pragma unroll
+            for (int c = 0; c < N; c++) px[c] = s[0][c];
+        } else {
+            uint32_t cb[N], cr[N];
+#pragma unroll
+            for (int c = 0; c < N; c++) cb[c] = cr[c] = 128u;
+            if constexpr (MODE == PXS_444) {
+#pragma unroll
+                for (int c = 0; c < N; c++) cb[c] = s[1][c], cr[c] = s[2][c];
+            }
+            if constexpr (MODE == PXS_PLANES) {
+                if (L.b < n && L.j < (uint32_t)N) {
+                    const uint32_t x0 = (run * 8u + L.b) * N;       /* below bw N */
+                    if (a.up == 0u) {
+                        uint32_t w0, w1;
+                        if constexpr (N == 4) {
+                            w0 = *(const uint32_t *)(crow + x0);
+                            w1 = *(const uint32_t *)(crow + a.plane + x0);
+                        } else {
+                            w0 = *(const uint16_t *)(crow + x0);
+                            w1 = *(const uint16_t *)(crow + a.plane + x0);
+                        }
+#pragma unroll
+                        for (int c = 0; c < N; c++) cb[c] = w0 >> (8 * c) & 255u, cr[c] = w1 >> (8 * c) & 255u;
+                    } else {
+                        /* samples i0 - 1 .. i0 + N / 2 of the row, every index clamped to [0, wc - 1] */
+                        const uint32_t i0 = x0 >> 1, last = a.wc - 1u;
+                        uint32_t p[2][N / 2 + 2];
+#pragma unroll
+                        for (int k = 0; k < N / 2 + 2; k++) {
+                            const uint32_t i = min(max(i0 + k, 1u) - 1u, last);
+                            p[0][k] = crow[i];
+                            p[1][k] = crow[a.plane + i];
+                        }
+#pragma unroll
+                        for (int i = 0; i < N / 2; i++) {
+                            if (a.up == 1u) {
+                                cb[2 * i] = cb[2 * i + 1] = p[0][i + 1];
+                                cr[2 * i] = cr[2 * i + 1] = p[1][i + 1];
+                            } else {
+                                cb[2 * i] = jxi_up_even(p[0][i + 1], p[0][i], 0);
+                                cb[2 * i + 1] = jxi_up_odd(p[0][i + 1], p[0][i + 2], 0);
+                                cr[2 * i] = jxi_up_even(p[1][i + 1], p[1][i], 0);
+                                cr[2 * i + 1] = jxi_up_odd(p[1][i + 1], p[1][i + 2], 0);
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < N; c++) jxi_rgb(s[0][c], cb[c], cr[c], &px[3 * c], &px[3 * c + 1], &px[3 * c + 2]);
+        }
+        const uint32_t at = run * 8u * BPP * N, end = BPP * a.ow;   /* the run's first byte of a row; the row's end */
+        pxs_store<BPP * N, N>(px, L, (uint8_t *)img, out + at, (size_t)a.pitch, rows,
+                              at < end ? min(BPP * N * n, end - at) : 0u);
+    }
+}
+
+/* Cb and Cr at N x N samples per block to the workspace: planes [2][N cbh][N cbw] per frame */
+template <int N>
+__global__ __launch_bounds__(kWave) void k_pxs_chroma(const PxArgsScaled a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t img[2 * 512];
+    const uint32_t f = blockIdx.z, by = blockIdx.y;     /* a chroma block row */
+    if (px_skip(a, f)) return;
+    Lane L;
+    px_lane(a, f, L);
+    const uint32_t nruns = (a.g.cbw + 7u) / 8u;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride + (size_t)a.g.nb * 64;
+    uint8_t *out = a.planes + (size_t)f * 2u * a.plane + ((size_t)by * N + (L.j & (uint32_t)(N - 1))) * a.pc;
+    const int tab[2] = {1, 1};
+    for (uint32_t run = blockIdx.x * kRunsPerWave; run < min(nruns, (blockIdx.x + 1u) * kRunsPerWave); run++) {
+        const uint32_t n = min(8u, a.g.cbw - run * 8u);
+        const size_t blk = (size_t)by * a.g.cbw + (size_t)run * 8u;
+        const int16_t *const src[2] = {frame + blk * 64, frame + ((size_t)a.g.nbc + blk) * 64};
+        uint32_t s[2][N];
+        pxs_transform<2, N>(src, tab, n, L, img, s);
+        if (L.b < n && L.j < (uint32_t)N) {
+#pragma unroll
+            for (int ch = 0; ch < 2; ch++) {
+                uint8_t *dst = out + ch * a.plane + ((size_t)run * 8u + L.b) * N;
+                if constexpr (N == 4) *(uint32_t *)dst = s[ch][0] | s[ch][1] << 8 | s[ch][2] << 16 | s[ch][3] << 24;
+                else *(uint16_t *)dst = (uint16_t)(s[ch][0] | s[ch][1] << 8);
+            }
+        }
+    }
+}
+
+enum { PXD_GRAY1, PXD_GRAY3, PXD_444, PXD_422, PXD_420 };
+
+/* 1/8 of the size: a block is one pixel, the range-limited DESCALE(DC, 3).  Lane = block: a wave takes
+ * 64 consecutive blocks of a block row and reads one int16 of each channel's block; 4:2:2 takes the
+ * chroma block of its pair (replication), 4:2:0 its 2 x 2 samples from the workspace (k_pxs_chroma<2>).
+ * The grid has the visible blocks only: blockIdx.y < oh <= bh and x < ow <= bw */
+template <int MODE>
+__global__ __launch_bounds__(kWave) void k_pxs_dc(const PxArgsScaled a)
+{
+    constexpr uint32_t BPP = MODE == PXD_GRAY1 ? 1u : 3u;
+    __shared__ __attribute__((aligned(8))) uint8_t stage[64 * BPP];
+    const uint32_t f = blockIdx.z, by = blockIdx.y, x0 = blockIdx.x * 64u, x = x0 + threadIdx.x;
+    if (px_skip(a, f)) return;          /* the same for the whole workgroup */
+    if (by >= a.oh || x0 >= a.ow) return;
+    const uint16_t *qt = a.qt + (size_t)f * a.qstride;
+    const int16_t *frame = a.coef + (size_t)f * a.cstride;
+    if (x < a.ow) {
+        const size_t blk = (size_t)by * a.g.bw + x;
+        const uint32_t y = jxi_range(jxi_idct1(jxi_dequant(frame[blk * 64], qt[0])));
+        if constexpr (MODE == PXD_GRAY1) {
+            stage[threadIdx.x] = (uint8_t)y;
+        } else {
+            uint32_t cb = 128u, cr = 128u, r, g, b;
+            if constexpr (MODE == PXD_444 || MODE == PXD_422) {
+                const size_t cblk = MODE == PXD_444 ? blk : (size_t)by * a.g.cbw + (x >> 1);
+                const uint16_t qc = qt[64];
+                cb = jxi_range(jxi_idct1(jxi_dequant(frame[((size_t)a.g.nb + cblk) * 64], qc)));
+                cr = jxi_range(jxi_idct1(jxi_dequant(frame[((size_t)a.g.nb + a.g.nbc + cblk) * 64], qc)));
+            }
+            if constexpr (MODE == PXD_420) {
+                const uint8_t *p = a.planes + (size_t)f * 2u * a.plane + (size_t)by * a.pc + x;
+                cb = p[0];
+                cr = p[a.plane];
+            }
+            jxi_rgb(y, cb, cr, &r, &g, &b);
+            stage[3u * threadIdx.x] = (uint8_t)r;
+            stage[3u * threadIdx.x + 1u] = (uint8_t)g;
+            stage[3u * threadIdx.x + 2u] = (uint8_t)b;
+        }
+    }
+    __syncthreads();
+    const uint32_t nbytes = BPP * min(64u, a.ow - x0);
+    uint8_t *out = a.rgb + (size_t)f * a.ostride + (size_t)by * a.pitch + (size_t)x0 * BPP;  /* 8-byte aligned */
+    if (threadIdx.x * 8u + 8u <= nbytes) *(uint2 *)(out + threadIdx.x * 8u) = *(const uint2 *)(stage + threadIdx.x * 8u);
+    if ((nbytes & 7u) && threadIdx.x == 0u) {
+        const uint32_t at = nbytes & ~7u;
+        const uint2 w = *(const uint2 *)(stage + at);
+        uint8_t *tail = out + at;
+        uint32_t v = w.x;
+        if (nbytes & 4u) {
+            *(uint32_t *)tail = v;
+            tail += 4;
+            v = w.y;
+        }
+        if (nbytes & 2u) {
+            *(uint16_t *)tail = (uint16_t)v;
+            tail += 2;
+            v >>= 16;
+        }
+        if (nbytes & 1u) *tail = (uint8_t)v;
+    }
+}
+
 /* the chroma sample planes (4:2:x): the workspace's one part */
 size_t px_workspace(const jx_frame &g, size_t nframes)
 {
@@ -593,9 +904,178 @@ int px_run_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes,
     return jx_hip_rc(hipGetLastError());
 }
 
+/* 1 / d of the size: which sampling keeps its chroma samples in the workspace (4:2:0 always; 4:2:2 but
+ * at 1/8, where a pixel pair takes its chroma block's DC), and the bytes of the two planes of a batch */
+bool pxs_planes(const jx_frame &g, const jx_frame_scaled &s) { return g.vs > 1 || (g.hs > 1 && s.m > 1); }
+
+size_t pxs_workspace(const jx_frame &g, const jx_frame_scaled &s, size_t nframes)
+{
+    jx_carve ws;
+    if (pxs_planes(g, s)) ws.take(nframes * 2 * (size_t)g.nbc * s.n * s.n);
+    return ws.at;
+}
+
+template <int MODE>
+void pxs_launch(uint32_t m, dim3 grid, hipStream_t s, const PxArgsScaled &a)
+{
+    if (m == 4) hipLaunchKernelGGL((k_pxs<4, MODE>), grid, dim3(kWave), 0, s, a);
+    else hipLaunchKernelGGL((k_pxs<2, MODE>), grid, dim3(kWave), 0, s, a);
+}
+
+/* jpgx_pixels_gpu_scaled, d = 2, 4, 8: px_run<1>'s checks in their order, the output's size in the
+ * place of the frame's */
+int pxs_run(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height, int sample_ratio,
+            int scale_denom, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status, uint8_t *d_rgb,
+            size_t out_pitch, size_t out_frame_stride, void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    PxArgsScaled a;
+    memset(&a, 0, sizeof a);
+    if (!d_coef || !d_qt || !d_rgb || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_rgb & 7) || !jx_frames_ok(nframes) || !jx_scaled_ok(scale_denom))
+        return JPGX_EARG;
+    jx_frame_any fa;
+    const int rc = jx_frame_rc_pixels(jx_frame_make_any(width, height, sample_ratio, &fa));
+    if (rc) return rc;
+    const jx_frame &f = fa.c;
+    jx_frame_scaled sc;
+    jx_frame_make_scaled(fa.w, fa.h, f.hs, f.vs, (uint32_t)scale_denom, &sc);
+    a.g = PxGeom{f.bw, f.bh, f.cbw, f.cbh, f.hs, f.vs, f.nb, f.nbc};
+    if (!jx_coef_batch_ok(coef_frame_stride, f.nblk)) return JPGX_EARG;
+    if (qt_frame_stride != 0 && qt_frame_stride < 128) return JPGX_EARG;
+    if (out_pitch < (size_t)sc.ow * 3 || out_pitch % 8) return JPGX_EARG;
+    if (out_frame_stride < out_pitch * (size_t)sc.oh || out_frame_stride % 8) return JPGX_EARG;
+    const size_t need = pxs_workspace(f, sc, nframes);
+    if (workspace_bytes < need) return JPGX_EWORKSPACE;
+    if (need && (!d_workspace || ((uintptr_t)d_workspace & 15))) return JPGX_EARG;
+    a.coef = d_coef;
+    a.cstride = coef_frame_stride;
+    a.qt = d_qt;
+    a.qstride = qt_frame_stride;
+    a.status = d_status;
+    a.rgb = d_rgb;
+    a.pitch = out_pitch;
+    a.ostride = out_frame_stride;
+    a.planes = (uint8_t *)d_workspace;
+    a.ow = sc.ow, a.oh = sc.oh, a.wc = sc.wc;
+    a.pc = f.cbw * sc.n;
+    a.plane = (unsigned long long)a.pc * f.cbh * sc.n;
+    a.up = sc.hfac == 1 ? 0u : (sc.wc <= 2 || sc.m == 1) ? 1u : 2u;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nf = (unsigned)nframes;
+    if (pxs_planes(f, sc)) {
+        const dim3 cgrid(px_grid_x(f.cbw), f.cbh, nf);
+        if (sc.n == 8) {
+            const PxArgs &plain = a;
+            hipLaunchKernelGGL(k_px_chroma, cgrid, dim3(kWave), 0, s, plain);
+        } else if (sc.n == 4) {
+            hipLaunchKernelGGL(k_pxs_chroma<4>, cgrid, dim3(kWave), 0, s, a);
+        } else {
+            hipLaunchKernelGGL(k_pxs_chroma<2>, cgrid, dim3(kWave), 0, s, a);
+        }
+    }
+    if (sc.m == 1) {
+        const dim3 grid((sc.ow + 63u) / 64u, sc.oh, nf);
+        if (sample_ratio == 0) hipLaunchKernelGGL(k_pxs_dc<PXD_444>, grid, dim3(kWave), 0, s, a);
+        else if (sample_ratio == 1) hipLaunchKernelGGL(k_pxs_dc<PXD_422>, grid, dim3(kWave), 0, s, a);
+        else hipLaunchKernelGGL(k_pxs_dc<PXD_420>, grid, dim3(kWave), 0, s, a);
+    } else {
+        const dim3 grid(px_grid_x(f.bw), (sc.oh + sc.m - 1u) / sc.m, nf);
+        if (sample_ratio == 0) pxs_launch<PXS_444>(sc.m, grid, s, a);
+        else pxs_launch<PXS_PLANES>(sc.m, grid, s, a);
+    }
+    return jx_hip_rc(hipGetLastError());
+}
+
+/* jpgx_pixels_gpu_gray_scaled, d = 2, 4, 8: px_run_gray's checks in their order */
+int pxs_run_gray(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                 int scale_denom, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status, uint8_t *d_out,
+                 size_t out_pitch, size_t out_frame_stride, int channels, void *stream)
+{
+    PxArgsScaled a;
+    memset(&a, 0, sizeof a);
+    if (!d_coef || !d_qt || !d_out || ((uintptr_t)d_coef & 15) || ((uintptr_t)d_qt & 1) || ((uintptr_t)d_status & 3) ||
+        ((uintptr_t)d_out & 7) || !jx_frames_ok(nframes) || (channels != 1 && channels != 3) ||
+        !jx_scaled_ok(scale_denom))
+        return JPGX_EARG;
+    jx_frame_gray g;
+    const int rc = jx_frame_rc_pixels(jx_frame_make_gray(width, height, &g));
+    if (rc) return rc;
+    jx_frame_scaled sc;
+    jx_frame_make_scaled(g.w, g.h, 1u, 1u, (uint32_t)scale_denom, &sc);
+    a.g = PxGeom{g.bw, g.bh, 0u, 0u, 1u, 1u, g.nb, 0u};
+    if (!jx_coef_batch_ok(coef_frame_stride, g.nb)) return JPGX_EARG;
+    if (qt_frame_stride != 0 && qt_frame_stride < 64) return JPGX_EARG;
+    if (out_pitch < (size_t)sc.ow * (size_t)channels || out_pitch % 8) return JPGX_EARG;
+    if (out_frame_stride < out_pitch * (size_t)sc.oh || out_frame_stride % 8) return JPGX_EARG;
+    a.coef = d_coef;
+    a.cstride = coef_frame_stride;
+    a.qt = d_qt;
+    a.qstride = qt_frame_stride;
+    a.status = d_status;
+    a.rgb = d_out;
+    a.pitch = out_pitch;
+    a.ostride = out_frame_stride;
+    a.ow = sc.ow, a.oh = sc.oh;
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned nf = (unsigned)nframes;
+    if (sc.m == 1) {
+        const dim3 grid((sc.ow + 63u) / 64u, sc.oh, nf);
+        if (channels == 1) hipLaunchKernelGGL(k_pxs_dc<PXD_GRAY1>, grid, dim3(kWave), 0, s, a);
+        else hipLaunchKernelGGL(k_pxs_dc<PXD_GRAY3>, grid, dim3(kWave), 0, s, a);
+    } else {
+        const dim3 grid(px_grid_x(g.bw), (sc.oh + sc.m - 1u) / sc.m, nf);
+        if (channels == 1) pxs_launch<PXS_GRAY1>(sc.m, grid, s, a);
+        else pxs_launch<PXS_GRAY3>(sc.m, grid, s, a);
+    }
+    return jx_hip_rc(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
+
+int jpgx_scaled_size(int width, int height, int scale_denom, int *out_width, int *out_height)
+{
+    if (!out_width || !out_height || width <= 0 || height <= 0 || width > 65535 || height > 65535 ||
+        (scale_denom != 1 && !jx_scaled_ok(scale_denom)))
+        return JPGX_EARG;
+    *out_width = (width + scale_denom - 1) / scale_denom;
+    *out_height = (height + scale_denom - 1) / scale_denom;
+    return JPGX_OK;
+}
+
+size_t jpgx_pixels_gpu_scaled_workspace_size(int width, int height, int sample_ratio, int scale_denom, size_t nframes)
+{
+    if (scale_denom == 1) return jpgx_pixels_gpu_any_workspace_size(width, height, sample_ratio, nframes);
+    jx_frame_any g;
+    if (!jx_frames_ok(nframes) || !jx_scaled_ok(scale_denom) || jx_frame_make_any(width, height, sample_ratio, &g)) return 0;
+    jx_frame_scaled sc;
+    jx_frame_make_scaled(g.w, g.h, g.c.hs, g.c.vs, (uint32_t)scale_denom, &sc);
+    return pxs_workspace(g.c, sc, nframes);
+}
+
+int jpgx_pixels_gpu_scaled(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                           int sample_ratio, int scale_denom, const uint16_t *d_qt, size_t qt_frame_stride,
+                           const int32_t *d_status, uint8_t *d_rgb, size_t out_pitch, size_t out_frame_stride,
+                           void *d_workspace, size_t workspace_bytes, void *stream)
+{
+    if (scale_denom == 1)
+        return px_run<1>(d_coef, coef_frame_stride, nframes, width, height, sample_ratio, d_qt, qt_frame_stride, d_status,
+                         d_rgb, out_pitch, out_frame_stride, d_workspace, workspace_bytes, stream);
+    return pxs_run(d_coef, coef_frame_stride, nframes, width, height, sample_ratio, scale_denom, d_qt, qt_frame_stride,
+                   d_status, d_rgb, out_pitch, out_frame_stride, d_workspace, workspace_bytes, stream);
+}
+
+int jpgx_pixels_gpu_gray_scaled(const int16_t *d_coef, size_t coef_frame_stride, size_t nframes, int width, int height,
+                                int scale_denom, const uint16_t *d_qt, size_t qt_frame_stride, const int32_t *d_status,
+                                uint8_t *d_out, size_t out_pitch, size_t out_frame_stride, int channels, void *stream)
+{
+    if (scale_denom == 1)
+        return px_run_gray(d_coef, coef_frame_stride, nframes, width, height, d_qt, qt_frame_stride, d_status, d_out,
+                           out_pitch, out_frame_stride, channels, stream);
+    return pxs_run_gray(d_coef, coef_frame_stride, nframes, width, height, scale_denom, d_qt, qt_frame_stride, d_status,
+                        d_out, out_pitch, out_frame_stride, channels, stream);
+}
 
 size_t jpgx_pixels_gpu_workspace_size(int width, int height, int sample_ratio, size_t nframes)
 {

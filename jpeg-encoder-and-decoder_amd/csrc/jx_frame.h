@@ -105,6 +105,40 @@ JXF_FN int jx_frame_make_any(int width, int height, int sample_ratio, jx_frame_a
     return 0;
 }
 
+/* A decode at 1 / d of the size, d = 2, 4 or 8 (the _scaled entry points): the output is
+ * ow x oh = ceil(w / d) x ceil(h / d); a luma block becomes m x m = 8 / d samples and a chroma block n x n.
+ * The rule for n is libjpeg's (one DCT_scaled_size per component): it starts at m and doubles while it is
+ * below 8 and divides the MCU's scaled extent both ways.  4:4:4 and 4:2:2: n = m; 4:2:0: n = 2 m, the
+ * chroma plane then has the luma's size.  jx_scaled_ok: d is one of the three. */
+JXF_FN int jx_scaled_ok(int scale_denom) { return scale_denom == 2 || scale_denom == 4 || scale_denom == 8; }
+
+JXF_FN uint32_t jx_scaled_chroma_n(uint32_t m, uint32_t hs, uint32_t vs)
+{
+    uint32_t n = m;
+    while (n < 8u && (hs * m) % (2u * n) == 0u && (vs * m) % (2u * n) == 0u) n *= 2u;
+    return n;
+}
+
+typedef struct jx_frame_scaled {
+    uint32_t d, m, n;       /* the denominator; samples per luma block and per chroma block, each way */
+    uint32_t ow, oh;        /* the output                                                        */
+    uint32_t wc, hc;        /* a chroma plane's real extent at n: ceil(w n / (8 hs)), ceil(h n / (8 vs)) */
+    uint32_t hfac;          /* luma samples per chroma sample across: hs m / n, 1 or 2 (down: always 1) */
+} jx_frame_scaled;
+
+/* of a visible frame w x h with sampling hs x vs (1 x 1 for a one-component frame) */
+JXF_FN void jx_frame_make_scaled(uint32_t w, uint32_t h, uint32_t hs, uint32_t vs, uint32_t d, jx_frame_scaled *s)
+{
+    s->d = d;
+    s->m = 8u / d;
+    s->n = jx_scaled_chroma_n(s->m, hs, vs);
+    s->ow = (w + d - 1u) / d;
+    s->oh = (h + d - 1u) / d;
+    s->wc = (w * s->n + 8u * hs - 1u) / (8u * hs);
+    s->hc = (h * s->n + 8u * vs - 1u) / (8u * vs);
+    s->hfac = hs * s->m / s->n;
+}
+
 /* A one-component (grayscale) file (the decode side's _gray entry points): its scan is
  * not interleaved, so whatever sampling factors SOF states, the MCU is one block and the frame codes
  * bw x bh = ceil(w / 8) x ceil(h / 8) blocks in raster order: coefficients Y [nb][64], no chroma. */

@@ -3,7 +3,8 @@
  * host routine (csrc/jpgx_pixels_host.cpp, g++) and the kernels (csrc/jpgx_pixels.hip):
  * dequantisation, the 13-bit fixed-point 8-point inverse transform applied down the columns and
  * along the rows, the wrapping range limit, the triangle-filter chroma upsampling and the 16-bit
- * fixed-point YCbCr -> RGB conversion -- the integer arithmetic of libjpeg's default decoder.
+ * fixed-point YCbCr -> RGB conversion -- the integer arithmetic of libjpeg's default decoder -- and the
+ * 4-, 2- and 1-point transforms of its decode at 1/2, 1/4 and 1/8 of the size.
  *
  * Every value is an int32 in two's complement that wraps: sums, products and left shifts are
  * written on uint32_t, so that no input is undefined behaviour, and >> is the arithmetic shift of
@@ -85,6 +86,56 @@ JXI_FN void jxi_idct8(uint32_t v[8], int s)
     v[5] = jxi_sar(t12 - a1 + r, s);
     v[3] = jxi_sar(t13 + a0 + r, s);
     v[4] = jxi_sar(t13 - a0 + r, s);
+}
+
+/* The reduced-size transforms of a 1/2, 1/4 and 1/8 scale decode (libjpeg's
+ * jpeg_idct_4x4, jpeg_idct_2x2 and jpeg_idct_1x1): v[0..7] are the eight inputs, the first 4, 2 or 1
+ * entries the outputs.  Pass 1 runs down the columns and pass 2 along the rows, as jxi_idct8's. */
+#define JXI_PASS1_SHIFT4 12
+#define JXI_PASS2_SHIFT4 19
+#define JXI_PASS1_SHIFT2 13
+#define JXI_PASS2_SHIFT2 20
+
+/* v[4] is never read.  M24 = 1 needs every input inside +-2^23: each factor is one input times a
+ * constant below 2^15.  Pass 2's inputs are int32 values shifted right by 12, inside +-2^19 */
+template <int M24>
+JXI_FN void jxi_idct4(uint32_t v[8], int s)
+{
+    const uint32_t tmp0 = v[0] << 14;
+    const uint32_t tmp2 = jxi_mul<M24>(v[2], 15137) - jxi_mul<M24>(v[6], 6270);
+    const uint32_t t10 = tmp0 + tmp2, t12 = tmp0 - tmp2;
+    const uint32_t o0 = jxi_mul<M24>(v[5], 11893) + jxi_mul<M24>(v[1], 8697) - jxi_mul<M24>(v[7], 1730) -
+                        jxi_mul<M24>(v[3], 17799);
+    const uint32_t o2 = jxi_mul<M24>(v[3], 7373) + jxi_mul<M24>(v[1], 20995) - jxi_mul<M24>(v[7], 4176) -
+                        jxi_mul<M24>(v[5], 4926);
+    const uint32_t r = 1u << (s - 1);
+    v[0] = jxi_sar(t10 + o2 + r, s);
+    v[1] = jxi_sar(t12 + o0 + r, s);
+    v[2] = jxi_sar(t12 - o0 + r, s);
+    v[3] = jxi_sar(t10 - o2 + r, s);
+}
+
+/* v[2], v[4] and v[6] are never read.  M24: as jxi_idct4's; pass 2's inputs are inside +-2^18 */
+template <int M24>
+JXI_FN void jxi_idct2(uint32_t v[8], int s)
+{
+    const uint32_t t10 = v[0] << 15;
+    const uint32_t o = jxi_mul<M24>(v[5], 6967) + jxi_mul<M24>(v[1], 29692) - jxi_mul<M24>(v[7], 5906) -
+                       jxi_mul<M24>(v[3], 10426);
+    const uint32_t r = 1u << (s - 1);
+    v[0] = jxi_sar(t10 + o + r, s);
+    v[1] = jxi_sar(t10 - o + r, s);
+}
+
+/* the 1-point transform of the dequantised DC d, before the range limit */
+JXI_FN uint32_t jxi_idct1(uint32_t d) { return jxi_sar(d + 4u, 3); }
+
+/* pass `pass` (1 or 2) of the N-point transform, N = 4 or 2 */
+template <int N, int M24>
+JXI_FN void jxi_idctn(uint32_t v[8], int pass)
+{
+    if (N == 4) jxi_idct4<M24>(v, pass == 1 ? JXI_PASS1_SHIFT4 : JXI_PASS2_SHIFT4);
+    else jxi_idct2<M24>(v, pass == 1 ? JXI_PASS1_SHIFT2 : JXI_PASS2_SHIFT2);
 }
 
 /* -2^15 <= d < 2^15 */

@@ -22,6 +22,8 @@ _gray entry points), or through decode_jpeg / decode_jpeg_coefficients with gray
 encode_blocks_gray (jpgx_blocks_gpu_gray: a one-channel image of any size and any row pitch to Y
 [nb][64]), jfif_gpu_gray (jpgx_jfif_gpu_gray: those coefficients to one-component files), or
 encode_jpeg with gray=True; the contract is the project's own (include/jpgx.h).
+pixels_gpu, pixels_gpu_gray and decode_jpeg take scale=2, 4 or 8 for libjpeg's decode at that fraction of
+the size (the library's _scaled entry points); scaled_size is the output's size.
 """
 from __future__ import annotations
 
@@ -69,6 +71,8 @@ EXPORTS = [
     "jpgx_jfif_decode_gpu_gray_workspace_size", "jpgx_jfif_decode_gpu_gray", "jpgx_pixels_gpu_gray",
     "jpgx_workspace_size_any", "jpgx_blocks_gpu_any", "jpgx_jfif_gpu_any_workspace_size", "jpgx_jfif_gpu_any",
     "jpgx_blocks_gpu_gray", "jpgx_jfif_gpu_gray_workspace_size", "jpgx_jfif_gpu_gray", "jpgx_guard_band_gray",
+    "jpgx_scaled_size", "jpgx_pixels_gpu_scaled_workspace_size", "jpgx_pixels_gpu_scaled",
+    "jpgx_pixels_gpu_gray_scaled",
 ]
 COMPAT_EXPORTS = [
     "jpgx_new_block", "jpgx_get_value_block", "jpgx_set_value_block", "jpgx_copy_block",
@@ -82,6 +86,7 @@ COMPAT_EXPORTS = [
     "jpgx_jfif_info_of_any", "jpgx_read_jfif_any", "jpgx_read_jfif_sub_any", "jpgx_pixels_host_any",
     "jpgx_jfif_info_of_gray", "jpgx_read_jfif_gray", "jpgx_read_jfif_sub_gray", "jpgx_pixels_host_gray",
     "jpgx_write_jfif_any", "jpgx_pad_edge", "jpgx_encode_rgb_to_jpeg_any", "jpgx_write_jfif_gray",
+    "jpgx_pixels_host_scaled", "jpgx_pixels_host_gray_scaled",
 ]
 
 
@@ -186,6 +191,11 @@ def _load(path: str = LIB_PATH) -> ctypes.CDLL:
     L.jpgx_jfif_gpu_gray_workspace_size.restype = sz
     L.jpgx_jfif_gpu_gray.argtypes = [vp, sz, sz, i, i, i, i, ctypes.c_uint, vp, sz, sz, vp, vp, sz, vp]
     L.jpgx_guard_band_gray.argtypes = [i, vp, vp]
+    L.jpgx_scaled_size.argtypes = [i, i, i, ctypes.POINTER(i), ctypes.POINTER(i)]
+    L.jpgx_pixels_gpu_scaled_workspace_size.argtypes = [i, i, i, i, sz]
+    L.jpgx_pixels_gpu_scaled_workspace_size.restype = sz
+    L.jpgx_pixels_gpu_scaled.argtypes = [vp, sz, sz, i, i, i, i, vp, sz, vp, vp, sz, sz, vp, sz, vp]
+    L.jpgx_pixels_gpu_gray_scaled.argtypes = [vp, sz, sz, i, i, i, vp, sz, vp, vp, sz, sz, i, vp]
     L.jpgx_version.restype = ctypes.c_char_p
     L.jpgx_host_create.argtypes = [ctypes.POINTER(vp), i, vp, i]
     L.jpgx_host_destroy.argtypes = [vp]
@@ -353,6 +363,26 @@ def coded_size(width: int, height: int, sample_ratio: int = 0) -> tuple[int, int
     cw, ch = ctypes.c_int(), ctypes.c_int()
     _check(lib.jpgx_coded_size(width, height, sample_ratio, ctypes.byref(cw), ctypes.byref(ch)), "jpgx_coded_size")
     return cw.value, ch.value
+
+
+SCALES = (1, 2, 4, 8)
+
+
+def _scale_arg(fn: str, scale) -> int:
+    """scale as an int, one of SCALES"""
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or int(scale) not in SCALES:
+        raise ValueError(f"{fn}: scale must be 1, 2, 4 or 8")
+    return int(scale)
+
+
+def scaled_size(width: int, height: int, scale: int) -> tuple[int, int]:
+    """jpgx_scaled_size: (ceil(width / scale), ceil(height / scale)), the size of a decode at 1 / scale
+    (scale 1, 2, 4 or 8; width and height 1 .. 65535)."""
+    scale = _scale_arg("scaled_size", scale)
+    ow, oh = ctypes.c_int(), ctypes.c_int()
+    if lib.jpgx_scaled_size(width, height, scale, ctypes.byref(ow), ctypes.byref(oh)):
+        raise ValueError("scaled_size: width and height must be 1 .. 65535")
+    return ow.value, oh.value
 
 
 def _frame(fn: str, width: int, height: int, sample_ratio: int, flags: int | None = None, d_coef=None,
@@ -736,7 +766,7 @@ def jfif_qt(quality: int) -> np.ndarray:
 
 
 def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None, status=None, out=None,
-               pitch: int | None = None, stream=None, any_size: bool = False):
+               pitch: int | None = None, stream=None, any_size: bool = False, scale: int = 1):
     """The pixels of a batch of coefficient frames (jpgx_pixels_gpu): d_coef int16
     [nframes][...] as jfif_decode_gpu returns it (each frame contiguous, frames d_coef.stride(0)
     elements apart), d_qt uint16 [nframes][2][64] (one pair per frame) or [2][64] (one for the batch),
@@ -746,29 +776,38 @@ def pixels_gpu(d_coef, width: int, height: int, sample_ratio: int = 0, d_qt=None
     buffer of nframes * H * pitch bytes to use instead of a fresh one.  Nothing is copied to the host
     and nothing waits.  any_size: jpgx_pixels_gpu_any -- d_coef holds the coded frame's coefficients
     (jfif_decode_gpu(any_size=True)), width and height are the visible frame's, any 1 .. 65535; the
-    default pitch is 3 W rounded up to 8, and only bytes [0, 3 W) of the H rows are written."""
+    default pitch is 3 W rounded up to 8, and only bytes [0, 3 W) of the H rows are written.  scale 2, 4
+    or 8: jpgx_pixels_gpu_scaled -- libjpeg's decode at 1 / scale of the size, uint8
+    [nframes][oh][ow][3] with (ow, oh) = scaled_size(W, H, scale); d_coef, width and height as with
+    any_size, whether or not it is set; pitch at least 3 ow, by default that rounded up to 8."""
     return _pixels("pixels_gpu", d_coef, width, height, d_qt, status, out, pitch, stream, sample_ratio=sample_ratio,
-                   any_size=any_size)
+                   any_size=any_size, scale=scale)
 
 
 def pixels_gpu_gray(d_coef, width: int, height: int, d_qt, status=None, channels: int = 1, out=None,
-                    pitch: int | None = None, stream=None):
+                    pitch: int | None = None, stream=None, scale: int = 1):
     """The pixels of a batch of one-component frames (jpgx_pixels_gpu_gray): d_coef int16
     [nframes][>= nb][64] as jfif_decode_gpu_gray returns it, d_qt uint16 [nframes][64] (a table per
     frame) or [64] (one for the batch), status as pixels_gpu's.  Returns uint8 [nframes][H][W]
     (channels 1) or [nframes][H][W][3] (channels 3, R = G = B) on the device: libjpeg's default
     decoder's pixels.  pitch (bytes between pixel rows, a multiple of 8, at least channels * W; default:
-    channels * W rounded up to 8) and out as pixels_gpu's.  Nothing is copied to the host and nothing waits."""
-    return _pixels("pixels_gpu_gray", d_coef, width, height, d_qt, status, out, pitch, stream, channels=channels)
+    channels * W rounded up to 8) and out as pixels_gpu's.  Nothing is copied to the host and nothing waits.
+    scale 2, 4 or 8: jpgx_pixels_gpu_gray_scaled -- the decode at 1 / scale of the size, [nframes][oh][ow]
+    (or [...][3]) with (ow, oh) = scaled_size(W, H, scale), the pitch measured against ow."""
+    return _pixels("pixels_gpu_gray", d_coef, width, height, d_qt, status, out, pitch, stream, channels=channels,
+                   scale=scale)
 
 
 def _pixels(fn: str, d_coef, width, height, d_qt, status, out, pitch, stream, sample_ratio: int = 0,
-            any_size: bool = False, channels: int | None = None):
+            any_size: bool = False, channels: int | None = None, scale: int = 1):
     """pixels_gpu and, with channels, pixels_gpu_gray: a pixel is 3 bytes or `channels`, a frame holds
     _frame's blocks or _gray_blocks', its tables are 128 elements or 64, and only pixels_gpu on whole MCUs
-    packs its rows by default"""
+    packs its rows by default.  scale 2, 4, 8: the _scaled entry points, a frame of any size, the output
+    scaled_size's"""
     import torch
     gray = channels is not None
+    scale = _scale_arg(fn, scale)
+    any_size = any_size or scale > 1
     if not _device_tensor(d_coef, torch.int16) or d_coef.dim() < 2:
         raise ValueError(f"{fn}: d_coef must be an int16 [nframes][...] device tensor")
     if not _device_tensor(d_qt, torch.uint16, contiguous=True):
@@ -783,6 +822,23 @@ def _pixels(fn: str, d_coef, width, height, d_qt, status, out, pitch, stream, sa
     qstride = _qt_stride(fn, d_qt, nf, 64 if gray else 128)
     d_status = _status_arg(fn, status, nf)
     bpp = channels if gray else 3
+    if scale > 1:
+        ow, oh = scaled_size(width, height, scale)
+        pitch, out = _pitch_out(fn, pitch, out, nf, ow, oh, bpp, "channels" if gray else "3", packed=False,
+                                dev=d_coef.device)
+        if gray:
+            rc = lib.jpgx_pixels_gpu_gray_scaled(d_coef.data_ptr(), cstride, nf, width, height, scale, d_qt.data_ptr(),
+                                                 qstride, d_status, out.data_ptr(), pitch, oh * pitch, channels,
+                                                 _stream_ptr(stream))
+        else:
+            need = int(lib.jpgx_pixels_gpu_scaled_workspace_size(width, height, sample_ratio, scale, nf))
+            ws = _workspace(need, d_coef.device, stream)
+            rc = lib.jpgx_pixels_gpu_scaled(d_coef.data_ptr(), cstride, nf, width, height, sample_ratio, scale,
+                                            d_qt.data_ptr(), qstride, d_status, out.data_ptr(), pitch, oh * pitch,
+                                            ws.data_ptr() if need else None, need, _stream_ptr(stream))
+        _check(rc, "jpgx_" + fn + "_scaled")
+        px = out.view(nf, oh, pitch)[:, :, :bpp * ow]
+        return px if bpp == 1 else px.unflatten(2, (ow, 3))
     pitch, out = _pitch_out(fn, pitch, out, nf, width, height, bpp, "channels" if gray else "3",
                             packed=not (gray or any_size), dev=d_coef.device)
     if gray:
@@ -800,7 +856,8 @@ def _pixels(fn: str, d_coef, width, height, d_qt, status, out, pitch, stream, sa
     return px if bpp == 1 else px.unflatten(2, (width, 3))
 
 
-def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False, gray: bool = False):
+def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False, gray: bool = False,
+                scale: int = 1):
     """Baseline JFIF file(s) in host memory -> RGB on `device`: decode_jpeg_coefficients' header step
     on the host for the geometry, one host-to-device copy of the bytes, then jfif_decode_gpu and
     pixels_gpu on one stream; the coefficients never leave the device.  data: bytes -> uint8 [H][W][3];
@@ -810,8 +867,12 @@ def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False,
     intervals, which one lane decodes otherwise.  any_size: files of any width and height (a list is
     still files of one geometry); the default refuses a size that is no multiple of the MCU.  gray:
     one-component files of any size (jfif_decode_gpu_gray, pixels_gpu_gray): uint8 [H][W], or
-    [n][H][W] for a list; the default refuses such files."""
+    [n][H][W] for a list; the default refuses such files.  scale 2, 4 or 8: the pixels of libjpeg's
+    decode at 1 / scale of the size (scaled_size(W, H, scale)), from the same coefficients; files of any
+    width and height, whether or not any_size is set."""
     import torch
+    scale = _scale_arg("decode_jpeg", scale)
+    any_size = any_size or scale > 1
     single = isinstance(data, (bytes, bytearray, memoryview))
     files = [bytes(data)] if single else [bytes(d) for d in data]
     if not files:
@@ -822,7 +883,7 @@ def decode_jpeg(data, device, subinterval: bool = False, any_size: bool = False,
     _, geometry, decode, pixels, what = _decode_path(files[0], subinterval, any_size, gray)
     d_files, lens = _upload_files(files, dev)
     coef, qt, status = decode(d_files, lens, *geometry)
-    px = pixels(coef, *geometry, d_qt=qt, status=status)
+    px = pixels(coef, *geometry, d_qt=qt, status=status, scale=scale)
     for rc in status.cpu().tolist():
         _check(int(rc), what)
     return px[0] if single else px

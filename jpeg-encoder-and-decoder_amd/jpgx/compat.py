@@ -18,7 +18,7 @@ import ctypes
 
 import numpy as np
 
-from . import EARG, JpgxError, coded_size, lib
+from . import EARG, JpgxError, _scale_arg, coded_size, lib
 
 c_int_p = ctypes.POINTER(ctypes.c_int)
 
@@ -115,6 +115,8 @@ def _setup(L):
     for name in ("jpgx_jfif_info_of", "jpgx_read_jfif", "jpgx_read_jfif_sub"):
         getattr(L, name + "_gray").argtypes = getattr(L, name).argtypes
     L.jpgx_pixels_host_gray.argtypes = [vp, i, i, vp, vp, ctypes.c_size_t, i, i]
+    L.jpgx_pixels_host_scaled.argtypes = [vp, i, i, i, i, vp, vp, ctypes.c_size_t, i]
+    L.jpgx_pixels_host_gray_scaled.argtypes = [vp, i, i, i, vp, vp, ctypes.c_size_t, i, i]
 
 
 _setup(lib)
@@ -401,11 +403,15 @@ def read_jfif_sub(data, sub_bytes: int = 0, tile_subs: int = 0, any_size: bool =
 
 
 def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt: np.ndarray,
-                nthreads: int = 0, pitch: int | None = None, any_size: bool = False) -> np.ndarray:
+                nthreads: int = 0, pitch: int | None = None, any_size: bool = False, scale: int = 1) -> np.ndarray:
     """jpgx_pixels_host: one frame's coefficients (read_jfif's layout) and its uint16 [2][64] zig-zag
     tables -> uint8 [H][W][3], libjpeg's default decoder's pixels, on `nthreads`
     threads (0: one per CPU).  pitch: bytes between pixel rows of the buffer the result is a view of.
-    any_size: jpgx_pixels_host_any -- coef is the coded frame's, width and height the visible frame's."""
+    any_size: jpgx_pixels_host_any -- coef is the coded frame's, width and height the visible frame's.
+    scale 2, 4 or 8: jpgx_pixels_host_scaled -- libjpeg's decode at 1 / scale of the size, uint8
+    [ceil(H / scale)][ceil(W / scale)][3]; coef, width and height as with any_size, set or not."""
+    scale = _scale_arg("pixels_host", scale)
+    any_size = any_size or scale > 1
     coef = np.ascontiguousarray(coef, np.int16)
     qt = np.ascontiguousarray(qt, np.uint16)
     cw, ch = width, height
@@ -415,6 +421,13 @@ def pixels_host(coef: np.ndarray, width: int, height: int, sample_ratio: int, qt
     nbc = (nb, nb // 2, nb // 4)[sample_ratio] if sample_ratio in (0, 1, 2) else nb
     if qt.shape != (2, 64) or width <= 0 or height <= 0 or coef.size < (nb + 2 * nbc) * 64:
         raise ValueError("pixels_host: qt [2][64], and coef must hold nb + 2 nbc blocks")
+    if scale > 1:
+        ow, oh = -(-width // scale), -(-height // scale)
+        pitch = 3 * ow if pitch is None else int(pitch)
+        buf = np.empty((oh, max(pitch, 1)), np.uint8)
+        _check(lib.jpgx_pixels_host_scaled(coef.ctypes.data, width, height, sample_ratio, scale, qt.ctypes.data,
+                                           buf.ctypes.data, pitch, nthreads), "jpgx_pixels_host_scaled")
+        return buf[:, :3 * ow].reshape(oh, ow, 3)
     pitch = 3 * width if pitch is None else int(pitch)
     buf = np.empty((height, max(pitch, 1)), np.uint8)
     _check((lib.jpgx_pixels_host_any if any_size else lib.jpgx_pixels_host)(coef.ctypes.data, width, height, sample_ratio, qt.ctypes.data, buf.ctypes.data,
@@ -441,15 +454,25 @@ def read_jfif_sub_gray(data, sub_bytes: int = 0, tile_subs: int = 0) -> dict:
 
 
 def pixels_host_gray(coef: np.ndarray, width: int, height: int, qt: np.ndarray, channels: int = 1,
-                     nthreads: int = 0, pitch: int | None = None) -> np.ndarray:
+                     nthreads: int = 0, pitch: int | None = None, scale: int = 1) -> np.ndarray:
     """jpgx_pixels_host_gray: a one-component frame's coefficients [nb][64] and its uint16 [64] zig-zag
     table -> uint8 [H][W] (channels 1) or [H][W][3] (channels 3, R = G = B): libjpeg's default decoder's
-    pixels.  pitch: bytes between pixel rows of the buffer the result is a view of."""
+    pixels.  pitch: bytes between pixel rows of the buffer the result is a view of.  scale 2, 4 or 8:
+    jpgx_pixels_host_gray_scaled -- the decode at 1 / scale of the size, [ceil(H / scale)][ceil(W / scale)]."""
+    scale = _scale_arg("pixels_host_gray", scale)
     coef = np.ascontiguousarray(coef, np.int16)
     qt = np.ascontiguousarray(qt, np.uint16)
     if qt.size != 64 or (0 < width < 65536 and 0 < height < 65536
                          and coef.size < ((width + 7) // 8) * ((height + 7) // 8) * 64):
         raise ValueError("pixels_host_gray: qt [64], and coef must hold ceil(W / 8) * ceil(H / 8) blocks")
+    if scale > 1:
+        ow, oh = max(-(-width // scale), 0), max(-(-height // scale), 0)
+        pitch = channels * ow if pitch is None else int(pitch)
+        buf = np.empty((max(oh, 1), max(pitch, 1)), np.uint8)
+        _check(lib.jpgx_pixels_host_gray_scaled(coef.ctypes.data, width, height, scale, qt.ctypes.data, buf.ctypes.data,
+                                                pitch, channels, nthreads), "jpgx_pixels_host_gray_scaled")
+        px = buf[:oh, :channels * ow]
+        return px if channels == 1 else px.reshape(oh, ow, 3)
     pitch = channels * width if pitch is None else int(pitch)
     buf = np.empty((max(height, 1), max(pitch, 1)), np.uint8)
     _check(lib.jpgx_pixels_host_gray(coef.ctypes.data, width, height, qt.ctypes.data, buf.ctypes.data, pitch,

@@ -111,7 +111,16 @@ and per size ("3840x2160", "3839x2159"):
                   frame after frame; best of 2
   bytes_equal     frame 0's coefficients == k_gray's restatement on the host (jx_gray_host_blocks), and frame 0's
                   files, standard and optimised, == jpgx_write_jfif_gray's; repeat_equal: the same after the timed calls
-Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels [--any-size
+With --pixels --scale the run times the decode at 1/2, 1/4 and 1/8 of the size (jpgx_pixels_gpu_scaled,
+jpgx_pixels_gpu_gray_scaled) beside the full-size call on the same coefficient batches: the
+three sample modes and one-component frames with 1 and 3 channels, the calls taken in turn, the
+full-size call timed before and after the scaled ones.  Per scale: the rounds, the fraction of 8 TB/s
+at the algorithmic bytes (the coefficient array read + the pixels written), the ratio to the full-size
+call's median and whether the scaled median is no longer than the full-size call's slowest round (the
+bar; reported, the exit status is the pixel checks').  Frames 0 and 7 of every scaled call are compared
+with the host twin.  Written to profiles/jfif_gpu_px_scaled.json.
+
+Usage (GPU box): python tools/jfif_gpu_bench.py [--optimize | --decode [--subinterval] | --pixels [--scale | --any-size
 [--parent-lib=PATH]] | --gray [--gray-files=DIR] | --encode-any [--kernel-stats=FILE.csv] | --encode-gray] [OUT.json]"""
 import json
 import os
@@ -528,6 +537,97 @@ def measure_px(name, d_rgb, dev):
         del coef, rgb, ws, d_want, pinned
     res["bytes_equal"] = all(m["pixels_equal"] for m in res["modes"])
     res["repeat_equal"] = all(m["repeat_equal"] for m in res["modes"])
+    return res
+
+
+def measure_px_scaled(name, d_rgb, dev):
+    """--pixels --scale: jpgx_pixels_gpu_scaled / jpgx_pixels_gpu_gray_scaled at 1/2, 1/4 and 1/8 beside the
+    full-size call (jpgx_pixels_gpu, jpgx_pixels_gpu_gray: kernels this commit does not touch) on the same
+    coefficients, in the same process, the calls taken in turn and the full-size one timed before and after
+    the scaled ones.  Frames 0 and F - 1 of every scaled call are checked against the host twin."""
+    nb = (W // 8) * (H // 8)
+    qt_host = jpgx.jfif_qt(Q)
+    d_qt = torch.from_numpy(qt_host.view(np.int16)).to(dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    L = jpgx.lib
+    res = {"input": name, "modes": []}
+    for mode in (0, 1, 2, "gray1", "gray3"):
+        gray = isinstance(mode, str)
+        sr = 0 if gray else mode
+        channels = int(mode[-1]) if gray else 3
+        flags = jpgx.FLAG_SUBSAMPLE if sr else 0
+        nbc = jpgx.chroma_blocks(W, 0, H // 8, sr, flags)
+        per = (nb + 2 * nbc) * 64
+        coef = torch.empty((F, per), dtype=torch.int16, device=dev)
+        fr = jpgx.frames(W, H, nframes=F, out_frame_stride=per)
+        p = jpgx.default_params(W, H, Q, sr, flags=flags)
+        xws = torch.empty(max(jpgx.workspace_size(fr), 1), dtype=torch.uint8, device=dev)
+        jpgx.blocks_gpu(fr, p, d_rgb, coef, xws)         # a one-component frame: the Y blocks and Y's table
+        torch.cuda.synchronize()
+        del xws
+        coef_bytes = F * (nb if gray else nb + 2 * nbc) * 128
+
+        def call(d):
+            ow, oh = jpgx.scaled_size(W, H, d)
+            pitch = (channels * ow + 7) // 8 * 8
+            out = torch.empty((F, oh, pitch), dtype=torch.uint8, device=dev)
+            if gray:
+                def run():
+                    rc = (L.jpgx_pixels_gpu_gray(coef.data_ptr(), per, F, W, H, d_qt.data_ptr(), 0, None, out.data_ptr(),
+                                                 pitch, oh * pitch, channels, stream) if d == 1 else
+                          L.jpgx_pixels_gpu_gray_scaled(coef.data_ptr(), per, F, W, H, d, d_qt.data_ptr(), 0, None,
+                                                        out.data_ptr(), pitch, oh * pitch, channels, stream))
+                    assert rc == 0, rc
+                return run, out, ow, oh, 0
+            wsb = int(L.jpgx_pixels_gpu_workspace_size(W, H, sr, F) if d == 1 else
+                      L.jpgx_pixels_gpu_scaled_workspace_size(W, H, sr, d, F))
+            ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+
+            def run():
+                rc = (L.jpgx_pixels_gpu(coef.data_ptr(), per, F, W, H, sr, d_qt.data_ptr(), 0, None, out.data_ptr(), pitch,
+                                        oh * pitch, ws.data_ptr() if wsb else None, wsb, stream) if d == 1 else
+                      L.jpgx_pixels_gpu_scaled(coef.data_ptr(), per, F, W, H, sr, d, d_qt.data_ptr(), 0, None,
+                                               out.data_ptr(), pitch, oh * pitch, ws.data_ptr() if wsb else None, wsb,
+                                               stream))
+                assert rc == 0, rc
+            return run, out, ow, oh, wsb
+
+        full, _, _, _, _ = call(1)
+        t_full = [timed(full)]
+        entry = {"mode": mode, "sample_ratio": sr, "channels": channels, "coef_bytes": coef_bytes, "scales": []}
+        for d in (2, 4, 8):
+            run, out, ow, oh, wsb = call(d)
+            out.fill_(0)
+            run()
+            torch.cuda.synchronize()
+            equal = True
+            for f in (0, F - 1):
+                c = coef[f].cpu().numpy()
+                want = (C.pixels_host_gray(c, W, H, qt_host[0], channels, HOST_THREADS, scale=d) if gray else
+                        C.pixels_host(c, W, H, sr, qt_host, HOST_THREADS, scale=d))
+                got = out[f, :, :channels * ow].cpu().numpy().reshape(want.shape)
+                equal = equal and bool(np.array_equal(got, want))
+            t = timed(run)
+            nbytes = coef_bytes + F * ow * oh * channels
+            entry["scales"].append({"scale_denom": d, "out": [ow, oh], "us": t, "workspace_bytes": wsb,
+                                    "algorithmic_bytes": nbytes,
+                                    "fraction_of_8TBps": nbytes / (median(t) * 1e-6) / 8e12, "pixels_equal": equal})
+            del out
+        t_full.append(timed(full))
+        both = sorted(t_full[0] + t_full[1])
+        full_bytes = coef_bytes + F * W * H * channels
+        entry.update({"full_us_before": t_full[0], "full_us_after": t_full[1], "full_median_us": median(both),
+                      "full_spread_us": [both[0], both[-1]], "full_algorithmic_bytes": full_bytes,
+                      "full_fraction_of_8TBps": full_bytes / (median(both) * 1e-6) / 8e12})
+        for s in entry["scales"]:
+            s["ratio_to_full"] = median(s["us"]) / median(both)
+            # the bar: no longer than the full-size call, with no margin beyond that call's own spread
+            s["within_bar"] = bool(median(s["us"]) <= both[-1])
+        res["modes"].append(entry)
+        del coef
+    res["bytes_equal"] = all(s["pixels_equal"] for m in res["modes"] for s in m["scales"])
+    res["repeat_equal"] = res["bytes_equal"]
+    res["within_bar"] = all(s["within_bar"] for m in res["modes"] for s in m["scales"])
     return res
 
 
@@ -1086,6 +1186,10 @@ def main_enc_gray(dst):
 def main():
     global PARENT, GRAY_FILES, KERNEL_STATS
     modes = ("--optimize", "--decode", "--pixels", "--subinterval", "--any-size", "--gray", "--encode-any", "--encode-gray")
+    scaled = "--scale" in sys.argv[1:]
+    if scaled:
+        sys.argv.remove("--scale")
+        assert "--pixels" in sys.argv[1:] and "--any-size" not in sys.argv[1:], "--scale goes with --pixels alone"
     for a in sys.argv[1:]:
         if a.startswith("--parent-lib="):
             # an older build has only the plain entry points: bind the one call that is timed
@@ -1107,14 +1211,14 @@ def main():
         return main_gray(args[0] if args else os.path.join(REPO, "profiles", "jfif_gpu_gray.json"))
     assert decoding or not sub, "--subinterval goes with --decode"
     assert pixels or not any_size, "--any-size goes with --pixels"
-    run = measure_enc_any if enc_any else measure_px_any if any_size else measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
+    run = measure_px_scaled if scaled else measure_enc_any if enc_any else measure_px_any if any_size else measure_px if pixels else measure_dec_sub if sub else measure_dec if decoding else \
         measure_opt if optimize else measure
     dst = args[0] if args else os.path.join(
-        REPO, "profiles", "jfif_gpu_enc_any.json" if enc_any else "jfif_gpu_px_any.json" if any_size else "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
+        REPO, "profiles", "jfif_gpu_px_scaled.json" if scaled else "jfif_gpu_enc_any.json" if enc_any else "jfif_gpu_px_any.json" if any_size else "jfif_gpu_px.json" if pixels else "jfif_gpu_dec_sub.json" if sub else
         "jfif_gpu_dec.json" if decoding else "jfif_gpu_opt.json" if optimize else "jfif_gpu.json")
     assert torch.cuda.is_available(), "needs a GPU"
     dev = torch.device("cuda:0")
-    res = {"what": "tools/jfif_gpu_bench.py" + (" --encode-any" if enc_any else " --pixels --any-size" if any_size else " --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
+    res = {"what": "tools/jfif_gpu_bench.py" + (" --encode-any" if enc_any else " --pixels --scale" if scaled else " --pixels --any-size" if any_size else " --pixels" if pixels else " --decode --subinterval" if sub else " --decode" if decoding else " --optimize" if optimize else ""), "width": W, "height": H, "frames": F, "quality": Q,
            "sample_ratio": 0, "restart_rows": 1, "device": torch.cuda.get_device_name(0),
            "version": jpgx.version(), "runs": []}
     d = torch.empty((F, H, W, 3), dtype=torch.uint8, device=dev)
@@ -1136,6 +1240,8 @@ def main():
         fh.write("\n")
     ok = all(r["bytes_equal"] and r["repeat_equal"] for r in res["runs"])
     print("bytes equal:", ok)
+    if scaled:
+        print("every scaled call within the full-size call's time:", all(r["within_bar"] for r in res["runs"]))
     sys.exit(0 if ok else 1)
 
 
